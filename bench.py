@@ -1,6 +1,12 @@
 """bench.py -- the headline benchmark of BASELINE.json on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times EXACTLY K steps and prints one JSON line whose `value` / `ms_per_step` are the headline
+below.  --dump-outputs DIR (N = 1) then writes the last timed step's result lists as DIR/labels.npy and DIR/scores.npy (seeded
+inputs: two builds can be compared output for output).  Everything else described here -- stage times, the other arithmetics
+and lengths, rooflines, oracle parity, the sustained loop, cpu_baseline, extras, and at N > 1 the one-GPU comparison,
+configs1_weak and configs[4] -- is measured with --full only (--no-sweep / --no-parity / --no-cpu-baseline / --no-extras trim it).
 
 N > 1 either under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`: RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment) or plain `python bench.py --gpus N`, which spawns its own N ranks (launch_ranks).
@@ -35,7 +41,7 @@ cpu_baseline  kind "reference": the UNMODIFIED reference's predict_batch (classi
 value_sustained  (config) the timed loop run for >= 2.5 s with the observed shader clock (ac_clock_stamp), next to the
          20-step `value`.
 extras   (N = 1, outside the timed region of `value`; --no-extras skips them) the other BASELINE configs in reduced form,
-         so that one default run measures every config: `predict_from_text` (predict_batch on raw strings, tokenisation
+         so that one --full run measures every config: `predict_from_text` (predict_batch on raw strings, tokenisation
          included, device WordPiece vs host tokenizer), `latency_ms_b1` (one predict() of one 16-token text + its CPU port),
          `cfg4` (configs[4] on one GPU: e5-large-v2 architecture, 2M x 1024 store, batch 1024, 5 steps, parity on 8 queries),
          `add_examples` (configs[3] at 6000 examples, as-wired EWC mode), `add_examples_with_encoder` (the same loop fed TEXTS:
@@ -512,7 +518,8 @@ def cpu_baseline_add_examples_reference(E, n_classes, cap=1000, seconds_hint=15.
             return time.perf_counter() - t
         one_call()                                                           # untimed warm-up (builds the head, thread pools)
         times = []
-        while not times or (sum(times) < seconds_hint and len(times) < 8):
+        # (every call consumes 32 fresh rows of the table: a fast host stops at the table's end, not past it)
+        while not times or (sum(times) < seconds_hint and len(times) < 8 and pos + 32 <= table.shape[0]):
             times.append(one_call())
         dt = sum(times) / len(times)
         stored = sum(len(v) for v in clf.memory.examples.values())
@@ -585,13 +592,13 @@ def _job_barrier():
     torch.cuda.synchronize()
 
 
-def sharded_cfg2(dev, rank, world, total_rows, steps, warmup, batch=4096, k=32, parity_queries=16):
+def sharded_cfg2(dev, rank, world, total_rows, steps, warmup, batch=4096, k=32, parity_queries=16, full=True):
     """BASELINE configs[2] on N GPUs through ShardedSearch (the production exchange): the 10M x 768 store row-sharded over
     the ranks, 4096 queries per step (4096 / N per rank, data parallel): all-gather(queries) -> local exact search of all
     4096 against the shard -> all-to-all of (exact fp64 distance, id) -> every rank merges its own block.  EXACTLY `steps`
     timed steps between barriers, max over ranks.  Rank 0 then repeats the same 4096-query batch against the WHOLE store on
     its own GPU (the one-GPU form of the same workload) -- the strong-scaling reference and, on its first `parity_queries`
-    queries, the check that the sharded ids equal the unsharded ones."""
+    queries, the check that the sharded ids equal the unsharded ones.  full=False: the timed steps and the self-check only."""
     from adaptive_classifier import index as ix
     from adaptive_classifier.sharded import ShardedSearch, shard_bounds
     lo, hi = shard_bounds(total_rows, world, rank)
@@ -617,18 +624,20 @@ def sharded_cfg2(dev, rank, world, total_rows, steps, warmup, batch=4096, k=32, 
                   "rows_total": sum(w[1] for w in who), "size_exchanges": ss.stats["size_exchanges"],
                   "message_buffers_allocated": ss.stats["buffer_allocations"], "query_gathers_prefetched": ss.stats["prefetched_gathers"]}
     # where the step goes on this rank: local search vs the rest (exchange + merge), HIP events on the current stream
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    q_all = ss.gather_queries(q_local, sizes)
-    torch.cuda.synchronize()
-    e[0].record()
-    ss._search(rows, hi - lo, DIM, q_all, k, lo)
-    e[1].record(); torch.cuda.synchronize()
-    local_ms = _max_over_ranks(e[0].elapsed_time(e[1]), dev)
+    local_ms = None
+    if full:
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        q_all = ss.gather_queries(q_local, sizes)
+        torch.cuda.synchronize()
+        e[0].record()
+        ss._search(rows, hi - lo, DIM, q_all, k, lo)
+        e[1].record(); torch.cuda.synchronize()
+        local_ms = _max_over_ranks(e[0].elapsed_time(e[1]), dev)
     ids_rank0 = Ig[:parity_queries].clone() if rank == 0 else None
     del rows, ss
     torch.cuda.empty_cache()
     one = None
-    if rank == 0:
+    if rank == 0 and full:
         P = ix.synth_unit_rows(total_rows, DIM, 1, device=dev)
         Q = ix.synth_unit_rows(batch, DIM, 2, device=dev)
         prep = ix.prepare_store(P, total_rows, DIM)
@@ -649,7 +658,7 @@ def sharded_cfg2(dev, rank, world, total_rows, steps, warmup, batch=4096, k=32, 
     dist.barrier()
     return {"ms_per_step": dt / steps * 1e3, "queries_per_s": batch * steps / dt, "rows_per_gpu": hi - lo, "self_check": self_check,
             "queries_per_gpu": qhi - qlo, "local_search_ms_max_over_ranks": local_ms,
-            "exchange_and_merge_ms": max(0.0, dt / steps * 1e3 - local_ms), "one_gpu_same_workload": one,
+            "exchange_and_merge_ms": None if local_ms is None else max(0.0, dt / steps * 1e3 - local_ms), "one_gpu_same_workload": one,
             "speedup_vs_one_gpu": None if one is None else one["ms_per_batch"] / (dt / steps * 1e3)}
 
 
@@ -1051,9 +1060,9 @@ def measure_predict_from_text(dev, clf, reps=5):
     return out
 
 
-def timed_predict(clf, ids, types, mask, steps, warmup):
+def timed_predict(clf, ids, types, mask, steps, warmup, return_last=False):
     """`warmup` untimed steps, then EXACTLY `steps` predict() steps between barrier + synchronize on both sides;
-    returns the elapsed seconds, max over ranks."""
+    returns the elapsed seconds, max over ranks (return_last: and the last timed step's result lists)."""
     for _ in range(warmup):
         preds = predict_step(clf, ids, types, mask)
     _job_barrier()
@@ -1065,7 +1074,22 @@ def timed_predict(clf, ids, types, mask, steps, warmup):
     if dist.is_initialized() and dist.get_world_size() > 1:
         dt = _max_over_ranks(dt, ids.device)
     assert len(preds) == ids.shape[0] and all(len(p) >= 1 for p in preds)
-    return dt
+    return (dt, preds) if return_last else dt
+
+
+def dump_outputs(out_dir, preds, label_to_id):
+    """--dump-outputs: the result lists of one predict() step as arrays.  labels.npy = class id of every (label, score) entry
+    (float32, [queries, max entries], -1 where a query has fewer); scores.npy = its score (float64, NaN there)."""
+    os.makedirs(out_dir, exist_ok=True)
+    width = max(len(p) for p in preds)
+    labels = np.full((len(preds), width), -1.0, np.float32)
+    scores = np.full((len(preds), width), np.nan, np.float64)
+    for i, p in enumerate(preds):
+        for j, (label, score) in enumerate(p):
+            labels[i, j] = label_to_id[label]
+            scores[i, j] = score
+    np.save(os.path.join(out_dir, "labels.npy"), labels)
+    np.save(os.path.join(out_dir, "scores.npy"), scores)
 
 
 def encoder_roofline(clf, stages, enc_flops, enc_peak, arith):
@@ -1143,12 +1167,7 @@ def main_multi(args, dev, rank, world):
     the same job is measured by rank 0 inside this run, `config.one_gpu_same_workload`).  `roofline` = every rank's shard
     sweep against N x 8 TB/s.  `configs1_weak` = the N = 1 headline workload (configs[1], predict() end to end) run data
     parallel with the 100k-row store row-sharded, 256 texts per rank per step."""
-    cfg2 = sharded_cfg2(dev, rank, world, args.sweep_rows, args.steps, args.warmup)
-    roof = None if args.no_sweep else shard_sweep_roofline(dev, rank, world, args.sweep_rows)
-    clf, hf = make_classifier(dev, rank, world)
-    ids, types, mask = synthetic_tokens(dev, rank)
-    dt = timed_predict(clf, ids, types, mask, args.steps, args.warmup)
-    stages = time_stages(clf, ids, types, mask)
+    cfg2 = sharded_cfg2(dev, rank, world, args.sweep_rows, args.steps, args.warmup, full=args.full)
     backend = dist.get_backend()
     line = {
         "metric": "predict() queries/sec + kNN GB/s vs HBM roofline, 768-d",
@@ -1173,13 +1192,18 @@ def main_multi(args, dev, rank, world):
                    "note": ("N = 1 of this file reports configs[1] (predict() end to end); the N > 1 line leads with the sharded "
                             "kNN of configs[2] because at configs[1] the kNN is 4 % of a step -- its data-parallel weak scaling is "
                             "carried as configs1_weak")},
-        "roofline": roof,
-        "configs1_weak": {"workload": "BASELINE configs[1] data parallel: 256 texts per rank per step, 100k x 768 store row-sharded "
-                                      "over the ranks, k=16 (all-gather queries, local search, all-to-all, merge), head, blend",
-                          "value": BATCH * world * args.steps / dt, "unit": "queries/s", "scaling": "weak",
-                          "ms_per_step": dt / args.steps * 1e3, "stages_ms": stages},
     }
-    if not args.no_extras:
+    if args.full:       # (the shard roofline, configs[1] data parallel and configs[4] are measured with --full only)
+        line["roofline"] = None if args.no_sweep else shard_sweep_roofline(dev, rank, world, args.sweep_rows)
+        clf, hf = make_classifier(dev, rank, world)
+        ids, types, mask = synthetic_tokens(dev, rank)
+        dt = timed_predict(clf, ids, types, mask, args.steps, args.warmup)
+        stages = time_stages(clf, ids, types, mask)
+        line["configs1_weak"] = {"workload": "BASELINE configs[1] data parallel: 256 texts per rank per step, 100k x 768 store row-sharded "
+                                             "over the ranks, k=16 (all-gather queries, local search, all-to-all, merge), head, blend",
+                                 "value": BATCH * world * args.steps / dt, "unit": "queries/s", "scaling": "weak",
+                                 "ms_per_step": dt / args.steps * 1e3, "stages_ms": stages}
+    if args.full and not args.no_extras:
         del clf
         torch.cuda.empty_cache()
         line["configs4_data_parallel_sharded"] = cfg4_multi(dev, rank, world, steps=max(2, min(args.steps, 5)), warmup=1)
@@ -1247,7 +1271,7 @@ def main():
     ap.add_argument("--no-sweep", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the on-box oracle checks (parity fields become null)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default run only: skip the other BASELINE configs carried as extra keys (latency_ms_b1, cfg4, add_examples, predict_from_text)")
+                    help="--full run: skip the other BASELINE configs carried as extra keys (latency_ms_b1, cfg4, add_examples, predict_from_text)")
     ap.add_argument("--config", default="predict", choices=["predict", "cfg4", "add_examples", "latency"],
                     help="predict = BASELINE configs[1] (the headline, default); cfg4 = configs[4] end to end on one GPU; "
                          "add_examples = configs[3] continuous-learning loop; latency = one predict() of one short text "
@@ -1256,7 +1280,18 @@ def main():
     ap.add_argument("--with-encoder", action="store_true",
                     help="--config add_examples: feed TEXTS through add_examples() (tokenizer + encoder in the loop) instead of "
                          "pre-computed embeddings")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: stage times, other arithmetics and lengths, "
+                         "rooflines, oracle parity, the sustained loop, CPU baselines and the other BASELINE configs (--no-* "
+                         "options trim this set).  Without it the run sets up, warms up, times the steps and prints the line.")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--gpus 1 predict workload: write what the last timed step returned as DIR/labels.npy (class id of each "
+                         "(label, score) entry, float32, -1 where a query has fewer entries) and DIR/scores.npy (float64, NaN there)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs is not None and (args.gpus > 1 or args.config != "predict"):
+        ap.error("--dump-outputs covers the --gpus 1 predict workload only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1305,15 +1340,54 @@ def main():
     # among 48 k ones in round 5).  gc.freeze() moves everything allocated so far into the permanent generation (what serving
     # stacks do after model load); the per-step garbage is still collected.
     import gc
-    dt_unfrozen = timed_predict(clf, ids, types, mask, args.steps, args.warmup)     # the same loop BEFORE the freeze, reported beside `value`
+    # the same loop BEFORE the freeze: reported beside `value` with --full; in every run it is also the warm-up that `value` has
+    # always been taken after
+    dt_unfrozen = timed_predict(clf, ids, types, mask, args.steps, args.warmup)
     gc.collect()
     gc.freeze()                                   # (stays in force for the rest of the process: the cpu_baseline legs run frozen too)
-    dt = timed_predict(clf, ids, types, mask, args.steps, args.warmup)
+    dt, preds = timed_predict(clf, ids, types, mask, args.steps, args.warmup, return_last=True)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, preds, clf.label_to_id)
+    del preds
+    from adaptive_classifier import _native as nv
+    arith = nv.lib().ac_gemm_get_arith()
+    lens_h = mask.sum(1).double().cpu()
+    tokens = int(getattr(clf.model, "last_tokens", BATCH * SEQ))
+    unpadded = tokens < BATCH * SEQ
+    line = {
+        "metric": "predict() queries/sec + kNN GB/s vs HBM roofline, 768-d",
+        "value": BATCH * args.steps / dt, "unit": "queries/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: bert-base-uncased arch (random init), 768-d, 100k prototypes, k=16, "
+                               "batch=256, max 32 tokens per text (RAGGED: lengths ~U[8,32], SURVEY 8d; the forward is "
+                               "padding-free, so a step runs tokens_per_step token rows, not 256 x 32), 4 classes",
+                   "batch_per_gpu": BATCH, "seq_len": SEQ, "tokens_per_step": tokens, "tokens_per_step_padded": BATCH * SEQ,
+                   "length_distribution": {"kind": "uniform integer [8, 32], first text 32", "min": int(lens_h.min()),
+                                           "mean": float(lens_h.mean()), "max": int(lens_h.max())},
+                   "padding_free": bool(unpadded),
+                   "step_pipeline": ("predict_tokens: ac_bert_encode_cls_unpad (packing + forward, the token count reaches the host through a "
+                                     "mapped slot while the embedding kernel runs: no stream synchronisation) -> search (distances, row ids) -> "
+                                     "head forward (3 launches) -> ac_predict_post (scores, hit classes, softmax, blend, top-k in one launch; the "
+                                     "packed result is copied to host-mapped memory by the last workgroup and the host waits on its flag) -> "
+                                     "_hostfast.unpack (the reference's lists, one C pass)"),
+                   "gc_frozen": True,
+                   "prototypes": NPROTO, "dim": DIM, "k": KNN_K, "classes": NCLASS, "parallelism": "dp1",
+                   "gemm_arith": ("bf16x3 split: fp32 operands = h+m+l exactly, 6 bf16 MFMA products, fp32 "
+                                  "accumulate (fp32-grade; tests/test_gemm_split_gpu.py)" if arith == 1
+                                  else "fp16x2 (AC_GEMM_ARITH=f16x2 in the environment: OPT-IN, operands rounded to 22 bits, "
+                                       "3 fp16 MFMA products; NOT fp32-grade -- see include/acamd.h)" if arith == 2
+                                  else "fp32-input MFMA")},
+    }
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
+
+    # --full: everything below is measured after the headline and only adds keys to its line
     stages = time_stages(clf, ids, types, mask)
 
     # the same loop with the fp32-input MFMA arithmetic for the large GEMMs (reported next to `value`)
-    from adaptive_classifier import _native as nv
-    arith = nv.lib().ac_gemm_get_arith()
     clf._gemm_arith = nv.AC_GEMM_F32              # per-object option (config["gemm_arith"]): no process-wide switch is touched
     dt32 = timed_predict(clf, ids, types, mask, args.steps, 2)
     clf._gemm_arith = None
@@ -1362,44 +1436,18 @@ def main():
     predict_step(clf, ids, types, mask)          # (restores last_tokens of the headline batch for the accounting below)
 
     enc_peak = BF16_MFMA_PEAK_TF / 6.0 if arith == 1 else BF16_MFMA_PEAK_TF / 3.0 if arith == 2 else F32_MFMA_PEAK_TF
-    lens_h = mask.sum(1).double().cpu()
-    tokens = int(getattr(clf.model, "last_tokens", BATCH * SEQ))
-    unpadded = tokens < BATCH * SEQ
     enc_flops = (clf.model.flops(BATCH, SEQ, tokens=float(lens_h.sum()), sum_len_sq=float((lens_h ** 2).sum()))
                  if unpadded else clf.model.flops(BATCH, SEQ))
     knn_flops = 2.0 * BATCH * clf.memory.index.ntotal * DIM
-    line = {
-        "metric": "predict() queries/sec + kNN GB/s vs HBM roofline, 768-d",
-        "value": BATCH * args.steps / dt, "unit": "queries/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: bert-base-uncased arch (random init), 768-d, 100k prototypes, k=16, "
-                               "batch=256, max 32 tokens per text (RAGGED: lengths ~U[8,32], SURVEY 8d; the forward is "
-                               "padding-free, so a step runs tokens_per_step token rows, not 256 x 32), 4 classes",
-                   "batch_per_gpu": BATCH, "seq_len": SEQ, "tokens_per_step": tokens, "tokens_per_step_padded": BATCH * SEQ,
-                   "length_distribution": {"kind": "uniform integer [8, 32], first text 32", "min": int(lens_h.min()),
-                                           "mean": float(lens_h.mean()), "max": int(lens_h.max())},
-                   "padding_free": bool(unpadded),
-                   "step_pipeline": ("predict_tokens: ac_bert_encode_cls_unpad (packing + forward, the token count reaches the host through a "
-                                     "mapped slot while the embedding kernel runs: no stream synchronisation) -> search (distances, row ids) -> "
-                                     "head forward (3 launches) -> ac_predict_post (scores, hit classes, softmax, blend, top-k in one launch; the "
-                                     "packed result is copied to host-mapped memory by the last workgroup and the host waits on its flag) -> "
-                                     "_hostfast.unpack (the reference's lists, one C pass)"),
-                   "gc_frozen": True,
+    line["config"].update({
                    "value_gc_unfrozen": BATCH * args.steps / dt_unfrozen,
-                   "prototypes": NPROTO, "dim": DIM, "k": KNN_K, "classes": NCLASS, "parallelism": "dp1",
-                   "gemm_arith": ("bf16x3 split: fp32 operands = h+m+l exactly, 6 bf16 MFMA products, fp32 "
-                                  "accumulate (fp32-grade; tests/test_gemm_split_gpu.py)" if arith == 1
-                                  else "fp16x2 (AC_GEMM_ARITH=f16x2 in the environment: OPT-IN, operands rounded to 22 bits, "
-                                       "3 fp16 MFMA products; NOT fp32-grade -- see include/acamd.h)" if arith == 2
-                                  else "fp32-input MFMA"),
                    "value_f16x2_opt_in": f16,
                    "value_f32_mfma": BATCH * args.steps / dt32,
                    "ms_per_step_f32_mfma": dt32 / args.steps * 1e3,
                    "value_full_length": BATCH * args.steps / dt_full,
                    "ms_per_step_full_length": dt_full / args.steps * 1e3,
-                   "tokens_per_step_full_length": tokens_full},
+                   "tokens_per_step_full_length": tokens_full})
+    line.update({
         "stages_ms": stages,
         "roofline_encoder": encoder_roofline(clf, stages, enc_flops, enc_peak, arith),
         "roofline_knn_batch": {"bound": "mfma", "achieved": knn_flops / stages["knn_ms"] / 1e9,
@@ -1410,7 +1458,7 @@ def main():
                                        "dense MFMA peak: at 256 queries x 100k rows the stage is "
                                        "launch- and append-bound, not MFMA-bound (the sweep kernel alone reaches 0.38 of that peak "
                                        "at 4096 x 10M: profiles/r03/knn_batch_sweep_pmc.json)"},
-    }
+    })
     if not args.no_sweep:
         free, _ = torch.cuda.mem_get_info(dev)
         n_rows = args.sweep_rows

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. per-kernel time of the default bench command (fewer steps; no CPU baseline leg)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o bench -- \
-    python $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_stdout.txt 2>&1
+    python $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/bench_stdout.txt 2>&1
 # 2. HBM traffic of the sweep kernel: separate PMC passes (FETCH_SIZE costs 3 TCC slots, WRITE_SIZE 2)
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o sweep -- \
     python $REPO/tools/knn_probe.py 10000000,768,16,32 > $OUT/pmc_fetch_stdout.txt 2>&1

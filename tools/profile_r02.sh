@@ -8,7 +8,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 T=/tmp/prof_r02; rm -rf $T; mkdir -p $T
 # 1. per-kernel time of the default bench command (no CPU-baseline leg)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T/bench -o bench -- python $REPO/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_stdout.txt 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T/bench -o bench -- python $REPO/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_stdout.txt 2>&1
 cp $(find $T/bench -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv
 grep '^{' $OUT/bench_stdout.txt > $OUT/bench_line_under_rocprof.json
 # 2. PMC passes (one counter set per run, no tracing)

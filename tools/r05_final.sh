@@ -8,13 +8,13 @@ cd $REPO
 s=$(date +%s); timeout 1500 python -m pytest tests -q -m gpu > $O/pytest_gpu_full.txt 2>&1; echo "pytest rc=$? wall $(( $(date +%s) - s )) s" >> $O/pytest_gpu_full.txt
 tail -4 $O/pytest_gpu_full.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-s=$(date +%s); timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.log; echo "bench rc=$? wall $(( $(date +%s) - s )) s"
+s=$(date +%s); timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.log; echo "bench rc=$? wall $(( $(date +%s) - s )) s"
 python -c "
 import json;d=json.load(open('$O/bench_line.json'))
 print({k:d[k] for k in ('value','ms_per_step')}, d['roofline']['frac'], d['roofline_fp16_plane']['frac'], d.get('latency_ms_b1',{}).get('value'), d.get('cfg4',{}).get('value'), d.get('add_examples',{}).get('value'), d.get('add_examples_with_encoder',{}).get('value'))
 print(d['stages_ms'], d.get('parity')); print(d['config']['value_sustained']); print(d['cpu_baseline']['value'], d['cpu_baseline']['kind'], d['cpu_baseline']['cores'])"
 cd /tmp && export TMPDIR=/tmp; T=/tmp/prof_fin5; rm -rf $T
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T -o b -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_prof_line.json 2> /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T -o b -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_prof_line.json 2> /dev/null
 cp $(find $T -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv 2>/dev/null; head -8 $O/bench_kernel_stats.csv | cut -c1-170
 T=/tmp/prof_sw5; rm -rf $T; mkdir -p $T
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_classifier_gpu.py -q -m gpu -k "residenc
 cat $O/pytest_residency.txt
 timeout 3000 python -m pytest tests -x -q -m gpu 2>&1 | tail -25 > $O/pytest_gpu_full_mid.txt
 cat $O/pytest_gpu_full_mid.txt
-timeout 900 python bench.py > $O/bench_line_mid.json 2> $O/bench_mid_stderr.txt
+timeout 900 python bench.py --full > $O/bench_line_mid.json 2> $O/bench_mid_stderr.txt
 tail -c 3000 $O/bench_mid_stderr.txt
 python - <<PY
 import json

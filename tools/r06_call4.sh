@@ -6,7 +6,7 @@ cd $REPO
 timeout 3300 python -m pytest tests -q -m gpu 2>&1 | tail -40 > $O/pytest_gpu_full_mid.txt
 cat $O/pytest_gpu_full_mid.txt
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -3
-timeout 900 python bench.py > $O/bench_line_mid.json 2> $O/bench_mid_stderr.txt
+timeout 900 python bench.py --full > $O/bench_line_mid.json 2> $O/bench_mid_stderr.txt
 tail -c 1500 $O/bench_mid_stderr.txt
 python - <<PY
 import json
@@ -16,7 +16,7 @@ print("roofline", d.get("roofline", {}).get("frac"), "encoder", d.get("roofline_
 print("add_examples", {k: d["add_examples"].get(k) for k in ("value", "examples", "steps_per_s")})
 print("cfg4", d["cfg4"]["value"], "full_length", d["config"]["value_full_length"], "unfrozen", d["config"].get("value_gc_unfrozen"))
 PY
-AC_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --sweep-rows 2000000 --no-cpu-baseline > $O/bench_line_gpus2_selfspawn_gloo_one_gpu.json 2> $O/bench_gpus2_stderr.txt
+AC_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --steps 3 --warmup 1 --sweep-rows 2000000 --no-cpu-baseline > $O/bench_line_gpus2_selfspawn_gloo_one_gpu.json 2> $O/bench_gpus2_stderr.txt
 tail -c 1200 $O/bench_gpus2_stderr.txt
 python - <<PY
 import json

@@ -7,7 +7,7 @@ cd $REPO
 s=$(date +%s); timeout 2400 python -m pytest tests -q -m gpu > $O/pytest_gpu_full.txt 2>&1; echo "pytest rc=$? wall $(( $(date +%s) - s )) s" >> $O/pytest_gpu_full.txt
 tail -4 $O/pytest_gpu_full.txt
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
-s=$(date +%s); timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.log; echo "bench rc=$? wall $(( $(date +%s) - s )) s"
+s=$(date +%s); timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench_err.log; echo "bench rc=$? wall $(( $(date +%s) - s )) s"
 python - <<PY
 import json
 d = json.load(open("$O/bench_line.json"))
@@ -19,7 +19,7 @@ print("parity", d.get("parity")); print("sustained", d["config"]["value_sustaine
 print("cpu", d["cpu_baseline"]["value"], d["cpu_baseline"]["kind"], d["cpu_baseline"]["cores"], "| add_examples cpu", (d["add_examples"].get("cpu_baseline") or {}).get("value"))
 print("full length", d["config"]["value_full_length"], "f32", d["config"]["value_f32_mfma"], "unfrozen", d["config"]["value_gc_unfrozen"])
 PY
-AC_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --steps 3 --warmup 1 --sweep-rows 2000000 --no-cpu-baseline > $O/bench_line_gpus2_selfspawn_gloo_one_gpu.json 2> /dev/null
+AC_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --steps 3 --warmup 1 --sweep-rows 2000000 --no-cpu-baseline > $O/bench_line_gpus2_selfspawn_gloo_one_gpu.json 2> /dev/null
 python -c "
 import json; d=json.load(open('$O/bench_line_gpus2_selfspawn_gloo_one_gpu.json')); print('gpus2', d['value'], d['config']['self_check'])"
 python tools/r06_layer_stamps_probe.py 2>&1 | grep -v amdgpu.ids > $O/layer_stamps.txt; cat $O/layer_stamps.txt

@@ -72,7 +72,7 @@ for n, c in sorted(out.items(), key=lambda kv: -kv[1].get("shader_cycles_per_lau
           c.get("td_busy_fraction_of_cu_cycles", 0), c.get("td_stalled_on_cache_fraction_of_cu_cycles", 0), c.get("l2_hit_rate", 0), c.get("shader_cycles_per_launch", 0)))
 PY
 T=/tmp/prof_fin6; rm -rf $T
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T -o b -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_line_under_rocprof.json 2> /dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $T -o b -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_line_under_rocprof.json 2> /dev/null
 cp $(find $T -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv 2>/dev/null; head -8 $O/bench_kernel_stats.csv | cut -c1-170
 T=/tmp/prof_sw6; rm -rf $T; mkdir -p $T
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -3,7 +3,7 @@
 Same public names as the reference package (/root/reference/src/adaptive_classifier/__init__.py:1-16)
 for the path in scope: predict()/add_examples() = encoder forward -> prototype kNN -> adaptive head
 (+ EWC-regularised AdamW training).  Arithmetic runs in libacamd.so (HIP, gfx950); see DESIGN.md.
-The multi-label classes are the N3 widening; strategic classes are outside this build.
+The multi-label classes are the N3 widening; the strategic classes live in adaptive_classifier.strategic.
 """
 from .classifier import AdaptiveClassifier
 from .ewc import EWC

@@ -137,6 +137,14 @@ _SIGNATURES = {
     "ac_head_fwd_bwd_loss": (c_int, [ctypes.POINTER(ac_head_dims), c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                      c_int64, c_int, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
+    "ac_strategic_workspace": (c_int, [ctypes.POINTER(ac_head_dims), c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ac_strategic_best_response": (c_int, [ctypes.POINTER(ac_head_dims), c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                           c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_uint64,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
+    "ac_head_fwd_bwd_strategic": (c_int, [ctypes.POINTER(ac_head_dims), c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_float, c_int, c_uint64, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
     "ac_sigmoid": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "ac_head_train_step": (c_int, [ctypes.POINTER(ac_head_dims), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_float, c_uint64,

@@ -8,8 +8,10 @@ reference for the path in scope:
   _train_new_classes :202-367 | get_memory_stats :1230 | get_example_statistics :1284 | clear_memory :1390 |
   merge_classifiers :1402-1426 | _update_adaptive_head :1524-1531 |
   save / load (format of :524-628, :764-915: config.json, examples.json, model.safetensors).
-Out of scope here and rejected loudly: ONNX runtime/export (:59-81,1031-1104), strategic mode
-(:482-522,1594-1823), Hub upload / model card (:917-1183).
+  strategic mode :106-112,193-197,369-390,392-521,1573-1830 (predict -> _predict_dual, predict_strategic, predict_robust,
+  evaluate_strategic_robustness, the strategic training step) with the best-response search and the strategic loss on the
+  device (strategic.py, csrc/strategic.hip).
+Out of scope here and rejected loudly: ONNX runtime/export (:59-81,1031-1104), Hub upload / model card (:917-1183).
 
 What changed underneath:
   * the encoder is `HipBertEncoder` / `HipModernBertEncoder` (one native call -> unit-norm CLS rows that stay in HBM);
@@ -42,6 +44,8 @@ from .ewc import EWC
 from .memory import PrototypeMemory
 from .models import AdaptiveHead, Example, ModelConfig
 from .ops import l2_normalize_rows, softmax_rows
+from .strategic import (CostFunctionFactory, StrategicEvaluator, StrategicOptimizer, best_response_batch,
+                        MASK_EXPLICIT, MASK_SEED, NUM_CANDIDATES)
 from .training import HeadTrainer
 
 logger = logging.getLogger(__name__)
@@ -110,9 +114,14 @@ class AdaptiveClassifier:
         self.id_to_label = {}
         self.train_steps = 0
         self.training_history = {}
+        self.strategic_cost_function = None
+        self.strategic_optimizer = None
+        self.strategic_evaluator = None
+        self.strategic_train_log = []   # one entry per strategic training call: {"losses", "choices"} per step (diagnostic)
         if self.config.enable_strategic_mode:
-            raise NotImplementedError("strategic mode (classifier.py:1594+) is outside the MI355X hot-path build")
-        self.strategic_mode = False
+            if not self._STRATEGIC_SUPPORTED:
+                raise NotImplementedError("strategic mode is not built for %s" % type(self).__name__)
+            self._initialize_strategic_components()
         # "as_wired": reproduce the reference, whose EWC term in _train_new_classes is identically 0
         # (SURVEY fact 3).  "intended": penalise the live head against the pre-expansion head.
         self.ewc_mode = (config or {}).get("ewc_mode", "as_wired")
@@ -128,6 +137,193 @@ class AdaptiveClassifier:
             raise ValueError("config['dropout_source'] must be 'device' or 'torch_cpu', got %r" % (self.dropout_source,))
         self.last_train_info = {}
         self.train_log = []             # one entry per head training run: {"kind", "epoch_losses", "steps"} (diagnostic)
+
+    _STRATEGIC_SUPPORTED = True
+
+    # ------------------------------------------------------------------------------ strategic mode
+    def _initialize_strategic_components(self):
+        """classifier.py:1573-1592: a cost function from config.cost_coefficients (always without feature names).  Empty or
+        None: a warning, strategic mode stays off.  A dict (no feature names), an unknown cost type -- or anything whose truth
+        value is undefined, such as a multi-element tensor -- fails inside the try: the error is logged and
+        config.enable_strategic_mode is switched off, as in the reference."""
+        try:
+            if self.config.cost_coefficients:
+                self.strategic_cost_function = CostFunctionFactory.create_cost_function(
+                    cost_type=self.config.cost_function_type, cost_coefficients=self.config.cost_coefficients)
+                self.strategic_optimizer = StrategicOptimizer(self.strategic_cost_function)
+                self.strategic_evaluator = StrategicEvaluator(self.strategic_cost_function)
+                logger.info(f"Initialized strategic mode with {self.config.cost_function_type} cost function")
+            else:
+                logger.warning("Strategic mode enabled but no cost coefficients provided")
+        except Exception as e:
+            logger.error(f"Failed to initialize strategic components: {e}")
+            self.config.enable_strategic_mode = False
+
+    @property
+    def strategic_mode(self) -> bool:
+        """Strategic mode is enabled AND a cost function was built (classifier.py:1594-1600)."""
+        return bool(self.config.enable_strategic_mode and self.strategic_cost_function is not None)
+
+    def _strategic_seed(self, salt: int) -> int:
+        """Counter-based dropout key of a strategic call (device mode): classifier seed, training call, salt."""
+        return (self._seed * 0x9E3779B97F4A7C15 + self.train_steps * 1000003 + 0x53545241 + salt * 0x2545F491) & 0x7FFFFFFFFFFFFFFF
+
+    def _perform_strategic_training(self):
+        """classifier.py:369-390: every stored example, in the memory's label order, raw embeddings (not re-normalised)."""
+        if not self.strategic_mode or not self.memory.examples:
+            return
+        embs, labs = [], []
+        for label in self.memory.examples:
+            for example in self.memory.examples[label]:
+                embs.append(example.embedding)
+                labs.append(self.label_to_id[label])
+        if embs:
+            X = torch.stack([torch.as_tensor(e, dtype=torch.float32) for e in embs])
+            self._strategic_training_step(X, torch.tensor(labs, dtype=torch.long))
+
+    def _strategic_training_step(self, all_embeddings: torch.Tensor, all_labels: torch.Tensor):
+        """classifier.py:1602-1646: a fresh AdamW (lr = learning_rate / 2, weight decay 0.01), 5 epochs over batches of
+        min(16, n) in the order of DataLoader(shuffle, Generator().manual_seed(42)), the head in train mode.  One step = the
+        batch's best responses (one search call) + the strategic loss forward/backward (one call) + clip + AdamW.
+        dropout_source "torch_cpu": every mask is drawn on the host in the reference's order -- per batch the [B, H1] / [B, H2]
+        masks of the batch forward, then per example the 50 single-row candidate forwards and the forward of its best response.
+        "device": counter-based masks keyed on (classifier seed, training call, step)."""
+        if not self.strategic_mode or self.adaptive_head is None:
+            return
+        head = self.adaptive_head
+        head.train()
+        trainer = HeadTrainer(head, lr=self.config.learning_rate * 0.5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01,
+                              max_grad_norm=1.0)
+        X = all_embeddings.to(device=trainer.device, dtype=torch.float32).contiguous()
+        y = all_labels.to(device=trainer.device, dtype=torch.int64).contiguous()
+        n = X.shape[0]
+        bs = min(16, n)
+        epoch_order = self._EpochOrder(n)
+        replay = getattr(self, "dropout_source", "device") == "torch_cpu"
+        p = AdaptiveHead.DROPOUT_P
+        H1, H2, M = trainer.dims.H1, trainer.dims.H2, NUM_CANDIDATES
+        losses, choices, step = [], [], 0
+        for _ in range(5):
+            order = epoch_order.next_epoch()
+            for i0 in range(0, n, bs):
+                idx = order[i0:i0 + bs]
+                B = int(idx.numel())
+                masks = None
+                if replay:
+                    nm = lambda r, h: torch.empty(r, h).bernoulli_(1 - p)
+                    b1, b2 = nm(B, H1), nm(B, H2)
+                    c1, c2, y1, y2 = [], [], [], []
+                    for _i in range(B):
+                        for _m in range(M):
+                            c1.append(nm(1, H1))
+                            c2.append(nm(1, H2))
+                        y1.append(nm(1, H1))
+                        y2.append(nm(1, H2))
+                    masks = ((torch.cat(c1).view(B, M, H1).to(torch.uint8), torch.cat(c2).view(B, M, H2).to(torch.uint8)),
+                             (torch.cat([b1] + y1).to(torch.uint8), torch.cat([b2] + y2).to(torch.uint8)))
+                di = idx.to(X.device)
+                loss, ch, _ = self.strategic_optimizer.strategic_loss(trainer, X.index_select(0, di), y.index_select(0, di),
+                                                                      self.config.strategic_lambda, masks=masks,
+                                                                      seed=self._strategic_seed(step), dropout_p=p)
+                losses.append(loss.clone())
+                choices.append(ch)
+                trainer.optimizer_step()
+                step += 1
+        self.strategic_train_log.append({"losses": [float(v) for v in torch.cat(losses).tolist()],
+                                         "choices": [c.tolist() for c in choices]})
+
+    def _strategic_weights(self, kind: str):
+        """(proto, head) weights of _predict_from_embedding (classifier.py:1735-1760) as the per-class fp64 vectors of
+        ac_predict_post: "strategic" 0.5 / 0.5, "robust" 0.8 / 0.2 (config)."""
+        C = len(self.id_to_label)
+        if kind == "robust":
+            wp, wh = self.config.strategic_robust_proto_weight, self.config.strategic_robust_head_weight
+        else:
+            wp, wh = self.config.strategic_prediction_proto_weight, self.config.strategic_prediction_head_weight
+        key = (kind, C, float(wp), float(wh))
+        cached = getattr(self, "_strat_w_cache", None)
+        if cached is None or cached[0] != key:
+            w = torch.tensor([[float(wp)] * C, [float(wh)] * C], dtype=torch.float64, device=self.device)
+            self._strat_w_cache = cached = (key, w)
+        return cached[1]
+
+    def _predict_from_embedding(self, emb: torch.Tensor, k: int, kind: str) -> List[Tuple[str, float]]:
+        """classifier.py:1702-1776 for one embedding [1, D] on the device: kNN with k, head top-min(k, C), fixed weights,
+        normalise, top-k -- the predict_batch form of ac_predict_post with the strategic / robust weights."""
+        if len(self.id_to_label) == 0:
+            return []
+        return self._finish_from_embeddings(emb, k, regular=False, weights=self._strategic_weights(kind))[0]
+
+    def _best_response_rows(self, emb: torch.Tensor) -> torch.Tensor:
+        """Best responses of the rows of emb against the head in eval mode (predict_strategic's classifier_func sets eval);
+        no head: a uniform classifier over the known classes."""
+        cf = self.strategic_cost_function
+        head = self.adaptive_head
+        if head is not None:
+            head.eval()
+        C = len(self.label_to_id) if self.label_to_id else 1
+        return best_response_batch(emb, head, C, cf.search_coefficients(), cf.cost_type)["Y"]
+
+    def predict_strategic(self, text: str, k: int = 5) -> List[Tuple[str, float]]:
+        """classifier.py:1648-1688: predict on the best response of the text's embedding (strategic blend weights).
+        Any failure falls back to the regular prediction, as in the reference."""
+        if not self.strategic_mode:
+            return self._predict_regular(text, k)
+        try:
+            return self._predict_strategic_emb(self._embed_device([text]), k)
+        except Exception as e:
+            logger.warning(f"Strategic prediction failed: {e}. Falling back to regular prediction.")
+            return self._predict_regular(text, k)
+
+    def _predict_strategic_emb(self, emb, k):
+        return self._predict_from_embedding(self._best_response_rows(emb), k, "strategic")
+
+    def predict_robust(self, text: str, k: int = 5) -> List[Tuple[str, float]]:
+        """classifier.py:1690-1700: the blend on the text's own embedding with the robust weights (0.8 / 0.2)."""
+        if not self.strategic_mode:
+            return self._predict_regular(text, k)
+        try:
+            return self._predict_from_embedding(self._embed_device([text]), k, "robust")
+        except Exception as e:
+            logger.warning(f"Robust prediction failed: {e}. Falling back to regular prediction.")
+            return self._predict_regular(text, k)
+
+    def _predict_dual(self, text: str, k: int = 5) -> List[Tuple[str, float]]:
+        """classifier.py:482-521 with ONE encoder call: regular top-k x 0.6 + strategic top-k x 0.4, normalise, top-k.
+        The two k-lists are merged on the host in Python floats, in the reference's insertion and stable-sort order."""
+        emb = self._embed_device([text])
+        max_classes = len(self.id_to_label) if self.id_to_label else k
+        regular_preds = self._finish_from_embeddings(emb, k, regular=True, k_proto=max_classes)[0]
+        try:
+            strategic_preds = self._predict_strategic_emb(emb, k)
+        except Exception as e:
+            logger.warning(f"Strategic prediction failed: {e}. Falling back to regular prediction.")
+            strategic_preds = regular_preds
+        rw, sw = self.config.strategic_blend_regular_weight, self.config.strategic_blend_strategic_weight
+        blended = {}
+        for label, score in regular_preds:
+            blended[label] = score * rw
+        for label, score in strategic_preds:
+            blended[label] = blended.get(label, 0) + score * sw
+        preds = sorted(blended.items(), key=lambda x: x[1], reverse=True)
+        total = sum(score for _, score in preds)
+        if total > 0:
+            preds = [(label, score / total) for label, score in preds]
+        return preds[:k]
+
+    def evaluate_strategic_robustness(self, test_texts: List[str], test_labels: List[str],
+                                      gaming_levels: List[float] = [0.0, 0.5, 1.0]) -> Dict[str, float]:
+        """classifier.py:1778-1800 / StrategicEvaluator.evaluate_robustness: the head runs in the train / eval state it is in
+        (train after add_examples, eval after a predict -- as in the reference); in train mode its dropout masks are drawn on the
+        host in the reference's order under dropout_source "torch_cpu", counter-based otherwise."""
+        if not self.strategic_mode:
+            raise ValueError("Strategic mode not enabled")
+        test_embeddings = torch.stack(self._get_embeddings(test_texts))
+        test_label_indices = torch.tensor([self.label_to_id[label] for label in test_labels])
+        self._eval_calls = getattr(self, "_eval_calls", 0) + 1
+        return self.strategic_evaluator.evaluate_robustness(
+            self.adaptive_head, test_embeddings, test_label_indices, gaming_levels,
+            replay=getattr(self, "dropout_source", "device") == "torch_cpu", seed=self._strategic_seed(1 << 20 | self._eval_calls))
 
     # ------------------------------------------------------------------------------ embeddings
     def _tokenize(self, texts: List[str]):
@@ -239,6 +435,8 @@ class AdaptiveClassifier:
                 self.adaptive_head.update_num_classes(len(self.label_to_id))
                 self.adaptive_head = self.adaptive_head.to(self.device)
             self._train_adaptive_head()
+            if self.strategic_mode and self.train_steps % self.config.strategic_training_frequency == 0:   # :196-197
+                self._perform_strategic_training()
         self.memory._rebuild_index()                 # classifier.py:200
 
     def _initialize_adaptive_head(self):
@@ -547,14 +745,14 @@ class AdaptiveClassifier:
             self._blend_w_cache = cached = (key, w)
         return cached[1]
 
-    def _blend_device(self, S, Cid, P, k: int, regular: bool):
+    def _blend_device(self, S, Cid, P, k: int, regular: bool, weights=None):
         """ac_blend_topk over one device stage -> (packed device buffer, layout).  No host synchronisation.
         packed: n[b] i32 | class[b,kk] i32 | score[b,kk] f64 (8-byte aligned)."""
         C = len(self.id_to_label)
         b = (S if S is not None else P).shape[0]
         kp = 0 if S is None else S.shape[1]
         kk = max(1, min(k, C))
-        w = self._blend_weights(regular)
+        w = self._blend_weights(regular) if weights is None else weights
         ncls = C if regular else min(k, C)
         off_cls = 4 * b
         off_val = (off_cls + 4 * b * kk + 7) // 8 * 8
@@ -602,7 +800,7 @@ class AdaptiveClassifier:
         n = n.tolist()
         return [pairs[q * kk:q * kk + min(n[q], kcap)] for q in range(b)]
 
-    def _finish(self, S, Cid, P, k: int, regular: bool, b: int = 0, check: bool = True):
+    def _finish(self, S, Cid, P, k: int, regular: bool, b: int = 0, check: bool = True, weights=None):
         """Blend + normalise + top-k of one device stage -> the reference's list of (label, score) per query.
         On the device (ac_blend_topk, one packed D2H) for up to 2048 classes; the numpy formula beyond."""
         C = len(self.id_to_label)
@@ -614,8 +812,8 @@ class AdaptiveClassifier:
             self._last_nan = bool((Sh is not None and np.isnan(Sh).any()) or (Ph is not None and np.isnan(Ph).any()))
             if self._last_nan and check:
                 self._raise_if_encoder_gave_up()
-            return self._blend(Sh, None if S is None else Cid.cpu().numpy(), Ph, k, regular)
-        out, layout = self._blend_device(S, Cid, P, k, regular)
+            return self._blend(Sh, None if S is None else Cid.cpu().numpy(), Ph, k, regular, weights=weights)
+        out, layout = self._blend_device(S, Cid, P, k, regular, weights=weights)
         return self._unpack(out.cpu().numpy(), layout, k, check)
 
     def _raise_if_encoder_gave_up(self):
@@ -638,9 +836,12 @@ class AdaptiveClassifier:
             off()
 
     def predict(self, text: str, k: int = 5) -> List[Tuple[str, float]]:
+        """classifier.py:392-413: the regular prediction, or with strategic mode on the dual one (_predict_dual)."""
         if not text:
             raise ValueError("Empty input text")
-        return self._predict_regular(text, k)
+        if not self.strategic_mode:
+            return self._predict_regular(text, k)
+        return self._predict_dual(text, k)
 
     def _predict_with_retry(self, encode, finish):
         """The predict paths' contract with the encoder's two bounded waits (HipBertEncoder.encode_cls): run the chain with
@@ -756,7 +957,8 @@ class AdaptiveClassifier:
             except Exception:       # interpreter shutdown
                 pass
 
-    def _finish_from_embeddings(self, emb: torch.Tensor, k: int, regular: bool, check: bool = True, k_proto: Optional[int] = None):
+    def _finish_from_embeddings(self, emb: torch.Tensor, k: int, regular: bool, check: bool = True, k_proto: Optional[int] = None,
+                                weights: Optional[torch.Tensor] = None):
         """Embeddings -> the reference's list of (label, score) per query.  One native call after the search and the head's
         forward (ac_predict_post: prototype scores, hit classes, F.softmax, blend, top-k, the packed result written straight
         into host-mapped memory and waited for without a stream synchronisation); the separate kernels + a D2H copy
@@ -768,7 +970,7 @@ class AdaptiveClassifier:
         if (mode == "0" or C < 1 or C > self._BLEND_DEVICE_MAX_CLASSES or b == 0
                 or k_proto > self._POST_MAX_HITS or not emb.is_cuda):
             S, Cid, P = self._device_stage(emb, k_proto)
-            return self._finish(S, Cid, P, k, regular=regular, b=b, check=check)
+            return self._finish(S, Cid, P, k, regular=regular, b=b, check=check, weights=weights)
         self._last_nan = False
         with torch.no_grad():
             D = I = head = None
@@ -784,12 +986,12 @@ class AdaptiveClassifier:
                 head = self._head_outputs(emb).contiguous()
         if D is None and head is None:
             return [[] for _ in range(b)]
-        stage, view, need, layout = self._post_launch(D, I, cmap, head, k, regular, host=mode != "2")
+        stage, view, need, layout = self._post_launch(D, I, cmap, head, k, regular, host=mode != "2", weights=weights)
         if mode == "2":                 # (A/B: the fused kernel with an ordinary D2H copy of its result)
             return self._unpack(stage[:need].cpu().numpy(), layout, k, check)
         return self._unpack(view[:need], layout, k, check)
 
-    def _post_launch(self, D, I, cmap, head, k: int, regular: bool, host: bool = True):
+    def _post_launch(self, D, I, cmap, head, k: int, regular: bool, host: bool = True, weights=None):
         """ac_predict_post over one batch's search result (D, I: may be None), class map and head outputs (may be None).
         host=True: returns when the packed result is readable in this classifier's host-mapped buffer (no stream
         synchronisation); host=False: asynchronous, the result stays in the device buffer.
@@ -799,7 +1001,7 @@ class AdaptiveClassifier:
         b = (D if D is not None else head).shape[0]
         kp = 0 if D is None else D.shape[1]
         kk = max(1, min(k, C))
-        w = self._blend_weights(regular)
+        w = self._blend_weights(regular) if weights is None else weights
         ncls = C if regular else min(k, C)
         off_cls = 4 * b
         off_val = (off_cls + 4 * b * kk + 7) // 8 * 8
@@ -818,7 +1020,7 @@ class AdaptiveClassifier:
         """predict_batch() after the encoder: device kNN + head, then the blend of :1359-1384."""
         return self._finish_from_embeddings(emb, k, regular=False)
 
-    def _blend(self, S, Cid, P, k, regular):
+    def _blend(self, S, Cid, P, k, regular, weights=None):
         """The two score-combination formulas of the reference, evaluated in fp64 like its Python floats,
         vectorised over the batch (no per-query device access).
 
@@ -838,6 +1040,8 @@ class AdaptiveClassifier:
         else:
             wp = np.full(C, 0.7)
             wh = np.full(C, 0.3)
+        if weights is not None:                         # (the strategic / robust blends: fixed per-class weights)
+            wp, wh = (w.cpu().numpy() for w in weights)
         combined = np.zeros((b, C), dtype=np.float64)
         BIG = 1 << 30
         ins = np.full((b, C), BIG, dtype=np.int64)          # insertion rank, for stable tie order
@@ -1028,15 +1232,6 @@ class AdaptiveClassifier:
     def _outside_this_build(self, what, where):
         raise NotImplementedError(f"{what} ({where}) is outside the MI355X hot-path build (predict / add_examples); "
                                   "use the reference package for it")
-
-    def predict_strategic(self, *args, **kwargs):
-        self._outside_this_build("strategic prediction", "classifier.py:1594+")
-
-    def predict_robust(self, *args, **kwargs):
-        self._outside_this_build("robust prediction", "classifier.py:1594+")
-
-    def evaluate_strategic_robustness(self, *args, **kwargs):
-        self._outside_this_build("strategic evaluation", "classifier.py:1594+")
 
     def export_onnx(self, *args, **kwargs):
         self._outside_this_build("ONNX export", "classifier.py:1031-1104")

@@ -64,8 +64,10 @@ class MultiLabelAdaptiveHead(_NativeMLP):
 
 
 class MultiLabelAdaptiveClassifier(AdaptiveClassifier):
-    """Multi-label AdaptiveClassifier: several labels per text, threshold-based decisions."""
+    """Multi-label AdaptiveClassifier: several labels per text, threshold-based decisions.
+    Strategic mode is not built for this class: `enable_strategic_mode` in its config still raises NotImplementedError."""
 
+    _STRATEGIC_SUPPORTED = False
     LOSS_KIND = LOSS_CE_SIGMOID          # what the inherited new-class loop computes on a sigmoid head
 
     def __init__(self, model_name: str, device: Optional[str] = None, config: Optional[Dict[str, Any]] = None,

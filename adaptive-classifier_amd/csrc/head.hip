@@ -120,6 +120,57 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const float* z, const
     }
 }
 
+// StrategicOptimizer.strategic_loss over 2B rows [x; y] (one block, a wave per row): rows r < B carry the batch's mean CE,
+// rows B + i the best response of example i, counted (weight lambda) only when argmax(z) != label (torch.argmax: first
+// maximum, NaN maximal).  loss = sum_{r<B} ce_r / B + lambda * (sum_{mispredicted i} ce_{B+i}) / B; dz the gradient of it.
+__global__ __launch_bounds__(256) void strategic_loss_kernel(const float* z, const int64_t* y, int B, int C, float lambda,
+                                                             float* dz, float* rowloss, float* loss, int32_t* mispred) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float invB = 1.f / (float)B;
+    for (int r = wave; r < 2 * B; r += 4) {
+        const float* zr = z + (size_t)r * C;
+        const int64_t yb = y[r < B ? r : r - B];
+        float mx = -INFINITY;
+        int am = 0x7fffffff;                 // first index of the maximum (NaN first if any)
+        bool nan = false;
+        for (int c = lane; c < C; c += 64) {
+            const float v = zr[c];
+            mx = fmaxf(mx, v);
+            if (v != v) { if (!nan) { nan = true; am = c; } }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        int anynan = nan ? 1 : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) anynan |= __shfl_xor(anynan, o);
+        if (!anynan) {
+            for (int c = lane; c < C; c += 64) if (zr[c] == mx) { am = c; break; }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) am = min(am, __shfl_xor(am, o));
+        const bool mis = r >= B && (int64_t)am != yb;
+        const float wgt = r < B ? invB : (mis ? lambda * invB : 0.f);
+        float sum = 0.f;
+        for (int c = lane; c < C; c += 64) sum += expf(zr[c] - mx);
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) sum += __shfl_xor(sum, o);
+        for (int c = lane; c < C; c += 64)
+            dz[(size_t)r * C + c] = (expf(zr[c] - mx) / sum - (c == yb ? 1.f : 0.f)) * wgt;
+        if (lane == 0) {
+            rowloss[r] = (r < B || mis) ? (mx + logf(sum)) - zr[yb] : 0.f;
+            if (r >= B && mispred) mispred[r - B] = mis ? 1 : 0;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        float s = 0.f, t = 0.f;
+        for (int r = lane; r < B; r += 64) { s += rowloss[r]; t += rowloss[B + r]; }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { s += __shfl_xor(s, o); t += __shfl_xor(t, o); }
+        if (lane == 0) *loss = s * invB + lambda * (t * invB);
+    }
+}
+
 // torch.sigmoid over n elements (multilabel.py:43)
 __global__ __launch_bounds__(256) void sigmoid_kernel(const float* in, int64_t n, float* out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -448,12 +499,15 @@ extern "C" int ac_head_forward(const ac_head_dims* dims, const float* d_params, 
 
 namespace {
 
+// internal loss kind of ac_head_fwd_bwd_strategic (never a value of the public AC_LOSS_* set)
+constexpr int kLossStrategic = 0x7001;
+
 // forward (train mode) + CE + backward into G; masks either explicit (uint8, 1 = keep) or generated
 // in-kernel from `seed` when dropout_p > 0 and no mask is given with use_seed.
 int head_fwd_bwd(const ac_head_dims& d, const float* P, const float* X, int64_t ldx, const int64_t* y,
                  const uint8_t* mask1, const uint8_t* mask2, float dropout_p, bool use_seed, uint64_t seed, int B,
                  float* d_loss, float* G, char* ws, const HeadWs& w, hipStream_t stream, int loss_kind = AC_LOSS_CE,
-                 const float* targets = nullptr, int64_t ldt = 0) {
+                 const float* targets = nullptr, int64_t ldt = 0, float strat_lambda = 0.f, int32_t* mispred = nullptr) {
     const HeadOffsets o = head_offsets(d);
     float* a1 = (float*)(ws + w.a1);
     float* a2 = (float*)(ws + w.a2);
@@ -474,7 +528,7 @@ int head_fwd_bwd(const ac_head_dims& d, const float* P, const float* X, int64_t 
     rc = ac::linear_f32(a1, d.H1, P + o.w2, d.H1, P + o.b2, nullptr, 0, a2, d.H2, B, d.H2, d.H1, 1, mask2, s2, stream, p2,
                         seed ^ 0xA5A5A5A5A5A5A5A5ull);
     if (rc) return rc;
-    const bool top = d.C <= kTopMaxC && B <= kTopMaxB;
+    const bool top = loss_kind != kLossStrategic && d.C <= kTopMaxC && B <= kTopMaxB;
     if (top) {
         // logits + loss + dz + gW3 + gb3 + d2 + gb2 in one launch (see head_top_kernel)
         const size_t stage_bytes = ((size_t)B + d.C) * d.H2 * sizeof(float);
@@ -491,8 +545,12 @@ int head_fwd_bwd(const ac_head_dims& d, const float* P, const float* X, int64_t 
     } else {
         rc = ac::linear_f32(a2, d.H2, P + o.w3, d.H2, P + o.b3, nullptr, 0, z, d.C, B, d.C, d.H2, 0, nullptr, 1.f, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(loss_fwd_bwd_kernel, dim3(1), dim3(256), 0, stream, z, y, targets, ldt, B, d.C, loss_kind, dz,
-                           rowloss, d_loss);
+        if (loss_kind == kLossStrategic)      // B = 2 x the batch: [x; y] rows
+            hipLaunchKernelGGL(strategic_loss_kernel, dim3(1), dim3(256), 0, stream, z, y, B / 2, d.C, strat_lambda, dz, rowloss,
+                               d_loss, mispred);
+        else
+            hipLaunchKernelGGL(loss_fwd_bwd_kernel, dim3(1), dim3(256), 0, stream, z, y, targets, ldt, B, d.C, loss_kind, dz,
+                               rowloss, d_loss);
         AC_LAUNCH_CHECK();
         // backward.  dW = dY^T A  (transA=1: dY stored [B,out] is the [K,M] layout), dA = dY W gated
         // by relu'/dropout (a != 0 ? scale : 0).
@@ -575,6 +633,23 @@ extern "C" int ac_head_fwd_bwd_loss(const ac_head_dims* dims, const float* d_par
     AC_REQUIRE(d_ws && ws_bytes >= w.total, AC_EWORKSPACE, "head_fwd_bwd_loss: workspace %zu < %zu", ws_bytes, w.total);
     return head_fwd_bwd(*dims, d_params, d_X, ldx, d_y, d_mask1, d_mask2, dropout_p, false, 0, B, d_loss, d_grads,
                         (char*)d_ws, w, (hipStream_t)stream_, loss_kind, d_targets, ldt);
+}
+
+extern "C" int ac_head_fwd_bwd_strategic(const ac_head_dims* dims, const float* d_params, const float* d_X2, int64_t ldx,
+                                         const int64_t* d_y, const uint8_t* d_mask1, const uint8_t* d_mask2, float dropout_p,
+                                         int use_seed, uint64_t dropout_seed, int B, float lambda, float* d_loss, float* d_grads,
+                                         int32_t* d_mispred, void* d_ws, size_t ws_bytes, ac_stream_t stream_) {
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    AC_REQUIRE(d_params && d_X2 && d_y && d_loss && d_grads && B > 0 && ldx >= dims->D, AC_EINVAL,
+               "head_fwd_bwd_strategic: bad arguments");
+    AC_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, AC_EINVAL, "head_fwd_bwd_strategic: dropout_p=%f", dropout_p);
+    AC_REQUIRE((d_mask1 == nullptr) == (d_mask2 == nullptr) && !(use_seed && d_mask1), AC_EINVAL,
+               "head_fwd_bwd_strategic: give both masks or use_seed, not both");
+    const HeadWs w = head_ws(*dims, 2 * B);
+    AC_REQUIRE(d_ws && ws_bytes >= w.total, AC_EWORKSPACE, "head_fwd_bwd_strategic: workspace %zu < %zu", ws_bytes, w.total);
+    return head_fwd_bwd(*dims, d_params, d_X2, ldx, d_y, d_mask1, d_mask2, dropout_p, use_seed != 0, dropout_seed, 2 * B, d_loss,
+                        d_grads, (char*)d_ws, w, (hipStream_t)stream_, kLossStrategic, nullptr, 0, lambda, d_mispred);
 }
 
 extern "C" int ac_sigmoid(const float* d_in, int64_t n, float* d_out, ac_stream_t stream) {

@@ -443,6 +443,46 @@ int ac_head_train_epoch(const ac_head_dims* dims, float* d_params, float* d_m,
                         float* d_out, float* d_loss_accum,
                         void* d_ws, size_t ws_bytes, int* steps_done, ac_stream_t stream);
 
+/* Strategic classification (strategic.py): the batched best-response search and the strategic training loss.
+ *
+ * ac_strategic_best_response: for b queries x and ONE shared candidate table of M <= 64 single-coordinate moves
+ * (d_cand_feat[m], d_cand_delta[m]; a feature outside [0, D) is the identity move -- entry 0 by convention), candidate m of
+ * query q is y = x with y[f] = fl(x[f] + delta).  Its utility is max(softmax(head(y))) - cost, cost = relu(coef[f] * dy),
+ * dy = fl(y[f] - x[f]), for both cost types (AC_STRAT_COST_*: the separable c.y - c.x and the linear alpha.(y - x) both reduce
+ * to that term for a single-coordinate move).  Per query: d_choice = the FIRST candidate of maximal utility (strict >, NaN never
+ * wins; all NaN -> 0), d_util its utility, d_Y [b, ldy] the chosen row y; optional d_util_all [b, M] every utility and
+ * d_logits [b, C] the chosen candidate's logits (same masks).  d_params NULL: no head, f is uniform (utility 1/C - cost).
+ * Dropout (train-mode head): mask_mode AC_STRAT_MASK_NONE (eval), _EXPLICIT (uint8 1 = keep, d_mask1 [b, M, H1],
+ * d_mask2 [b, M, H2]), _SEED (counter-based in-kernel, element index ((q M + m) H + h), layer 2 under seed ^ 0xA5A5A5A5A5A5A5A5
+ * as the head's training).  Launches: layer 1 at x (one [b, D] x [D, H1] GEMM), the rank-1 candidate rows
+ * z1(x) + dy W1[:, f] with ReLU + mask 1, layer 2 as one [b M, H1] x [H1, H2] GEMM with bias + ReLU + mask 2 in its epilogue,
+ * then layer 3 + softmax max + cost + first-wins argmax + the y row in one kernel.  C <= 2048.
+ * Workspace: ac_strategic_workspace. */
+#define AC_STRAT_COST_SEPARABLE 0
+#define AC_STRAT_COST_LINEAR    1
+#define AC_STRAT_MASK_NONE      0
+#define AC_STRAT_MASK_EXPLICIT  1
+#define AC_STRAT_MASK_SEED      2
+#define AC_STRAT_MAX_CANDIDATES 64
+int ac_strategic_workspace(const ac_head_dims* dims, int b, int M, size_t* bytes);
+int ac_strategic_best_response(const ac_head_dims* dims, const float* d_params, const float* d_X, int64_t ldx, int b,
+                               const int32_t* d_cand_feat, const float* d_cand_delta, int M,
+                               const float* d_coef, int cost_type, int mask_mode, const uint8_t* d_mask1,
+                               const uint8_t* d_mask2, float dropout_p, uint64_t dropout_seed,
+                               int32_t* d_choice, float* d_util, float* d_util_all, float* d_Y, int64_t ldy,
+                               float* d_logits, void* d_ws, size_t ws_bytes, ac_stream_t stream);
+
+/* StrategicOptimizer.strategic_loss (strategic.py) forward + backward over 2B rows X2 = [x; y] (train mode, per-row dropout:
+ * explicit uint8 masks [2B, H1] / [2B, H2], or -- both NULL and use_seed = 1 -- the head's counter-based masks under
+ * dropout_seed):  loss = CE_mean(x rows) + lambda * sum_{i: argmax(z(y_i)) != y_i} CE(y_i) / B, the misprediction test on the
+ * device from the y rows' logits (first maximum, NaN counts as maximal like torch.argmax).  d_grads receives the gradient of
+ * that loss, d_loss the scalar, d_mispred (optional) int32 [B] the test.  Workspace: ac_head_workspace(dims, 2 B).
+ * The clip + AdamW step after it is ac_ewc_adamw_step without EWC. */
+int ac_head_fwd_bwd_strategic(const ac_head_dims* dims, const float* d_params, const float* d_X2, int64_t ldx,
+                              const int64_t* d_y, const uint8_t* d_mask1, const uint8_t* d_mask2, float dropout_p,
+                              int use_seed, uint64_t dropout_seed, int B, float lambda, float* d_loss, float* d_grads,
+                              int32_t* d_mispred, void* d_ws, size_t ws_bytes, ac_stream_t stream);
+
 /* F.softmax(logits, dim=1) over [B, C] rows (classifier.py:435,1345). */
 int ac_softmax_rows(const float* d_in, int B, int C, float* d_out,
                     ac_stream_t stream);

@@ -1,0 +1,206 @@
+"""GPU suite: strategic mode on MI355X.
+  * ac_strategic_best_response against an fp64 restatement written here (eval mode and explicit masks; both cost types; NaN
+    rows; no head): the choice must be the fp64 one wherever the fp64 top-2 margin exceeds BOUND, else its utility within
+    BOUND of the maximum;
+  * ac_head_fwd_bwd_strategic (loss + gradient) against fp64 autograd on the same masks;
+  * the classifier against the unmodified reference (tests/golden/strategic_bert_mini.json, gen_strategic.py): the replayed
+    strategic training makes the same best-response choices, losses within 1e-5, parameters within 1e-4; predict (dual),
+    predict_strategic, predict_robust and evaluate_strategic_robustness equal;
+  * device-mode strategic training is deterministic for a seed."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+BOUND = 2e-5          # |utility - fp64 utility|: fp32 GEMM sums at D = 768 (see csrc/strategic.hip for the cost term)
+
+
+def _head(D, H1, H2, C, dev, seed):
+    from adaptive_classifier import AdaptiveHead
+    head = AdaptiveHead(D, C, [H1, H2]).to(dev)
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for p in head.parameters():                 # non-zero biases, weights of the trained scale
+            p.copy_((torch.rand(p.shape, generator=g) - 0.5) * (2.0 / p.shape[-1] ** 0.5))
+    head.flat_params()
+    return head
+
+
+def _fp64_utilities(head, X, coef, masks, p=0.1):
+    from adaptive_classifier.strategic import candidate_table
+    feat, delta = candidate_table(X.shape[1])
+    b, D = X.shape
+    M = feat.numel()
+    Y = X.unsqueeze(1).repeat(1, M, 1)                      # fp32, the reference's candidate rows
+    for m in range(1, M):
+        f = int(feat[m])
+        Y[:, m, f] = X[:, f] + delta[m]
+    dy = torch.stack([Y[:, m, int(feat[m])] - X[:, int(feat[m])] if feat[m] >= 0 else torch.zeros(b, device=X.device)
+                      for m in range(M)], 1).double()
+    cf = torch.stack([coef[int(f)] if f >= 0 else torch.zeros((), device=X.device) for f in feat]).double()
+    cost = torch.relu(dy * cf[None, :])
+    if head is None:
+        return None, cost, Y
+    lin = head.linears()
+    W = [(l.weight.double(), l.bias.double()) for l in lin]
+    a = torch.relu(Y.double() @ W[0][0].T + W[0][1])
+    if masks is not None:
+        a = a * masks[0].double() / (1 - p)
+    a = torch.relu(a @ W[1][0].T + W[1][1])
+    if masks is not None:
+        a = a * masks[1].double() / (1 - p)
+    z = a @ W[2][0].T + W[2][1]
+    return torch.softmax(z, -1).max(-1).values - cost, cost, Y
+
+
+@pytest.mark.parametrize("dims", [(64, 64, 32), (768, 768, 384)])
+@pytest.mark.parametrize("C", [1, 2, 7, 33])
+@pytest.mark.parametrize("b", [1, 17, 256])
+def test_best_response_kernel_matches_fp64(cuda_dev, dims, C, b):
+    from adaptive_classifier.strategic import COST_LINEAR, COST_SEPARABLE, MASK_EXPLICIT, best_response_batch
+    D, H1, H2 = dims
+    head = _head(D, H1, H2, C, cuda_dev, seed=D + C)
+    g = torch.Generator().manual_seed(b)
+    X = torch.nn.functional.normalize(torch.randn(b, D, generator=g), dim=1).to(cuda_dev)
+    coef = (torch.randn(D, generator=g) * 0.05).to(cuda_dev)
+    M = 50
+    masks = ((torch.rand(b, M, H1, generator=g) >= 0.1).to(torch.uint8).to(cuda_dev),
+             (torch.rand(b, M, H2, generator=g) >= 0.1).to(torch.uint8).to(cuda_dev))
+    for mode, mk in ((0, None), (MASK_EXPLICIT, masks)):
+        for ct in (COST_SEPARABLE, COST_LINEAR):
+            r = best_response_batch(X, head, coef=coef, cost_type=ct, mask_mode=mode, masks=mk, want_all=True)
+            u64, _, Y = _fp64_utilities(head, X, coef, mk)
+            got_all = r["util_all"].double()
+            assert (got_all - u64).abs().max().item() <= BOUND
+            top2 = u64.topk(2 if C > 0 else 1, dim=1).values
+            want = u64.argmax(1)                                  # (first maximum)
+            ch = r["choice"].long()
+            sure = (top2[:, 0] - top2[:, 1]) > 2 * BOUND
+            assert torch.equal(ch[sure], want[sure])
+            assert ((u64.max(1).values - u64.gather(1, ch[:, None])[:, 0]).abs() <= 2 * BOUND).all()
+            assert torch.equal(r["Y"], Y[torch.arange(b), ch])
+            assert torch.equal(r["util"], r["util_all"].gather(1, ch[:, None].int().long())[:, 0])
+
+
+def test_best_response_nan_rows_and_no_head(cuda_dev):
+    from adaptive_classifier.strategic import best_response_batch
+    head = _head(64, 64, 32, 5, cuda_dev, seed=1)
+    X = torch.nn.functional.normalize(torch.randn(4, 64), dim=1).to(cuda_dev)
+    X[2] = float("nan")
+    coef = torch.full((64,), 0.05, device=cuda_dev)
+    r = best_response_batch(X, head, coef=coef)
+    assert r["choice"][2].item() == 0 and torch.isnan(r["Y"][2]).all() and torch.isnan(r["util"][2])
+    assert torch.isfinite(r["Y"][[0, 1, 3]]).all()
+    # no head: f uniform, utility 1/C - cost; x itself (cost 0) is the first maximum
+    r0 = best_response_batch(X[[0, 1, 3]], None, 4, coef=coef, want_all=True)
+    assert r0["choice"].tolist() == [0, 0, 0] and torch.equal(r0["Y"], X[[0, 1, 3]])
+    assert torch.allclose(r0["util"], torch.full((3,), 0.25, device=cuda_dev))
+    assert (r0["util_all"] <= 0.25).all()
+
+
+def test_strategic_loss_and_gradients_match_fp64_autograd(cuda_dev):
+    import ctypes
+    from adaptive_classifier import _native as nv
+    from adaptive_classifier.training import HeadTrainer
+    D, H1, H2, C, B, lam, p = 64, 64, 32, 7, 9, 0.7, 0.1
+    head = _head(D, H1, H2, C, cuda_dev, seed=3)
+    tr = HeadTrainer(head)
+    g = torch.Generator().manual_seed(5)
+    X2 = torch.randn(2 * B, D, generator=g).to(cuda_dev)
+    y = torch.randint(0, C, (B,), generator=g).to(cuda_dev)
+    m1 = (torch.rand(2 * B, H1, generator=g) >= p).to(torch.uint8).to(cuda_dev)
+    m2 = (torch.rand(2 * B, H2, generator=g) >= p).to(torch.uint8).to(cuda_dev)
+    mis = torch.empty(B, dtype=torch.int32, device=cuda_dev)
+    ws = tr._workspace(2 * B)
+    nv.check(nv.lib().ac_head_fwd_bwd_strategic(ctypes.byref(tr.dims), nv.ptr(tr.flat), nv.ptr(X2), D, nv.ptr(y), nv.ptr(m1),
+                                                nv.ptr(m2), p, 0, 0, B, lam, nv.ptr(tr.loss), nv.ptr(tr.grads), nv.ptr(mis),
+                                                nv.ptr(ws), ws.numel(), nv.stream_ptr(cuda_dev)), "ac_head_fwd_bwd_strategic")
+    torch.cuda.synchronize()
+    P = [t.detach().double().clone().requires_grad_(True) for l in head.linears() for t in (l.weight, l.bias)]
+    a = torch.relu(X2.double() @ P[0].T + P[1]) * m1.double() / (1 - p)
+    a = torch.relu(a @ P[2].T + P[3]) * m2.double() / (1 - p)
+    z = a @ P[4].T + P[5]
+    reg = torch.nn.functional.cross_entropy(z[:B], y)
+    pred = z[B:].argmax(1)
+    wrong = pred != y
+    strat = torch.nn.functional.cross_entropy(z[B:], y, reduction="none")[wrong].sum() / B
+    loss = reg + lam * strat
+    loss.backward()
+    assert mis.bool().tolist() == wrong.tolist() and 0 < int(wrong.sum()) < B
+    assert abs(tr.loss.item() - loss.item()) <= 1e-5
+    gw = torch.cat([t.grad.flatten() for t in P])
+    assert (tr.grads.double() - gw).abs().max().item() <= 1e-5
+
+
+def _standin():
+    from oracle import hub_standin
+    hub_standin.install()
+    return hub_standin
+
+
+def _same(got, want, tol=1e-5):
+    assert [l for l, _ in got] == [l for l, _ in want], (got, want)
+    assert max([abs(a - b) for (_, a), (_, b) in zip(got, want)] + [0.0]) <= tol, (got, want)
+
+
+def test_classifier_replays_the_reference(cuda_dev):
+    from adaptive_classifier import AdaptiveClassifier
+    st = _standin()
+    try:
+        ex = json.load(open(os.path.join(GOLD, "strategic_bert_mini.json")))
+        head_ref = np.load(os.path.join(GOLD, "strategic_bert_mini_head.npz"))
+        torch.manual_seed(0)
+        np.random.seed(0)
+        clf = AdaptiveClassifier(ex["model_name"], device="cuda:0", config=dict(ex["config"], dropout_source="torch_cpu"))
+        assert clf.strategic_mode
+        clf.add_examples([t for t, _ in ex["train"]], [l for _, l in ex["train"]])
+        log = clf.strategic_train_log
+        assert len(log) == 1
+        assert [c for step in log[0]["choices"] for c in step] == ex["train_choices"]
+        assert len(log[0]["losses"]) == len(ex["step_losses"])
+        for got, want in zip(log[0]["losses"], ex["step_losses"]):
+            assert abs(got - want) <= 1e-5, (got, want)
+        sd = clf.adaptive_head.state_dict()
+        for k, v in head_ref.items():
+            assert np.abs(sd[k].cpu().numpy() - v).max() <= 1e-4, k
+        k = ex["k"]
+        for i, q in enumerate(ex["queries"]):
+            _same(clf.predict(q, k=k), ex["predict"][i])
+            _same(clf.predict_strategic(q, k=k), ex["predict_strategic"][i])
+            _same(clf.predict_robust(q, k=k), ex["predict_robust"][i])
+        torch.manual_seed(ex["eval_seed"])
+        assert not clf.adaptive_head.training
+        assert clf.evaluate_strategic_robustness(ex["eval_texts"], ex["eval_labels"], [0.0, 0.5, 1.0]) == ex["robustness"]
+    finally:
+        st.uninstall()
+
+
+def test_strategic_off_predicts_like_regular_and_device_training_is_deterministic(cuda_dev):
+    from adaptive_classifier import AdaptiveClassifier
+    st = _standin()
+    try:
+        ex = json.load(open(os.path.join(GOLD, "strategic_bert_mini.json")))
+        texts, labels = [t for t, _ in ex["train"]], [l for _, l in ex["train"]]
+        plain = AdaptiveClassifier(ex["model_name"], device="cuda:0")
+        readme = AdaptiveClassifier(ex["model_name"], device="cuda:0", config={"enable_strategic_mode": True})   # no coefficients
+        assert not readme.strategic_mode
+        for c in (plain, readme):
+            c.add_examples(texts, labels)
+        for q in ex["queries"]:
+            assert readme.predict(q, k=3) == plain.predict(q, k=3)
+            assert readme.predict_strategic(q, k=3) == plain.predict(q, k=3)
+        with pytest.raises(ValueError):
+            readme.evaluate_strategic_robustness(texts[:2], labels[:2])
+        runs = []
+        for _ in range(2):
+            c = AdaptiveClassifier(ex["model_name"], device="cuda:0", config=ex["config"])
+            c.add_examples(texts, labels)
+            runs.append((c.strategic_train_log[0], c.adaptive_head.flat_params().clone(), c.predict(ex["queries"][0], k=3)))
+        assert runs[0][0] == runs[1][0] and torch.equal(runs[0][1], runs[1][1]) and runs[0][2] == runs[1][2]
+        assert all(np.isfinite(runs[0][0]["losses"]))
+    finally:
+        st.uninstall()

@@ -7,7 +7,8 @@ Protocol kept (reference call sites in /root/reference/src/adaptive_classifier/m
 Rows live in one resident, row-major fp32 device matrix with a 16-byte aligned, zero padded
 leading dimension (growth by doubling, so `add` is amortised O(1) like faiss's vector).
 search() is one call into the C ABI (`ac_knn_l2_topk`): exact squared L2, ascending, ties to
-the lower id.
+the lower id.  HipFlatIPIndex is the same store searched by inner product (`ac_knn_ip_topk`,
+faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.
 """
 import ctypes
 
@@ -94,6 +95,11 @@ def knn_l2_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=Non
     """
     if prepared is not None and batch_applies(N, Q.shape[0], k):
         return _knn_l2_topk_batch(P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out)
+    return _knn_topk_x("ac_knn_l2_topk_x", P, N, D, Q, k, row_offset, out, workspace, stats, exact_out)
+
+
+def _knn_topk_x(entry, P, N, D, Q, k, row_offset, out, workspace, stats, exact_out):
+    """the fp32-sweep search of either metric: `entry` = ac_knn_l2_topk_x or ac_knn_ip_topk_x (same arguments, same workspace)"""
     nv.require_gpu()
     assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
     assert P.stride(1) == 1 and Q.stride(1) == 1
@@ -108,12 +114,26 @@ def knn_l2_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=Non
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = nv.lib().ac_knn_l2_topk_x(
+        rc = getattr(nv.lib(), entry)(
             nv.ptr(P), N, P.stride(0), D, nv.ptr(Q), nq, Q.stride(0), k, row_offset,
             nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(),
             nv.ptr(stats), nv.stream_ptr(dev))
-    nv.check(rc, "ac_knn_l2_topk_x")
+    nv.check(rc, entry)
     return outD, outI
+
+
+def knn_ip_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=None, exact_out=None):
+    """Exact inner-product top-k (`ac_knn_ip_topk_x`, faiss.IndexFlatIP.search): the k rows with the largest p.q per query,
+    descending, ties to the lower id; rows need not be normalised.  Arguments and workspace as `knn_l2_topk` (the fp32 sweeps
+    serve every shape: there is no prepared form).  Returns (values fp32 [nq,k], ids int64 [nq,k]); k > N pads with (-FLT_MAX, -1)."""
+    return _knn_topk_x("ac_knn_ip_topk_x", P, N, D, Q, k, row_offset, out, workspace, stats, exact_out)
+
+
+def knn_ip_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None):
+    """(exact fp64 inner products [nq,k] descending, ids [nq,k]): what a row shard contributes to a sharded IP search."""
+    ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
+    _, I = knn_ip_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex)
+    return ex, I
 
 
 def _knn_l2_topk_batch(P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out):
@@ -151,12 +171,15 @@ def knn_l2_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, p
     return ex, I
 
 
-class HipFlatL2Index:
-    """Drop-in for faiss.IndexFlatL2 as used by PrototypeMemory.
+class _HipFlatIndex:
+    """The flat store both metrics share: resident rows, lazy upload, compaction, in-place updates.  `metric` ("l2" / "ip")
+    picks the search entry point; only the L2 index ever prepares an fp16 plane.
 
     Host-side bookkeeping (add / ntotal / remove_ids) works without a GPU: added rows are queued on
     the host and uploaded in one copy when the device matrix is first needed.  search() has no CPU
     implementation -- without a GPU it raises."""
+
+    metric = None
 
     def __init__(self, d, device=None):
         self.d = int(d)
@@ -323,6 +346,11 @@ class HipFlatL2Index:
             q = q.unsqueeze(0)
         if q.stride(-1) != 1:
             q = q.contiguous()
+        if self.metric == "ip":                 # the fp32 sweeps for every shape; no plane is ever prepared
+            need = knn_workspace_bytes(self._n, self.d, q.shape[0], k)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            return knn_ip_topk(self._store, self._n, self.d, q, k, workspace=self._ws, stats=self._stats)
         batch = batch_applies(self._n, q.shape[0], k, auto=True)
         if batch and self._prepared is None:
             # preparing costs two passes over the rows (~0.14 s at 10M x 768): at once for a many-query search (it pays within
@@ -351,6 +379,33 @@ class HipFlatL2Index:
     def exact_fallbacks(self):
         """Queries of the last search() that needed the exact fp64 fallback sweep."""
         return 0 if self._stats is None else int(self._stats[0].item())
+
+
+class HipFlatL2Index(_HipFlatIndex):
+    """Drop-in for faiss.IndexFlatL2 as used by PrototypeMemory: exact squared L2, ascending, ties to the lower id."""
+    metric = "l2"
+
+
+class HipFlatIPIndex(_HipFlatIndex):
+    """Drop-in for faiss.IndexFlatIP: exact inner product, descending, ties to the lower id (`ac_knn_ip_topk`).  Rows need not
+    be normalised; for L2-normalised rows this is the cosine search.  Same protocol and storage as HipFlatL2Index."""
+    metric = "ip"
+
+
+def topk_merge_ip(D_in, I_in):
+    """[shards, nq, k] per-shard DESCENDING float64 lists (`knn_ip_topk_exact`) -> global (values fp32, ids) [nq, k] by (value
+    descending, id ascending) -- ac_topk_merge_ip_f64, the merge of a row-sharded inner-product search."""
+    nv.require_gpu()
+    assert D_in.dtype == torch.float64
+    S, nq, k = D_in.shape
+    D_in = D_in.contiguous()
+    I_in = I_in.contiguous()
+    outD = torch.empty((nq, k), dtype=torch.float32, device=D_in.device)
+    outI = torch.empty((nq, k), dtype=torch.int64, device=D_in.device)
+    with torch.cuda.device(D_in.device):
+        nv.check(nv.lib().ac_topk_merge_ip_f64(nv.ptr(D_in), nv.ptr(I_in), S, nq, k, nv.ptr(outD), nv.ptr(outI),
+                                               nv.stream_ptr(D_in.device)), "ac_topk_merge_ip_f64")
+    return outD, outI
 
 
 def topk_merge(D_in, I_in):

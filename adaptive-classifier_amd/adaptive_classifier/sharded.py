@@ -49,8 +49,11 @@ def _unpack(both):
 
 class ShardedSearch:
     def __init__(self, local_rows, n_local, dim, row_offset, group=None, local_search=None, merge=None,
-                 force_collectives=False, equal_blocks=False, block_rows=None):
-        """force_collectives: run the collectives even on a one-rank group (tests: executes the RCCL calls on one GPU).
+                 force_collectives=False, equal_blocks=False, block_rows=None, metric="l2"):
+        """metric: "l2" (default) or "ip" -- which search and merge are wired when none is injected: squared L2 ascending
+        (`knn_l2_topk_exact` + `topk_merge`) or inner product descending (`knn_ip_topk_exact` + `topk_merge_ip`); the exchange
+        itself (exact fp64 values and ids on the wire) is the same.
+        force_collectives: run the collectives even on a one-rank group (tests: executes the RCCL calls on one GPU).
         equal_blocks: the caller guarantees that every rank passes the same number of queries to every search_block /
         gather_queries call (a fixed per-rank batch): the ranks then skip the exchange of their block sizes.
         block_rows: the FIXED-BATCH path (what a serving loop and bench.py use): every rank's query block has AT MOST this many
@@ -58,6 +61,9 @@ class ShardedSearch:
         between the collectives (a short or empty block only costs its padding rows of local search), every message has a
         fixed shape and lives in buffers allocated once (`search_block`), and the query all-gather of the NEXT batch can run
         under the local sweep of the current one (`prefetch_queries` / `search_blocks`)."""
+        if metric not in ("l2", "ip"):
+            raise ValueError(f"metric must be 'l2' or 'ip', got {metric!r}")
+        self.metric = metric
         self.rows, self.n_local, self.dim, self.row_offset = local_rows, n_local, dim, row_offset
         self.group = group
         self.force_collectives = bool(force_collectives)
@@ -79,8 +85,11 @@ class ShardedSearch:
                     return ix.knn_l2_topk_exact(P, n, D, Q, k, row_offset=off, prepared=self._prepared)
                 return ix.knn_l2_topk_exact(P, n, D, Q, k, row_offset=off)
 
-            local_search = local_search or _hip_search
-            merge = merge or ix.topk_merge
+            def _hip_search_ip(P, n, D, Q, k, off):
+                return ix.knn_ip_topk_exact(P, n, D, Q, k, row_offset=off)
+
+            local_search = local_search or (_hip_search_ip if metric == "ip" else _hip_search)
+            merge = merge or (ix.topk_merge_ip if metric == "ip" else ix.topk_merge)
         self._search, self._merge = local_search, merge
         self._ws = None
 

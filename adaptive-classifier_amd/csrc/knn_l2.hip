@@ -23,6 +23,9 @@
 //  3. knn_exact_fallback + knn_exact_fb_merge  only for queries whose certificate failed: a plain fp64
 //                     sweep, parallel over row slabs.
 //
+// Inner-product search (ac_knn_ip_topk, faiss.IndexFlatIP.search) runs through the same kernels, instantiated with IP = true:
+// the sweep value is -2 (p.q)~ (the |p|^2 fold is dropped), and every later stage ranks by the exact key -(p.q) ascending.
+//
 // Roofline: algorithmic bytes per sweep = N*D*4; MFMA time at TQ=32 is
 // 16 B/clk/CU (> the 10.3 B/clk/CU HBM feed), so the sweep is HBM-bound for nq <= 32.
 #include "common.h"
@@ -180,7 +183,11 @@ __device__ __forceinline__ void prune_dispatch(float* ld, int32_t* li, int* cnt_
     else prune_list<8>(ld, li, cnt_p, tau_p, cap, kp, lane);
 }
 
-template <int J>
+// IP = true is the inner-product form (ac_knn_ip_topk): the sweep value is v = -2 (p.q)~ alone.  The query tile is pre-scaled
+// by -2 either way, so "smaller is better" still holds and the lists, prune_list and tau are untouched: they order by `<` on
+// floats and by fkey, which is monotone over negative values too, and the padding sentinel +inf stays the largest key.  Only the
+// |p|^2 fold of the epilogue goes; the running sum of squares stays, because the certificate needs the largest row norm.
+template <int J, bool IP = false>
 __global__ __launch_bounds__(kThreads, 2) void knn_sweep(SweepParams prm) {
     typedef Shape S;
     typedef S::acc_t acc_t;
@@ -283,9 +290,11 @@ __global__ __launch_bounds__(kThreads, 2) void knn_sweep(SweepParams prm) {
     int cur_grp = 0;
 
     auto epilogue = [&]() {
-        // fold |p|^2 in: A = this lane's partial sum of squares, B = 1
+        // fold |p|^2 in: A = this lane's partial sum of squares, B = 1  (inner product: v = -2 p.q, nothing to fold)
+        if constexpr (!IP) {
 #pragma unroll
-        for (int jj = 0; jj < J; ++jj) acc[jj] = S::mfma(nsq, 1.0f, acc[jj]);
+            for (int jj = 0; jj < J; ++jj) acc[jj] = S::mfma(nsq, 1.0f, acc[jj]);
+        }
         // row norm for the error-bound certificate
         float rn = nsq;                     // lanes i, i+16, i+32, i+48 hold the 4 k-slices of row i
         rn += __shfl_xor(rn, 16);
@@ -433,7 +442,7 @@ constexpr int ring_qs_bytes(int maxch) { return (maxch - ring_reg_chunks(maxch))
 
 template <int N> __device__ __forceinline__ void sweep_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <int RINGC, int MAXCH>
+template <int RINGC, int MAXCH, bool IP = false>
 __global__ __launch_bounds__(kThreads, 2) void knn_sweep_ring(SweepParams prm) {
     constexpr int kRingMaxChunks = MAXCH, kRingRegChunks = ring_reg_chunks(MAXCH), kRingQsBytes = ring_qs_bytes(MAXCH);
     typedef Shape S;
@@ -523,8 +532,8 @@ __global__ __launch_bounds__(kThreads, 2) void knn_sweep_ring(SweepParams prm) {
     int64_t cur_tile = 0;
 
     auto epilogue = [&]() {
-        // fold |p|^2 in: A = this lane's partial sum of squares, B = 1
-        acc[0] = S::mfma(nsq, 1.0f, acc[0]);
+        // fold |p|^2 in: A = this lane's partial sum of squares, B = 1  (inner product: v = -2 p.q, nothing to fold)
+        if constexpr (!IP) acc[0] = S::mfma(nsq, 1.0f, acc[0]);
         // row norm for the error-bound certificate
         float rn = nsq;                     // lanes i, i+16, i+32, i+48 hold the 4 k-slices of row i
         rn += __shfl_xor(rn, 16);
@@ -940,6 +949,30 @@ struct MergeParams {
     int thr_only = 0;
 };
 
+// Inner-product search (ac_knn_ip_topk, template flag IP below): every stage after the sweep ranks by the exact KEY -(p.q),
+// ascending, ties to the lower id -- the order the L2 stages already implement on their distances.  Negation is exact in fp32
+// and fp64, so the key order is the descending order of p.q; none of the stages assumes a non-negative key (they compare
+// doubles with `<` / `==`, and their padding, +inf with id 0x7fffffff, stays last).  The key is negated back once, where a
+// result is written.  exact_term = one fp64 accumulation step of the exact value: (p - q)^2, or p q (an fp32 product is exact in
+// fp64, so fma(p, q, acc) is the fp64 sum of the exact products).
+template <bool IP>
+__device__ __forceinline__ double exact_term(float p, float q, double acc) {
+    if constexpr (IP) {
+        return fma((double)p, (double)q, acc);
+    } else {
+        const double e = (double)p - (double)q;
+        return fma(e, e, acc);
+    }
+}
+// one output slot: a hit (its exact key, local row id) or faiss-style padding -- (FLT_MAX, -1) for L2, (-FLT_MAX, -1) for IP
+template <bool IP>
+__device__ __forceinline__ void emit_hit(const MergeParams& prm, size_t at, bool real, double key, int64_t id) {
+    const double v = IP ? -key : key;
+    prm.outD[at] = real ? (float)v : (IP ? -FLT_MAX : FLT_MAX);
+    if (prm.outD64) prm.outD64[at] = real ? v : (IP ? -(double)INFINITY : (double)INFINITY);
+    prm.outI[at] = real ? id + prm.row_offset : -1;
+}
+
 constexpr int kMergeThreads = 256;
 
 // Block-wide radix select (8 bits per round) over 32-bit keys held in LDS: returns the `want`-th
@@ -990,8 +1023,8 @@ __device__ __forceinline__ uint32_t block_radix_select(int n, int want, KeyFn ke
     return prefix;
 }
 
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <bool IP>
+__device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, char* smem) {
     const int q = blockIdx.x;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1137,10 +1170,8 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams pr
             const f32x4 qq = *reinterpret_cast<const f32x4*>(qrow + 4 * c4);
 #pragma unroll
             for (int u = 0; u < RU; ++u) {
-                const double e0 = (double)p[u].x - (double)qq.x, e1 = (double)p[u].y - (double)qq.y;
-                const double e2 = (double)p[u].z - (double)qq.z, e3 = (double)p[u].w - (double)qq.w;
-                acc[u][0] = fma(e0, e0, acc[u][0]); acc[u][1] = fma(e1, e1, acc[u][1]);
-                acc[u][2] = fma(e2, e2, acc[u][2]); acc[u][3] = fma(e3, e3, acc[u][3]);
+                acc[u][0] = exact_term<IP>(p[u].x, qq.x, acc[u][0]); acc[u][1] = exact_term<IP>(p[u].y, qq.y, acc[u][1]);
+                acc[u][2] = exact_term<IP>(p[u].z, qq.z, acc[u][2]); acc[u][3] = exact_term<IP>(p[u].w, qq.w, acc[u][3]);
             }
         }
 #pragma unroll
@@ -1148,7 +1179,7 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams pr
             double a = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
-            if (lane == 0 && s0 + u < ns) exact[s0 + u] = a;
+            if (lane == 0 && s0 + u < ns) exact[s0 + u] = IP ? -a : a;          // (inner product: the key -(p.q))
         }
     }
     if (wave == 0) {
@@ -1171,18 +1202,11 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams pr
             const uint32_t is = (uint32_t)(sel[s] & 0xffffffffull);
             rank += (ds < dt || (ds == dt && is < it)) ? 1 : 0;
         }
-        if (rank < kout) {
-            prm.outD[(size_t)q * kout + rank] = (float)dt;
-            if (prm.outD64) prm.outD64[(size_t)q * kout + rank] = dt;
-            prm.outI[(size_t)q * kout + rank] = (int64_t)it + prm.row_offset;
-        }
+        if (rank < kout) emit_hit<IP>(prm, (size_t)q * kout + rank, true, dt, (int64_t)it);
         if (rank == kout - 1) dmisc[1] = dt;
     }
-    for (int t = ns + tid; t < kout; t += kMergeThreads) {   // k > N: faiss-style padding
-        prm.outD[(size_t)q * kout + t] = FLT_MAX;
-        if (prm.outD64) prm.outD64[(size_t)q * kout + t] = INFINITY;
-        prm.outI[(size_t)q * kout + t] = -1;
-    }
+    for (int t = ns + tid; t < kout; t += kMergeThreads)    // k > N: faiss-style padding
+        emit_hit<IP>(prm, (size_t)q * kout + t, false, 0.0, -1);
     __syncthreads();
 
     // ---- certificate ----
@@ -1221,7 +1245,16 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams pr
             // every row that was NOT re-ranked has sweep value >= a_last, hence exact
             // distance >= a_last - E + |q|^2.  The k-th re-ranked must beat that strictly.
             const double kth = dmisc[1];
-            ok = (ns >= kout) && (kth < a_last - E + qn2) && !overflow;
+            if constexpr (IP) {
+                // inner product: the sweep value is v = -2 (p.q)~, the same fma chain without the |p|^2 terms, so
+                // |v - (-2 p.q)| <= gamma_n * 2 sum|q_i p_i| <= gamma_n * 2 |p||q| <= gamma_n (|p|max + |q|)^2 = E.  Every row that
+                // was NOT re-ranked has v >= a_last, hence -2 p.q >= a_last - E, i.e. p.q <= -(a_last - E) / 2: its key -(p.q) is
+                // >= (a_last - E) / 2 (halving is exact).  The k-th re-ranked key must lie strictly below that, i.e. the k-th exact
+                // inner product strictly above every value an unseen row can have.
+                ok = (ns >= kout) && (kth < 0.5 * (a_last - E)) && !overflow;
+            } else {
+                ok = (ns >= kout) && (kth < a_last - E + qn2) && !overflow;
+            }
             if (prm.cand_cnt && nreal < kp) ok = 0;      // fewer than k' candidates kept: the "unseen rows >= a_last" premise is gone
         }
         int flag = 0;
@@ -1232,6 +1265,14 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams pr
         }
         prm.flags[q] = flag;
     }
+}
+__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_merge_rerank_body<false>(prm, smem);
+}
+__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank_ip(MergeParams prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_merge_rerank_body<true>(prm, smem);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1250,6 +1291,7 @@ constexpr int kFbRound = 32;          // rows per wave between barriers
 //  no query flagged -- every call of an ordinary batch -- dispatching fb_S x nq = 16 384 empty 512-thread blocks cost 8.5 us;
 //  fb_S x 8 cost 2.  A device holds <= ~1000 of these blocks at once, so flagged batches lose nothing.)
 constexpr int kFbQueryGroups = 8, kFbMergeGroups = 32;
+template <bool IP>
 __device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm, const int q, const int slab, char* smem) {
     const int flag = prm.flags[q];
     if (flag == 0 || (flag < 0 && slab != 0)) return;
@@ -1310,13 +1352,13 @@ __device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm,
             for (int c4 = lane; c4 < nc4; c4 += 64) {
                 const f32x4 p = prow[c4];
                 const f32x4 qq = *reinterpret_cast<const f32x4*>(qrow + 4 * c4);
-                const double e0 = (double)p.x - (double)qq.x, e1 = (double)p.y - (double)qq.y;
-                const double e2 = (double)p.z - (double)qq.z, e3 = (double)p.w - (double)qq.w;
-                a0 = fma(e0, e0, a0); a1 = fma(e1, e1, a1); a2 = fma(e2, e2, a2); a3 = fma(e3, e3, a3);
+                a0 = exact_term<IP>(p.x, qq.x, a0); a1 = exact_term<IP>(p.y, qq.y, a1);
+                a2 = exact_term<IP>(p.z, qq.z, a2); a3 = exact_term<IP>(p.w, qq.w, a3);
             }
             double a = (a0 + a1) + (a2 + a3);
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
+            if (IP) a = -a;                 // (inner product: the key -(p.q); the same bits knn_merge_rerank computes for this row)
             if (lane == 0 && (a < td || (a == td && (int32_t)row < ti))) {
                 const int s = atomicAdd(&misc[0], 1);
                 if (s < kFbCap) { ld[s] = a; li[s] = (int32_t)row; }
@@ -1330,11 +1372,7 @@ __device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm,
     prune();
     const int n = misc[0];
     if (direct) {
-        for (int t = tid; t < k; t += kFbThreads) {
-            prm.outD[(size_t)q * k + t] = t < n ? (float)ld[t] : FLT_MAX;
-            if (prm.outD64) prm.outD64[(size_t)q * k + t] = t < n ? ld[t] : (double)INFINITY;
-            prm.outI[(size_t)q * k + t] = t < n ? (int64_t)li[t] + prm.row_offset : -1;
-        }
+        for (int t = tid; t < k; t += kFbThreads) emit_hit<IP>(prm, (size_t)q * k + t, t < n, ld[t], (int64_t)li[t]);    // (k <= kFbCap)
     } else {
         const size_t base = ((size_t)(flag - 1) * prm.fb_S + slab) * k;
         for (int t = tid; t < k; t += kFbThreads) {
@@ -1346,12 +1384,20 @@ __device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm,
 __global__ __launch_bounds__(kFbThreads) void knn_exact_fallback(MergeParams prm, int nq) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     for (int q = blockIdx.y; q < nq; q += gridDim.y) {
-        knn_exact_fallback_query(prm, q, blockIdx.x, smem);
+        knn_exact_fallback_query<false>(prm, q, blockIdx.x, smem);
         __syncthreads();                                            // (the next query reuses the lists)
+    }
+}
+__global__ __launch_bounds__(kFbThreads) void knn_exact_fallback_ip(MergeParams prm, int nq) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    for (int q = blockIdx.y; q < nq; q += gridDim.y) {
+        knn_exact_fallback_query<true>(prm, q, blockIdx.x, smem);
+        __syncthreads();
     }
 }
 
 // merge the fb_S slab results of a flagged query: bitonic sort of fb_S * k (<= 4096) exact entries
+template <bool IP>
 __device__ __forceinline__ void knn_exact_fb_merge_query(const MergeParams& prm, const int npow2, const int q, char* smem) {
     const int tid = threadIdx.x;
     const int flag = prm.flags[q];
@@ -1378,17 +1424,19 @@ __device__ __forceinline__ void knn_exact_fb_merge_query(const MergeParams& prm,
             }
             __syncthreads();
         }
-    for (int t = tid; t < prm.k; t += 256) {
-        const bool real = is[t] != 0x7fffffff;
-        prm.outD[(size_t)q * prm.k + t] = real ? (float)ds[t] : FLT_MAX;
-        if (prm.outD64) prm.outD64[(size_t)q * prm.k + t] = real ? ds[t] : (double)INFINITY;
-        prm.outI[(size_t)q * prm.k + t] = real ? (int64_t)is[t] + prm.row_offset : -1;
-    }
+    for (int t = tid; t < prm.k; t += 256) emit_hit<IP>(prm, (size_t)q * prm.k + t, is[t] != 0x7fffffff, ds[t], (int64_t)is[t]);
 }
 __global__ __launch_bounds__(256) void knn_exact_fb_merge(MergeParams prm, int npow2, int nq) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-        knn_exact_fb_merge_query(prm, npow2, q, smem);
+        knn_exact_fb_merge_query<false>(prm, npow2, q, smem);
+        __syncthreads();
+    }
+}
+__global__ __launch_bounds__(256) void knn_exact_fb_merge_ip(MergeParams prm, int npow2, int nq) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    for (int q = blockIdx.x; q < nq; q += gridDim.x) {
+        knn_exact_fb_merge_query<true>(prm, npow2, q, smem);
         __syncthreads();
     }
 }
@@ -1396,7 +1444,9 @@ __global__ __launch_bounds__(256) void knn_exact_fb_merge(MergeParams prm, int n
 // --------------------------------------------------------------------------------------
 // shard merge and prototype scores
 // --------------------------------------------------------------------------------------
-template <typename DT>
+// DESC = the inner-product form: per-shard DESCENDING lists -> global top-k by (value descending, id ascending); padding
+// (id < 0) comes out as (-FLT_MAX, -1).  Pure selection either way.
+template <typename DT, bool DESC = false>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const DT* Din, const int64_t* Iin,
                                                          int shards, int nq, int k, float* outD,
                                                          int64_t* outI) {
@@ -1410,7 +1460,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const DT* Din, const in
         ids[t] = Iin[((size_t)s * nq + q) * k + e];
         ds[t] = Din[((size_t)s * nq + q) * k + e];
     }
-    for (int t = tid; t < k; t += 256) { outD[(size_t)q * k + t] = FLT_MAX; outI[(size_t)q * k + t] = -1; }
+    for (int t = tid; t < k; t += 256) { outD[(size_t)q * k + t] = DESC ? -FLT_MAX : FLT_MAX; outI[(size_t)q * k + t] = -1; }
     __syncthreads();
     for (int t = tid; t < n; t += 256) {
         const int64_t it = ids[t];
@@ -1421,7 +1471,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const DT* Din, const in
             const int64_t is = ids[s];
             if (is < 0) continue;
             const DT d = ds[s];
-            rank += (d < dt || (d == dt && (is < it || (is == it && s < t)))) ? 1 : 0;
+            rank += ((DESC ? d > dt : d < dt) || (d == dt && (is < it || (is == it && s < t)))) ? 1 : 0;
         }
         if (rank < k) { outD[(size_t)q * k + rank] = (float)dt; outI[(size_t)q * k + rank] = it; }
     }
@@ -1472,8 +1522,8 @@ __global__ __launch_bounds__(256) void rows_to_class_kernel(const int64_t* I, in
 constexpr int kSmallN = 8192;
 constexpr int kSmallThreads = 256;
 
-__global__ __launch_bounds__(kSmallThreads) void knn_small_exact(MergeParams prm, int npow2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+template <bool IP>
+__device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int npow2, char* smem) {
     double* ds = reinterpret_cast<double*>(smem);                // [npow2]
     int32_t* is = reinterpret_cast<int32_t*>(ds + npow2);        // [npow2]
     const int q = blockIdx.x, tid = threadIdx.x;
@@ -1485,12 +1535,12 @@ __global__ __launch_bounds__(kSmallThreads) void knn_small_exact(MergeParams prm
             double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
             int c = 0;
             for (; c + 3 < prm.D; c += 4) {
-                const double e0 = (double)p[c] - (double)qv[c], e1 = (double)p[c + 1] - (double)qv[c + 1];
-                const double e2 = (double)p[c + 2] - (double)qv[c + 2], e3 = (double)p[c + 3] - (double)qv[c + 3];
-                a0 = fma(e0, e0, a0); a1 = fma(e1, e1, a1); a2 = fma(e2, e2, a2); a3 = fma(e3, e3, a3);
+                a0 = exact_term<IP>(p[c], qv[c], a0); a1 = exact_term<IP>(p[c + 1], qv[c + 1], a1);
+                a2 = exact_term<IP>(p[c + 2], qv[c + 2], a2); a3 = exact_term<IP>(p[c + 3], qv[c + 3], a3);
             }
-            for (; c < prm.D; ++c) { const double e = (double)p[c] - (double)qv[c]; a0 = fma(e, e, a0); }
+            for (; c < prm.D; ++c) a0 = exact_term<IP>(p[c], qv[c], a0);
             a = (a0 + a1) + (a2 + a3);
+            if (IP) a = -a;                                      // (inner product: the key -(p.q))
         }
         ds[r] = a;
         is[r] = r < prm.N ? r : 0x7fffffff;
@@ -1510,11 +1560,17 @@ __global__ __launch_bounds__(kSmallThreads) void knn_small_exact(MergeParams prm
             __syncthreads();
         }
     for (int t = tid; t < prm.k; t += kSmallThreads) {
-        const bool real = t < prm.N;
-        prm.outD[(size_t)q * prm.k + t] = real ? (float)ds[t] : FLT_MAX;
-        if (prm.outD64) prm.outD64[(size_t)q * prm.k + t] = real ? ds[t] : (double)INFINITY;
-        prm.outI[(size_t)q * prm.k + t] = real ? (int64_t)is[t] + prm.row_offset : -1;
+        const bool real = t < prm.N;                             // (k may exceed npow2: the lists are read for real hits only)
+        emit_hit<IP>(prm, (size_t)q * prm.k + t, real, real ? ds[t] : 0.0, real ? (int64_t)is[t] : -1);
     }
+}
+__global__ __launch_bounds__(kSmallThreads) void knn_small_exact(MergeParams prm, int npow2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_small_exact_body<false>(prm, npow2, smem);
+}
+__global__ __launch_bounds__(kSmallThreads) void knn_small_exact_ip(MergeParams prm, int npow2) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_small_exact_body<true>(prm, npow2, smem);
 }
 
 // ---- host-side planning ----
@@ -1658,10 +1714,11 @@ extern "C" int ac_knn_l2_topk(const float* d_P, int64_t N, int64_t ldP, int D, c
                             d_stats, stream_);
 }
 
-extern "C" int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
-                                int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64,
-                                int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
-                                ac_stream_t stream_) {
+// the fp32-sweep search of both metrics: ip = false squared L2 (ac_knn_l2_topk_x), true inner product (ac_knn_ip_topk_x).  One
+// plan, one workspace layout and one launch sequence; the metric only picks the instantiation of each kernel.
+static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
+                    int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64,
+                    int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     Plan pl;
     int rc = make_plan(N, D, nq, k, &pl);
@@ -1685,8 +1742,9 @@ extern "C" int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
         sp.P = d_P; sp.N = N; sp.ldP = ldP; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.k = k; sp.row_offset = row_offset;
         sp.outD = d_outD; sp.outD64 = d_outD64; sp.outI = d_outI;
         const size_t lds = (size_t)pl.small_pow2 * 12;
-        (void)hipFuncSetAttribute((const void*)knn_small_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(knn_small_exact, dim3(nq), dim3(kSmallThreads), lds, stream, sp, pl.small_pow2);
+        void (*small_fn)(MergeParams, int) = ip ? knn_small_exact_ip : knn_small_exact;
+        (void)hipFuncSetAttribute((const void*)small_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(small_fn, dim3(nq), dim3(kSmallThreads), lds, stream, sp, pl.small_pow2);
         AC_LAUNCH_CHECK();
         return AC_OK;
     }
@@ -1726,41 +1784,62 @@ extern "C" int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
         sp.clear_stats = d_stats;
         const int nblk = pl.G * pl.nqt;
         if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
+        void (*sweep_fn)(SweepParams);
         if (pl.ring) {
-            if (D <= 768) {
-                AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_sweep_ring<4, 24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
-                hipLaunchKernelGGL((knn_sweep_ring<4, 24>), dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
-            } else {
-                AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_sweep_ring<4, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
-                hipLaunchKernelGGL((knn_sweep_ring<4, 32>), dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
-            }
-        } else if (pl.TQ == 32) {
-            (void)hipFuncSetAttribute((const void*)knn_sweep<2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)pl.sweep_lds);
-            hipLaunchKernelGGL(knn_sweep<2>, dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
+            if (D <= 768) sweep_fn = ip ? knn_sweep_ring<4, 24, true> : knn_sweep_ring<4, 24, false>;
+            else sweep_fn = ip ? knn_sweep_ring<4, 32, true> : knn_sweep_ring<4, 32, false>;
+            AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
         } else {
-            (void)hipFuncSetAttribute((const void*)knn_sweep<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)pl.sweep_lds);
-            hipLaunchKernelGGL(knn_sweep<1>, dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
+            if (pl.TQ == 32) sweep_fn = ip ? knn_sweep<2, true> : knn_sweep<2, false>;
+            else sweep_fn = ip ? knn_sweep<1, true> : knn_sweep<1, false>;
+            (void)hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds);
         }
+        hipLaunchKernelGGL(sweep_fn, dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
         AC_LAUNCH_CHECK();
         if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
     }
-    (void)hipFuncSetAttribute((const void*)knn_merge_rerank, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)pl.merge_lds);
-    hipLaunchKernelGGL(knn_merge_rerank, dim3(nq), dim3(kMergeThreads), pl.merge_lds, stream, mp);
+    void (*merge_fn)(MergeParams) = ip ? knn_merge_rerank_ip : knn_merge_rerank;
+    (void)hipFuncSetAttribute((const void*)merge_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.merge_lds);
+    hipLaunchKernelGGL(merge_fn, dim3(nq), dim3(kMergeThreads), pl.merge_lds, stream, mp);
     AC_LAUNCH_CHECK();
     if (N > 0) {
-        (void)hipFuncSetAttribute((const void*)knn_exact_fallback, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)pl.fb_lds);
-        hipLaunchKernelGGL(knn_exact_fallback, dim3(pl.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups), dim3(kFbThreads), pl.fb_lds, stream, mp, nq);
+        void (*fb_fn)(MergeParams, int) = ip ? knn_exact_fallback_ip : knn_exact_fallback;
+        (void)hipFuncSetAttribute((const void*)fb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.fb_lds);
+        hipLaunchKernelGGL(fb_fn, dim3(pl.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups), dim3(kFbThreads), pl.fb_lds, stream, mp, nq);
         AC_LAUNCH_CHECK();
         const int np2 = next_pow2(pl.fb_S * k > 2 ? pl.fb_S * k : 2);
-        (void)hipFuncSetAttribute((const void*)knn_exact_fb_merge, hipFuncAttributeMaxDynamicSharedMemorySize, np2 * 12);
-        hipLaunchKernelGGL(knn_exact_fb_merge, dim3(nq < kFbMergeGroups ? nq : kFbMergeGroups), dim3(256), (size_t)np2 * 12, stream, mp, np2, nq);
+        void (*fbm_fn)(MergeParams, int, int) = ip ? knn_exact_fb_merge_ip : knn_exact_fb_merge;
+        (void)hipFuncSetAttribute((const void*)fbm_fn, hipFuncAttributeMaxDynamicSharedMemorySize, np2 * 12);
+        hipLaunchKernelGGL(fbm_fn, dim3(nq < kFbMergeGroups ? nq : kFbMergeGroups), dim3(256), (size_t)np2 * 12, stream, mp, np2, nq);
         AC_LAUNCH_CHECK();
     }
     return AC_OK;
+}
+
+extern "C" int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
+                                int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64,
+                                int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                ac_stream_t stream_) {
+    return knn_topk(false, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes, d_stats, stream_);
+}
+
+// inner product (faiss.IndexFlatIP.search): the plan, and hence the workspace, is the L2 search's
+extern "C" int ac_knn_ip_topk_workspace(int64_t N, int D, int nq, int k, size_t* bytes) {
+    return ac_knn_l2_topk_workspace(N, D, nq, k, bytes);
+}
+
+extern "C" int ac_knn_ip_topk(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
+                              int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD,
+                              int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                              ac_stream_t stream_) {
+    return knn_topk(true, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_outD, nullptr, d_outI, d_ws, ws_bytes, d_stats, stream_);
+}
+
+extern "C" int ac_knn_ip_topk_x(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
+                                int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64,
+                                int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                ac_stream_t stream_) {
+    return knn_topk(true, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes, d_stats, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2171,6 +2250,21 @@ extern "C" int ac_topk_merge_f64(const double* d_D_in, const int64_t* d_I_in, in
     AC_REQUIRE(lds <= 128 * 1024, AC_EUNSUPPORTED, "topk_merge_f64: shards*k=%d too large", shards * k);
     (void)hipFuncSetAttribute((const void*)topk_merge_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(topk_merge_kernel<double>, dim3(nq), dim3(256), lds, stream, d_D_in, d_I_in, shards, nq, k,
+                       d_outD, d_outI);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
+}
+
+extern "C" int ac_topk_merge_ip_f64(const double* d_D_in, const int64_t* d_I_in, int shards, int nq, int k,
+                                    float* d_outD, int64_t* d_outI, ac_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    AC_REQUIRE(shards >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "topk_merge_ip_f64: bad shape");
+    AC_REQUIRE(d_D_in && d_I_in && d_outD && d_outI, AC_EINVAL, "topk_merge_ip_f64: null pointer");
+    if (nq == 0) return AC_OK;
+    const size_t lds = (size_t)shards * k * 16;
+    AC_REQUIRE(lds <= 128 * 1024, AC_EUNSUPPORTED, "topk_merge_ip_f64: shards*k=%d too large", shards * k);
+    (void)hipFuncSetAttribute((const void*)topk_merge_kernel<double, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((topk_merge_kernel<double, true>), dim3(nq), dim3(256), lds, stream, d_D_in, d_I_in, shards, nq, k,
                        d_outD, d_outI);
     AC_LAUNCH_CHECK();
     return AC_OK;

@@ -109,6 +109,38 @@ int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
                      ac_stream_t stream);
 
 /*
+ * Exact inner-product top-k, the semantics of faiss.IndexFlatIP.search (no reference call site: the reference only builds
+ * IndexFlatL2; this is what a store of L2-normalised embeddings is searched with -- cosine -- and it needs no normalisation):
+ * for each query the k rows with the LARGEST p.q, in DESCENDING order, ties to the lower row id.  Values may be negative.
+ * Argument lists, alignment / ldP / ldQ rules, error codes, limits (k <= AC_KNN_MAX_K and the LDS bound on D for big
+ * stores, the small-store exact path for N <= 8192, AC_EUNSUPPORTED beyond), workspace size and d_stats are those of the L2
+ * namesakes; the fp32 sweeps serve every shape (there is no prepared-store form).
+ *
+ * Exactness contract: the ids are the top-k under the exactly computed inner product (fp64 accumulation of the fp32
+ * products, each of which is exact in fp64), d_outD is that value rounded once to fp32, d_outD64 (may be NULL) the fp64
+ * value.  If k > N the tail is (-FLT_MAX, -1), -inf in d_outD64.
+ * Mechanism: the L2 kernels instantiated for the key -(p.q).  The sweep proposes k+pad candidates per query from
+ * v = -2 (p.q)~ (fp32 MFMA chain, |v - (-2 p.q)| <= E = gamma 2 |p||q| <= gamma (|p|max + |q|)^2, gamma = n 2^-24 x 1.01 for
+ * the chain's n roundings per term); the candidates are re-ranked by the exact fp64 value; every row that was not re-ranked
+ * has v >= a_last (the largest proposed sweep value), hence p.q <= -(a_last - E) / 2.  A query is certified when its k-th
+ * re-ranked exact value is STRICTLY greater than that, its list is full and nothing overflowed; every other query is redone
+ * by an exact fp64 sweep inside the same call (counted in d_stats[0]).
+ */
+int ac_knn_ip_topk_workspace(int64_t N, int D, int nq, int k, size_t* bytes);
+int ac_knn_ip_topk(const float* d_P, int64_t N, int64_t ldP, int D,
+                   const float* d_Q, int nq, int64_t ldQ, int k,
+                   int64_t row_offset,
+                   float* d_outD, int64_t* d_outI,
+                   void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                   ac_stream_t stream);
+int ac_knn_ip_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
+                     const float* d_Q, int nq, int64_t ldQ, int k,
+                     int64_t row_offset,
+                     float* d_outD, double* d_outD64, int64_t* d_outI,
+                     void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                     ac_stream_t stream);
+
+/*
  * Search over a PREPARED store (BASELINE configs[2] / [4], predict_batch; replaces the same faiss call, memory.py:114).  Same
  * result contract as ac_knn_l2_topk_x -- the ids are the exact top-k, bit for bit -- but candidates are PROPOSED from ONE fp16
  * plane per operand (one v_mfma_f32_32x32x16_f16 per 32 x 32 x 16 block) and only the re-rank / certificate / fallback stay in
@@ -153,7 +185,7 @@ int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D,
 
 /*
  * Optional profiling hook: when both events are non-NULL, every following
- * ac_knn_l2_topk call of THIS thread records `start` immediately before and
+ * ac_knn_l2_topk / ac_knn_ip_topk call of THIS thread records `start` immediately before and
  * `stop` immediately after its sweep kernel (the HBM-bound kernel) on the
  * call's stream, so the caller can read that kernel's duration with
  * hipEventElapsedTime.  Pass NULLs to switch it off.  (hipEvent_t as void*.)
@@ -174,6 +206,11 @@ int ac_topk_merge(const float* d_D_in, const int64_t* d_I_in, int shards,
 int ac_topk_merge_f64(const double* d_D_in, const int64_t* d_I_in, int shards,
                       int nq, int k, float* d_outD, int64_t* d_outI,
                       ac_stream_t stream);
+/* The inner-product form (ac_knn_ip_topk_x's d_outD64): per-shard DESCENDING fp64 lists -> global top-k by (value
+ * descending, id ascending), the fp32 rounding out; padding (id < 0) comes out as (-FLT_MAX, -1). */
+int ac_topk_merge_ip_f64(const double* d_D_in, const int64_t* d_I_in, int shards,
+                         int nq, int k, float* d_outD, int64_t* d_outI,
+                         ac_stream_t stream);
 
 /*
  * memory.py:117,129-130: s = exp(-d) per hit, then softmax over the k hits of

@@ -106,10 +106,10 @@ class HeadTrainer:
         return self.loss
 
     def fused_step(self, X_all, y_all, index=None, dropout_p=0.1, seed=0, fisher=None, old_params=None,
-                   lambda_over_B=0.0, loss_kind=LOSS_CE, targets_all=None):
+                   lambda_over_B=0.0, loss_kind=LOSS_CE, targets_all=None, stepwise=False):
         """One call = gather batch (rows `index` of X_all / y_all) + train-mode forward with in-kernel
         counter-based dropout + CE + backward + EWC/clip/AdamW (`ac_head_train_step`).  No torch kernels,
-        no host sync; the step's CE + penalty is added to self.loss_accum on device."""
+        no host sync; the step's CE + penalty is added to self.loss_accum on device.  stepwise=True: as in fused_epoch."""
         B = int(index.numel()) if index is not None else X_all.shape[0]
         ws = self._workspace(B)
         self.t += 1
@@ -117,7 +117,8 @@ class HeadTrainer:
             nv.check(nv.lib().ac_head_train_step(
                 ctypes.byref(self.dims), nv.ptr(self.flat), nv.ptr(self.m), nv.ptr(self.v), nv.ptr(self.grads),
                 nv.ptr(X_all), X_all.stride(0), nv.ptr(y_all), nv.ptr(targets_all),
-                0 if targets_all is None else targets_all.stride(0), loss_kind, nv.ptr(index), B, dropout_p, seed,
+                0 if targets_all is None else targets_all.stride(0), loss_kind | (LOSS_STEPWISE if stepwise else 0),
+                nv.ptr(index), B, dropout_p, seed,
                 nv.ptr(fisher), nv.ptr(old_params), lambda_over_B, self.max_grad_norm, self.lr, self.betas[0],
                 self.betas[1], self.eps, self.weight_decay, self.t, nv.ptr(self.out3), nv.ptr(self.loss_accum),
                 nv.ptr(ws), ws.numel(), nv.stream_ptr(self.device)), "ac_head_train_step")

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from head_epoch_ref import dropout_keep_np as _dropout_keep_np          # the numpy port of ac::dropout_keep, shared
+
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-4
@@ -179,19 +181,6 @@ def test_ewc_fisher_penalty_and_fused_step(cuda_dev):
         assert (tr.flat.cpu() - head_oracle.flat(ref)).abs().max().item() < 5e-5
 
 
-def _dropout_keep_np(seed, n_rows, n_cols, p):
-    """numpy port of ac::dropout_keep (csrc/common.h): keep iff u(seed, row*N+col) >= p."""
-    M = np.uint64(0xFFFFFFFFFFFFFFFF)
-    with np.errstate(over="ignore"):
-        idx = np.arange(n_rows * n_cols, dtype=np.uint64)
-        z = np.uint64(seed) + idx * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    u = (z >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    return (u >= np.float32(p)).reshape(n_rows, n_cols)
-
-
 def test_softmax_and_normalize_rows(cuda_dev):
     from adaptive_classifier.ops import l2_normalize_rows, softmax_rows
     g = torch.Generator().manual_seed(0)
@@ -275,6 +264,7 @@ def test_persistent_epoch_kernel_agrees_with_the_launch_by_launch_path(D, C, n, 
     """head_epoch.hip (weights + AdamW moments stationary in LDS, one launch per epoch) against the step-by-step kernels of
     head.hip on the same batches, dropout seeds and optimizer state: the two differ only in summation order (fma chains /
     wave-strided dots vs MFMA tiles), so parameters, moments and the epoch loss agree to fp32 round-off -- not bit for bit."""
+    import ctypes
     from adaptive_classifier import _native as nv
     B = 32
     _, _, head_a, tr_a = _make_pair(D, C, cuda_dev)
@@ -287,16 +277,26 @@ def test_persistent_epoch_kernel_agrees_with_the_launch_by_launch_path(D, C, n, 
         fisher = torch.rand(tr_a.flat.numel(), generator=g).to(cuda_dev)
         old = (tr_a.flat + 0.01 * torch.randn(tr_a.flat.numel(), generator=g).to(cuda_dev)).contiguous()
     order = torch.randperm(n, generator=torch.Generator().manual_seed(10)).to(cuda_dev)
+    def launches():
+        he, bs = ctypes.c_int64(0), ctypes.c_int64(0)
+        nv.check(nv.lib().ac_persistent_launches(ctypes.byref(he), ctypes.byref(bs)), "ac_persistent_launches")
+        return he.value
     prev = nv.lib().ac_set_persistent_kernels(-1)
+    added = []
     try:
         for tr, mask in ((tr_a, prev | 1), (tr_b, prev & ~1)):
             nv.lib().ac_set_persistent_kernels(mask)
             tr.loss_accum.zero_()
+            before = launches()
             for epoch in range(1):      # (a few steps: AdamW turns round-off on near-zero gradients into O(lr) differences over time)
                 tr.fused_epoch(Xd, yd, order, B, 0.1, 500 + epoch, fisher=fisher, old_params=old, lambda_B=5.0 if with_ewc else 0.0)
             torch.cuda.synchronize()
+            added.append(launches() - before)
     finally:
         nv.lib().ac_set_persistent_kernels(prev)
+    # the comparison below means something only if the first leg took the persistent kernel (one launch per epoch) and the second
+    # did not: head_epoch_persistent() declines silently
+    assert added == [1, 0], added
     assert tr_a.t == tr_b.t
     assert (tr_a.flat - tr_b.flat).abs().max().item() < 5e-5
     assert (tr_a.m - tr_b.m).abs().max().item() < 1e-5 and (tr_a.v - tr_b.v).abs().max().item() < 1e-6

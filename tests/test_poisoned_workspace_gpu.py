@@ -17,28 +17,77 @@ def _fill(t, byte):
     t.view(torch.uint8).fill_(byte)
 
 
-@pytest.mark.parametrize("D,C,n,B", [(768, 3, 5, 5), (768, 4, 64, 32), (768, 3, 40, 32), (128, 3, 5, 5), (128, 2, 1, 1),
-                                     (1024, 64, 70, 32), (768, 3, 33, 32)])
-@pytest.mark.parametrize("stepwise", [False, True])
-def test_head_training_ignores_workspace_garbage(cuda_dev, D, C, n, B, stepwise):
-    from adaptive_classifier import AdaptiveHead
-    from adaptive_classifier.training import HeadTrainer
+def _head_epoch_launches():
+    import ctypes
+    from adaptive_classifier import _native as nv
+    he, bs = ctypes.c_int64(0), ctypes.c_int64(0)
+    nv.check(nv.lib().ac_persistent_launches(ctypes.byref(he), ctypes.byref(bs)), "ac_persistent_launches")
+    return he.value
+
+
+def _table_device():
+    """The expected paths below are written for 256 active CUs and 160 KB of LDS per workgroup."""
+    import ctypes
+    from adaptive_classifier import _native as nv
+    chip, act = ctypes.c_int(0), ctypes.c_int(0)
+    nv.check(nv.lib().ac_device_cus(ctypes.byref(chip), ctypes.byref(act)), "ac_device_cus")
+    return act.value == 256 and nv.device_info()["lds_per_block"] >= 160 * 1024
+
+
+def _train_on_garbage(cuda_dev, D, hidden, C, n, B, stepwise, persistent, bce=False):
+    """Two epochs from a zero-filled and from a 0xFF-filled workspace: the same bits; and the path that was meant ran
+    (`persistent`: written by hand from head_epoch_persistent()'s rule, as in tests/head_epoch_ref.py)."""
+    from adaptive_classifier import AdaptiveHead, MultiLabelAdaptiveHead
+    from adaptive_classifier.training import LOSS_BCE_SIGMOID, LOSS_CE, HeadTrainer
     g = torch.Generator().manual_seed(1)
     X = torch.nn.functional.normalize(torch.randn(n, D, generator=g), dim=1).to(cuda_dev)
     y = (torch.arange(n) % C).to(cuda_dev)
+    T = ((torch.arange(n)[:, None] * 3 + torch.arange(C)[None, :] * 5) % 7 < 2).float().to(cuda_dev) if bce else None
     res = []
     for byte in (0, 0xFF):
-        head = AdaptiveHead(D, C, [D, D // 2]).to(cuda_dev)
+        if bce:
+            torch.manual_seed(7)
+            head = MultiLabelAdaptiveHead(D, C, list(hidden)).to(cuda_dev)
+        else:
+            head = AdaptiveHead(D, C, list(hidden)).to(cuda_dev)
         tr = HeadTrainer(head)
         _fill(tr._workspace(min(B, n)), byte)
         _fill(tr.grads, byte)                            # the gradient block is scratch to the step (written before it is read)
         tr.loss_accum.zero_()
+        before = _head_epoch_launches()
         for ep in range(2):
-            tr.fused_epoch(X, y, None, min(B, n), 0.1, 1234 + ep, stepwise=stepwise)
+            tr.fused_epoch(X, None if bce else y, None, min(B, n), 0.1, 1234 + ep, stepwise=stepwise,
+                           loss_kind=LOSS_BCE_SIGMOID if bce else LOSS_CE, targets_all=T)
         torch.cuda.synchronize()
+        if _table_device():
+            assert _head_epoch_launches() - before == (2 if persistent and not stepwise else 0)
         res.append(torch.cat([head.flat_params().detach().clone(), tr.loss_accum.clone()]))
     assert torch.isfinite(res[1]).all()
     assert torch.equal(res[0], res[1])
+
+
+@pytest.mark.parametrize("D,C,n,B", [(768, 3, 5, 5), (768, 4, 64, 32), (768, 3, 40, 32), (128, 3, 5, 5), (128, 2, 1, 1),
+                                     (1024, 64, 70, 32), (768, 3, 33, 32)])
+@pytest.mark.parametrize("stepwise", [False, True])
+def test_head_training_ignores_workspace_garbage(cuda_dev, D, C, n, B, stepwise):
+    # every shape here fits the persistent epoch kernel but (1024 / [1024, 512], C = 64): C > 16, H2 > 384
+    _train_on_garbage(cuda_dev, D, (D, D // 2), C, n, B, stepwise, persistent=C <= 16)
+
+
+@pytest.mark.parametrize("D,hidden,C,n,B,bce", [
+    (1024, (1024, 256), 16, 70, 32, False),         # r1 = 4: head_epoch_kernel<16, 4, 2>
+    (1024, (1024, 256), 3, 5, 5, False),            #         head_epoch_kernel<4, 4, 2>, 5 rows
+    (640, (520, 260), 7, 45, 32, False),            # ragged ownership, short last batch
+    (640, (520, 260), 7, 18, 5, False),             # ... and an epoch of 5-row batches (5, 5, 5, 3)
+    (768, (768, 384), 3, 20, 5, False),             # batch = 5 for a whole epoch
+    (768, (768, 384), 3, 6, 1, False),              # batch = 1 for a whole epoch
+    (64, (32, 16), 2, 40, 32, False),               # most workgroups own nothing
+    (768, (768, 384), 6, 40, 32, True),             # BCE on sigmoid outputs, float targets
+    (128, (128, 64), 16, 7, 7, True),
+])
+@pytest.mark.parametrize("stepwise", [False, True])
+def test_head_training_ignores_workspace_garbage_more_shapes(cuda_dev, D, hidden, C, n, B, bce, stepwise):
+    _train_on_garbage(cuda_dev, D, hidden, C, n, B, stepwise, persistent=True, bce=bce)
 
 
 def test_head_forward_ignores_workspace_garbage(cuda_dev):

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(64) void blend_topk_kernel(const float* __restrict_
 }
 
 // ---- the whole tail of a predict batch in ONE launch (ac_predict_post) ------------------------------------------------------------
-// proto_scores_kernel (knn_l2.hip: exp(-d), softmax over the hits) + rows_to_class_kernel (hit row -> classifier class) +
+// proto_scores_kernel (knn_exact.hip: exp(-d), softmax over the hits) + rows_to_class_kernel (hit row -> classifier class) +
 // softmax_rows_kernel (head.hip: F.softmax over the head's outputs) + blend_topk_kernel above, the same arithmetic in the same order
 // (the three preludes leave their results in LDS instead of global memory), one wave per query.  The packed result may live in
 // host-mapped memory: the last workgroup to finish (agent-scope counter; every workgroup made its stores visible system-wide first)

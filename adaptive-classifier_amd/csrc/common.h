@@ -68,6 +68,7 @@ bool first_call_on_device(std::atomic<unsigned long long>& done);
     } while (0)
 
 __host__ __device__ static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 // gemm.hip: fp32 MFMA GEMMs shared by head.hip and bert.hip
 //   C[M,N] = epi(A[M,K] . W[N,K]^T): bias, act (0 none / 1 relu / 2 gelu-erf), optional inverted
@@ -256,9 +257,18 @@ __device__ __forceinline__ gelu_f32x2 gelu_erf2(gelu_f32x2 x) {
 __device__ __forceinline__ int64_t plane_off(int64_t rows, int64_t row, int k) {
     return ((int64_t)(k >> 3) * rows + row) * 8 + (k & 7);
 }
+// monotone map float -> uint32 (ascending float order == ascending unsigned order): the kNN candidate lists select on these keys
+__device__ __forceinline__ uint32_t fkey(float f) {
+    uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float fkey_inv(uint32_t k) {
+    uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    return __uint_as_float(b);
+}
 #endif
 
-// knn_batch.hip: fp16 operand plane + GEMM-form proposal sweep for batched kNN (used by knn_l2.hip)
+// knn_batch.hip: fp16 operand plane + GEMM-form proposal sweep for batched kNN (used by knn_l2.hip; exact results: knn_exact.hip)
 size_t knn_planes_bytes(int64_t rows, int D);      // bytes of the fp16 plane of a [rows, D] operand (rows padded to 256, D to 64)
 double knn_batch_gamma(int D);                     // |sweep value - exact| <= gamma (max|p| + |q|)^2
 int knn_prepare_store(const float* X, int64_t ldx, int64_t rows, int D, uint16_t* plane, float* norms, uint32_t* maxnorm_bits,
@@ -276,6 +286,73 @@ int knn_batch_launch(const uint16_t* Pp, const float* pnorm, int64_t N, int D, c
 bool ln_fusion_enabled();        // gemm_pipe.hip: false = this call / process runs no in-launch exchange between workgroups
 bool knn_batch_two_phase_applies(int64_t N, int nq, int kp, int segs);
 size_t knn_batch_two_phase_bytes();
+
+// knn_exact.hip: the exact stages every kNN route ends in -- merge + fp64 re-rank + certificate, exact fallback, small-store search
+// (used by knn_l2.hip, whose routes fill the candidate-source half of MergeParams: G / nblk / gamma, part_*, cand_*, thr_*).
+// The kernels take the struct by value: the field order is their kernarg layout.
+struct MergeParams {
+    const float* P = nullptr;
+    int64_t N = 0;
+    int64_t ldP = 0;
+    const float* Q = nullptr;
+    int64_t ldQ = 0;
+    int D = 0;
+    int Dp = 0;
+    int k = 0;
+    int kp = 0;
+    int G = 0;
+    int nblk = 0;       // entries of part_maxnorm
+    double gamma = 0;   // |sweep value - exact| <= gamma (|p| + |q|)^2: n * 2^-24 for the fp32 fma chain (n roundings per term);
+                        // the fp16 GEMM-form sweep uses its own bound (knn_batch_gamma, knn_batch.hip)
+    // candidate-buffer mode (knn_batch.hip): one list of up to cand_cap entries per query instead of G lists of kp;
+    // the list is cand_segs segments of cand_cap / cand_segs entries; cand_cnt[q * cand_segs + s] = entries offered to segment s
+    // (may exceed the segment: overflow -> exact fallback)
+    const int32_t* cand_cnt = nullptr;
+    int cand_cap = 0, cand_segs = 1;
+    int32_t* cand_cnt_clear = nullptr;   // (threshold stages) = cand_cnt: this query's counters are zeroed once read, for the next sweep's appends
+    float* thr_out = nullptr;            // (threshold stages) thr_out[q] = min(thr_out[q], tau_q - |q|^2 + E rounded up), tau_q = the k-th (= k'-th)
+                                         // exact distance of this stage -- what knn_thr_kernel computed in a launch of its own (round 3)
+    int64_t run_stride = 0;      // 0, or 8 * stride of a threshold stage's sample: candidate id i is store row (i >> 3) * run_stride + (i & 7)
+    int64_t row_offset = 0;
+    const float* part_d = nullptr;
+    const int32_t* part_i = nullptr;
+    const float* part_maxnorm = nullptr;
+    float* outD = nullptr;
+    double* outD64 = nullptr;   // optional: the exact fp64 distances next to their fp32 roundings (shard merges order by these)
+    int64_t* outI = nullptr;
+    int32_t* flags = nullptr;   // [nq] 0 = certified; slot + 1 = exact fallback over fb_S row slabs; -1 = fallback, no slot
+    int32_t* stats = nullptr;   // optional
+    // slab-parallel exact fallback: fb_F slots of fb_S slabs x k (exact distance, id) partial results
+    int fb_S = 0, fb_F = 0;
+    double* fb_d = nullptr;
+    int32_t* fb_i = nullptr;
+    int32_t* fb_slotctr = nullptr;
+    // (threshold stages of the batch path, round 6) 1 = stop after the selection: thr_out[q] = the k'-th smallest SWEEP value of this
+    // stage's candidates, one ulp up (the sweep keeps v < thr).  Those candidates are k' real rows, so at least k' rows of the whole
+    // store pass the next sweep -- all the final merge's certificate asks of a threshold ("nreal >= k'"; a short list sends the
+    // query to the exact fallback).  No row is gathered, nothing is re-ranked: the stage's merge drops from 26 us to its loads +
+    // four radix rounds, and the bound is tighter than tau - |q|^2 + E (no error term: both sides are sweep values).
+    int thr_only = 0;
+};
+constexpr int kKnnSmallN = 8192;                    // rows the small-store search covers
+struct WsTake {                                      // running-offset workspace allocator (256-byte granules)
+    size_t off = 0;
+    size_t operator()(size_t n) { const size_t o = off; off += align_up(n, 256); return o; }
+};
+struct ExactPlan {                                   // workspace and LDS of the exact stages; off_flags is taken by the route's planner
+    int fb_S = 1, fb_F = 1;
+    size_t off_flags = 0, off_fb_d = 0, off_fb_i = 0, off_fb_ctr = 0, merge_lds = 0, fb_lds = 0;
+};
+void knn_exact_plan(ExactPlan* ep, WsTake& take, int k, int kp, int Dp, size_t list_bytes, int fb_F);
+// the fields every route shares (problem, outputs, flags and the fb_* block at their workspace offsets)
+MergeParams knn_merge_params(const float* P, int64_t N, int64_t ldP, const float* Q, int64_t ldQ, int D, int Dp, int k, int kp,
+                             int64_t row_offset, float* outD, double* outD64, int64_t* outI, int32_t* stats, char* ws,
+                             const ExactPlan& ep);
+// ip: the inner-product instantiations.  attr_lds: dynamic-LDS opt-in to set first (0 = the caller's earlier launch did)
+int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream);
+// merge / re-rank, then (N > 0) exact fallback + fallback merge; merge_lds = this launch's share of ep.merge_lds
+int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream);
+int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream);
 
 // Per-call options (ac_bert_config.gemm_arith_opt / ln_fusion_opt / one_launch_opt): for the duration of ONE native call on the
 // calling thread they take precedence over the process-wide switches (ac_gemm_set_arith, ac_gemm_set_ln_fusion,

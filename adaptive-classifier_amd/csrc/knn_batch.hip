@@ -3,7 +3,7 @@
 // 4096 x 10M, configs[4]: 1024 x 2M) -- where the fp32-MFMA sweep of knn_l2.hip is bound by its 157 TFLOP/s pipe.
 //
 // Exactness does not come from the sweep: knn_merge_rerank recomputes the proposed candidates in fp64 and a
-// certificate proves no other row can enter the top-k (knn_l2.hip).  The sweep only has to PROPOSE with a bounded
+// certificate proves no other row can enter the top-k (knn_exact.hip).  The sweep only has to PROPOSE with a bounded
 // error, so it runs on ONE fp16 plane per operand and ONE v_mfma_f32_32x32x16_f16 per tile and 16 k (round 2 used two
 // bf16 planes and three products: 3x the matrix work and 2x the bytes for a bound only 1.75x tighter):
 //   * operands are scaled by powers of two into fp16's normal range -- the store by 2^-e_p with 2^e_p > max |p| (one
@@ -623,11 +623,11 @@ int knn_batch_launch(const uint16_t* Pp, const float* pnorm, int64_t N, int D, c
     //  ~200 accumulator registers per iteration and a lone wave per SIMD hides nothing)
     constexpr int ns = 4, nwv = 8;
     const size_t lds = (size_t)ns * BSLOT * 16;
-    // (per call, like the launch sites of knn_l2.hip: function attributes are per device, and a cached flag is neither)
+    // (per call, like the launch sites of knn_l2.hip and knn_exact.hip: function attributes are per device, and a cached flag is neither)
     AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BatchParams p;
+    BatchParams p{};
     p.Pp = Pp; p.p_rows = (N + 255) / 256 * 256; p.pnorm = pnorm;
     p.q_rows = ((int64_t)nq + 255) / 256 * 256;
     p.row_stride = row_stride < 1 ? 1 : row_stride;

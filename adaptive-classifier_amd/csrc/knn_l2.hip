@@ -3,9 +3,11 @@
 //   /root/reference/src/adaptive_classifier/memory.py:113-114
 // (third-party faiss-cpu>=1.7.4, requirements.txt:4 -- not vendored).
 //
-// Three kernels, all on one stream, no host synchronisation:
+// This file: the three sweeps that build the candidate lists, their planners and the search entry points.  Every route ends in
+// the exact stages of knn_exact.hip (merge + fp64 re-rank + certificate, exact fallback), all on one stream, no host
+// synchronisation:
 //
-//  1. knn_sweep<TQ>   the HBM sweep.  Every prototype row is read from HBM exactly once per
+//  knn_sweep<TQ>      the HBM sweep.  Every prototype row is read from HBM exactly once per
 //                     query tile of TQ queries.  The query tile lives in LDS, pre-scaled by -2
 //                     and pre-arranged in MFMA B-fragment order; prototype rows stream
 //                     HBM -> VGPR (float4 per lane, no LDS round trip: nothing is shared between
@@ -16,14 +18,11 @@
 //                     register; a candidate is pushed to the block's per-query LDS list only if
 //                     acc < tau_q (rare after warm-up).  Lists are pruned to the k' = k+pad best
 //                     by a wave-level rank-by-counting pass, which also tightens tau_q.
-//  2. knn_merge_rerank  per query: radix-select the k' best of the G per-block lists, recompute
-//                     those k' distances exactly (fp64 sum of (p-q)^2), order by (exact, id),
-//                     emit top-k, and certify with an fp32 error bound that no unseen row can
-//                     beat the k-th (see acamd.h "exactness contract").
-//  3. knn_exact_fallback + knn_exact_fb_merge  only for queries whose certificate failed: a plain fp64
-//                     sweep, parallel over row slabs.
+//  knn_sweep_ring     the same sweep for <= 16 queries: rows by non-temporal LDS-DMA, queries in registers (see there).
+//  knn_plane_sweep    one pass over a PREPARED store's fp16 plane for <= 64 queries (see there); larger batches take the
+//                     GEMM-form sweep of knn_batch.hip, launched from ac_knn_l2_topk_batch below.
 //
-// Inner-product search (ac_knn_ip_topk, faiss.IndexFlatIP.search) runs through the same kernels, instantiated with IP = true:
+// Inner-product search (ac_knn_ip_topk, faiss.IndexFlatIP.search) runs through the same sweeps and exact stages, instantiated with IP = true:
 // the sweep value is -2 (p.q)~ (the |p|^2 fold is dropped), and every later stage ranks by the exact key -(p.q) ascending.
 //
 // Roofline: algorithmic bytes per sweep = N*D*4; MFMA time at TQ=32 is
@@ -33,9 +32,14 @@
 #include <float.h>
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 
 namespace {
+
+using ac::ExactPlan;
+using ac::MergeParams;
+using ac::fkey;
+using ac::fkey_inv;
+using ac::next_pow2;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -85,16 +89,6 @@ struct SweepParams {
     int32_t* clear_ctr;   // [64] the merge / fallback kernels' slot counter and ...
     int32_t* clear_stats; // [4] the caller's d_stats (or NULL): zeroed by workgroup 0 here instead of by two memset launches
 };
-
-// monotone map float -> uint32 (ascending float order == ascending unsigned order)
-__device__ __forceinline__ uint32_t fkey(float f) {
-    uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-    uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(b);
-}
 
 // XCD-aware block id remap (cdna guide T1, bijective form): hardware places block b on XCD
 // b % 8; give each XCD a contiguous range of virtual ids so that the nqt query-tile blocks
@@ -892,9 +886,6 @@ __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams 
     }
 }
 
-// --------------------------------------------------------------------------------------
-// merge + exact re-rank + certificate.  One block (256 threads) per query.
-// --------------------------------------------------------------------------------------
 const float* zeros_device() {                 // (the symbol has one address per device)
     static const float* cache[64] = {nullptr};
     int dev = 0;
@@ -904,675 +895,6 @@ const float* zeros_device() {                 // (the symbol has one address per
     return cache[dev];
 }
 
-struct MergeParams {
-    const float* P;
-    int64_t N;
-    int64_t ldP;
-    const float* Q;
-    int64_t ldQ;
-    int D;
-    int Dp;
-    int k;
-    int kp;
-    int G;
-    int nblk;       // entries of part_maxnorm
-    double gamma;   // |sweep value - exact| <= gamma (|p| + |q|)^2: n * 2^-24 for the fp32 fma chain (n roundings per term);
-                    // the fp16 GEMM-form sweep uses its own bound (knn_batch_gamma, knn_batch.hip)
-    // candidate-buffer mode (knn_batch.hip): one list of up to cand_cap entries per query instead of G lists of kp;
-    // the list is cand_segs segments of cand_cap / cand_segs entries; cand_cnt[q * cand_segs + s] = entries offered to segment s
-    // (may exceed the segment: overflow -> exact fallback)
-    const int32_t* cand_cnt;
-    int cand_cap, cand_segs;
-    int32_t* cand_cnt_clear;   // (threshold stages) = cand_cnt: this query's counters are zeroed once read, for the next sweep's appends
-    float* thr_out;            // (threshold stages) thr_out[q] = min(thr_out[q], tau_q - |q|^2 + E rounded up), tau_q = the k-th (= k'-th)
-                               // exact distance of this stage -- what knn_thr_kernel computed in a launch of its own (round 3)
-    int64_t run_stride;      // 0, or 8 * stride of a threshold stage's sample: candidate id i is store row (i >> 3) * run_stride + (i & 7)
-    int64_t row_offset;
-    const float* part_d;
-    const int32_t* part_i;
-    const float* part_maxnorm;
-    float* outD;
-    double* outD64;   // optional: the exact fp64 distances next to their fp32 roundings (shard merges order by these)
-    int64_t* outI;
-    int32_t* flags;   // [nq] 0 = certified; slot + 1 = exact fallback over fb_S row slabs; -1 = fallback, no slot
-    int32_t* stats;   // optional
-    // slab-parallel exact fallback: fb_F slots of fb_S slabs x k (exact distance, id) partial results
-    int fb_S, fb_F;
-    double* fb_d;
-    int32_t* fb_i;
-    int32_t* fb_slotctr;
-    // (threshold stages of the batch path, round 6) 1 = stop after the selection: thr_out[q] = the k'-th smallest SWEEP value of this
-    // stage's candidates, one ulp up (the sweep keeps v < thr).  Those candidates are k' real rows, so at least k' rows of the whole
-    // store pass the next sweep -- all the final merge's certificate asks of a threshold ("nreal >= k'"; a short list sends the
-    // query to the exact fallback).  No row is gathered, nothing is re-ranked: the stage's merge drops from 26 us to its loads +
-    // four radix rounds, and the bound is tighter than tau - |q|^2 + E (no error term: both sides are sweep values).
-    int thr_only = 0;
-};
-
-// Inner-product search (ac_knn_ip_topk, template flag IP below): every stage after the sweep ranks by the exact KEY -(p.q),
-// ascending, ties to the lower id -- the order the L2 stages already implement on their distances.  Negation is exact in fp32
-// and fp64, so the key order is the descending order of p.q; none of the stages assumes a non-negative key (they compare
-// doubles with `<` / `==`, and their padding, +inf with id 0x7fffffff, stays last).  The key is negated back once, where a
-// result is written.  exact_term = one fp64 accumulation step of the exact value: (p - q)^2, or p q (an fp32 product is exact in
-// fp64, so fma(p, q, acc) is the fp64 sum of the exact products).
-template <bool IP>
-__device__ __forceinline__ double exact_term(float p, float q, double acc) {
-    if constexpr (IP) {
-        return fma((double)p, (double)q, acc);
-    } else {
-        const double e = (double)p - (double)q;
-        return fma(e, e, acc);
-    }
-}
-// one output slot: a hit (its exact key, local row id) or faiss-style padding -- (FLT_MAX, -1) for L2, (-FLT_MAX, -1) for IP
-template <bool IP>
-__device__ __forceinline__ void emit_hit(const MergeParams& prm, size_t at, bool real, double key, int64_t id) {
-    const double v = IP ? -key : key;
-    prm.outD[at] = real ? (float)v : (IP ? -FLT_MAX : FLT_MAX);
-    if (prm.outD64) prm.outD64[at] = real ? v : (IP ? -(double)INFINITY : (double)INFINITY);
-    prm.outI[at] = real ? id + prm.row_offset : -1;
-}
-
-constexpr int kMergeThreads = 256;
-
-// Block-wide radix select (8 bits per round) over 32-bit keys held in LDS: returns the `want`-th
-// smallest (1-based) among the entries with active(t) != 0.  On return *rank_in_ties is how many of
-// the entries equal to the result are needed to reach `want`, *n_ties how many such entries exist.
-template <typename KeyFn, typename ActiveFn>
-__device__ __forceinline__ uint32_t block_radix_select(int n, int want, KeyFn key_of, ActiveFn active,
-                                                       int* hist, int* bcast, int* rank_in_ties, int* n_ties) {
-    const int tid = threadIdx.x;
-    __shared__ int wave_tot[kMergeThreads / 64];
-    uint32_t prefix = 0;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        hist[tid] = 0;                       // kMergeThreads == 256 bins
-        __syncthreads();
-        const uint32_t himask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
-        // distances of one query's candidates share their leading bits, so in the first rounds nearly every key lands in
-        // the same bin: run-length aggregation per thread (one LDS atomic per run instead of one per key)
-        int run_bin = -1, run_cnt = 0;
-        for (int t = tid; t < n; t += kMergeThreads) {
-            if (!active(t)) continue;
-            const uint32_t key = key_of(t);
-            if ((key & himask) != (prefix & himask)) continue;
-            const int bin = (int)((key >> shift) & 255u);
-            if (bin == run_bin) { ++run_cnt; continue; }
-            if (run_cnt) atomicAdd(&hist[run_bin], run_cnt);
-            run_bin = bin; run_cnt = 1;
-        }
-        if (run_cnt) atomicAdd(&hist[run_bin], run_cnt);
-        __syncthreads();
-        // exclusive prefix of bin `tid`: wave scan + the totals of the waves below (kMergeThreads == 256 = 4 waves)
-        const int mine_cnt = hist[tid];
-        int c = mine_cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(c, o); if ((tid & 63) >= o) c += v; }
-        if ((tid & 63) == 63) wave_tot[tid >> 6] = c;
-        __syncthreads();
-        for (int w = 0; w < (tid >> 6); ++w) c += wave_tot[w];
-        c -= mine_cnt;
-        const int mine = hist[tid];
-        if (c < want && want <= c + mine) { bcast[0] = tid; bcast[1] = want - c; bcast[2] = mine; }
-        __syncthreads();
-        prefix |= (uint32_t)bcast[0] << shift;
-        want = bcast[1];
-        *n_ties = bcast[2];
-        __syncthreads();
-    }
-    *rank_in_ties = want;
-    return prefix;
-}
-
-template <bool IP>
-__device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, char* smem) {
-    const int q = blockIdx.x;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int n = prm.cand_cnt ? prm.cand_cap : prm.G * prm.kp;
-    const int kp = prm.kp;
-    // candidate mode (knn_batch.hip): the list is cand_segs segments of segcap entries with a count each; the entries in use
-    // are compacted into LDS (keys + ids), so the selection below walks the ~k' * stride real candidates, not the capacity
-    const int segs = prm.cand_cnt ? prm.cand_segs : 1, segcap = n / segs;
-    const bool cand = segs > 1;                            // (one segment: the list is walked in place, like the per-block lists)
-
-    // LDS: keys[n] u32 | (cand) cid[n] i32 | qrow[Dp] f32 | sel[kp] u64 | exact[kp] f64 | hist[256] | misc
-    uint32_t* keys = reinterpret_cast<uint32_t*>(smem);
-    size_t off = ac::align_up((size_t)n * 4, 16);
-    int32_t* cid = reinterpret_cast<int32_t*>(smem + off);
-    if (cand) off += ac::align_up((size_t)n * 4, 16);
-    float* qrow = reinterpret_cast<float*>(smem + off);
-    off += ac::align_up((size_t)prm.Dp * 4, 16);
-    unsigned long long* sel = reinterpret_cast<unsigned long long*>(smem + off);
-    off += (size_t)kp * 8;
-    double* exact = reinterpret_cast<double*>(smem + off);
-    off += (size_t)kp * 8;
-    int* hist = reinterpret_cast<int*>(smem + off);
-    off += 256 * 4;
-    int* misc = reinterpret_cast<int*>(smem + off);       // [0..2] radix broadcast, [4] nsel counter, [5] nreal, [6] segment overflow
-    double* dmisc = reinterpret_cast<double*>(misc + 8);  // [0] qnorm2, [1] exact k-th
-
-    const float* pd = prm.part_d + (size_t)q * n;
-    const int32_t* pi = prm.part_i + (size_t)q * n;
-    if (tid < 8) misc[tid] = 0;
-    for (int c = tid; c < prm.Dp; c += kMergeThreads)
-        qrow[c] = c < prm.D ? prm.Q[(size_t)q * prm.ldQ + c] : 0.f;
-    int nkeys = n;                                         // key slots the selection walks
-    if (cand) {
-        // segment s holds min(count, segcap) entries; exclusive offsets by a block scan (segs <= 256 = one per thread)
-        __shared__ int seg_off[kMergeThreads + 1];
-        __shared__ int scan_tot[kMergeThreads / 64];
-        const int raw = tid < segs ? prm.cand_cnt[(size_t)q * segs + tid] : 0;
-        const int mine = raw < segcap ? raw : segcap;
-        int c = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(c, o); if (lane >= o) c += v; }
-        if (lane == 63) scan_tot[wave] = c;
-        __syncthreads();
-        if (raw > segcap) misc[6] = 1;                     // (benign race: every writer stores 1)
-        for (int w = 0; w < wave; ++w) c += scan_tot[w];
-        seg_off[tid + 1] = c;
-        if (tid == 0) seg_off[0] = 0;
-        __syncthreads();
-        nkeys = seg_off[kMergeThreads];
-        for (int j = tid; j < nkeys; j += kMergeThreads) {
-            int lo = 0, hi = segs;                         // largest s with seg_off[s] <= j
-            while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= j) lo = mid; else hi = mid; }
-            const int t = lo * segcap + (j - seg_off[lo]);
-            keys[j] = fkey(pd[t]);
-            cid[j] = pi[t];
-        }
-        if (tid == 0) misc[5] = nkeys;
-        if (prm.cand_cnt_clear && tid < segs) prm.cand_cnt_clear[(size_t)q * segs + tid] = 0;       // (read above, before the barriers)
-    } else {
-        // monotone 32-bit key of the sweep value; padding (id < 0) and slots past the count sort last
-        const int raw = prm.cand_cnt ? prm.cand_cnt[q] : n;
-        const int nfill = raw < n ? raw : n;
-        if (tid == 0 && raw > n) misc[6] = 1;
-        int nreal_local = 0;
-#pragma unroll 8
-        for (int t = tid; t < n; t += kMergeThreads) {      // (unrolled: the loads of several candidates in flight)
-            const bool real = t < nfill && pi[t] >= 0;
-            keys[t] = real ? fkey(pd[t]) : 0xffffffffu;
-            nreal_local += real ? 1 : 0;
-        }
-        __syncthreads();
-        atomicAdd(&misc[5], nreal_local);
-        if (prm.cand_cnt_clear && tid == 0) prm.cand_cnt_clear[q] = 0;
-    }
-    __syncthreads();
-    const bool overflow = misc[6] != 0;
-    const int nreal = misc[5];
-    const int nsel = nreal < kp ? nreal : kp;     // how many candidates we re-rank
-    auto id_of = [&](int t) -> int32_t { return cand ? cid[t] : pi[t]; };
-
-    // ---- the nsel-th smallest sweep value T; ties at T are resolved by the lowest ids ----
-    uint32_t T = 0xffffffffu;
-    int32_t tie_id_max = 0x7fffffff;
-    if (nsel > 0) {
-        int r = 0, c_eq = 0;
-        T = block_radix_select(nkeys, nsel, [&](int t) { return keys[t]; },
-                               [&](int t) { return keys[t] != 0xffffffffu; }, hist, misc, &r, &c_eq);
-        if (c_eq != r) {     // rare: several candidates share the boundary value -> r lowest ids of them
-            int r2 = 0, c2 = 0;
-            tie_id_max = (int32_t)block_radix_select(
-                nkeys, r, [&](int t) { return (uint32_t)id_of(t); },
-                [&](int t) { return keys[t] != 0xffffffffu && keys[t] == T; }, hist, misc, &r2, &c2);
-        }
-    }
-    if (prm.thr_only) {
-        if (tid == 0 && prm.thr_out && nreal >= kp && nsel > 0) {
-            const float t = nextafterf(fkey_inv(T), INFINITY);
-            if (t < prm.thr_out[q]) prm.thr_out[q] = t;
-        }
-        return;
-    }
-    // ---- compact the selected candidates ----
-    for (int t = tid; t < nkeys; t += kMergeThreads) {
-        const uint32_t key0 = keys[t];
-        const int32_t id = key0 != 0xffffffffu ? id_of(t) : -1;
-        if (nsel > 0 && id >= 0) {
-            const uint32_t key = key0;
-            if (key < T || (key == T && id <= tie_id_max)) {
-                const int s = atomicAdd(&misc[4], 1);
-                if (s < kp) sel[s] = ((unsigned long long)key << 32) | (uint32_t)id;
-            }
-        }
-    }
-    __syncthreads();
-    const int ns = misc[4] < kp ? misc[4] : kp;
-    const unsigned long long T64 = (unsigned long long)T << 32;
-
-    // ---- exact fp64 distances of the selected rows; |q|^2 ----
-    // Four rows per wave at a time: their loads are issued together, so a wave pays the (random-row, HBM) latency once per
-    // group instead of once per row -- the per-row arithmetic (four accumulators over c4 = lane, lane + 64, ..., the
-    // (a0 + a1) + (a2 + a3) fold, the xor-shuffle tree) is unchanged, hence the same bits.  (One row at a time this loop was
-    // most of the kernel: ~20 of its 27 - 32 us.)
-    const int nc4 = prm.Dp >> 2;
-    constexpr int RU = 4;
-    for (int s0 = wave * RU; s0 < ns; s0 += (kMergeThreads / 64) * RU) {
-        const f32x4* prow[RU];
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-            const int s = s0 + u < ns ? s0 + u : s0;                  // (a short last group re-reads its first row)
-            const int32_t id = (int32_t)(uint32_t)(sel[s] & 0xffffffffull);
-            const int64_t prow_i = prm.run_stride ? (int64_t)(id >> 3) * prm.run_stride + (id & 7) : (int64_t)id;     // (threshold stages: sample row -> store row)
-            prow[u] = reinterpret_cast<const f32x4*>(prm.P + (size_t)prow_i * prm.ldP);
-        }
-        double acc[RU][4];
-#pragma unroll
-        for (int u = 0; u < RU; ++u) { acc[u][0] = 0; acc[u][1] = 0; acc[u][2] = 0; acc[u][3] = 0; }
-#pragma unroll 2
-        for (int c4 = lane; c4 < nc4; c4 += 64) {
-            f32x4 p[RU];
-#pragma unroll
-            for (int u = 0; u < RU; ++u) p[u] = prow[u][c4];
-            const f32x4 qq = *reinterpret_cast<const f32x4*>(qrow + 4 * c4);
-#pragma unroll
-            for (int u = 0; u < RU; ++u) {
-                acc[u][0] = exact_term<IP>(p[u].x, qq.x, acc[u][0]); acc[u][1] = exact_term<IP>(p[u].y, qq.y, acc[u][1]);
-                acc[u][2] = exact_term<IP>(p[u].z, qq.z, acc[u][2]); acc[u][3] = exact_term<IP>(p[u].w, qq.w, acc[u][3]);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RU; ++u) {
-            double a = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
-            if (lane == 0 && s0 + u < ns) exact[s0 + u] = IP ? -a : a;          // (inner product: the key -(p.q))
-        }
-    }
-    if (wave == 0) {
-        double a = 0;
-        for (int c = lane; c < prm.Dp; c += 64) a = fma((double)qrow[c], (double)qrow[c], a);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
-        if (lane == 0) { dmisc[0] = a; dmisc[1] = INFINITY; }
-    }
-    __syncthreads();
-
-    // ---- final order by (exact, id); emit top-k ----
-    const int kout = prm.k;
-    for (int t = tid; t < ns; t += kMergeThreads) {
-        const double dt = exact[t];
-        const uint32_t it = (uint32_t)(sel[t] & 0xffffffffull);
-        int rank = 0;
-        for (int s = 0; s < ns; ++s) {
-            const double ds = exact[s];
-            const uint32_t is = (uint32_t)(sel[s] & 0xffffffffull);
-            rank += (ds < dt || (ds == dt && is < it)) ? 1 : 0;
-        }
-        if (rank < kout) emit_hit<IP>(prm, (size_t)q * kout + rank, true, dt, (int64_t)it);
-        if (rank == kout - 1) dmisc[1] = dt;
-    }
-    for (int t = ns + tid; t < kout; t += kMergeThreads)    // k > N: faiss-style padding
-        emit_hit<IP>(prm, (size_t)q * kout + t, false, 0.0, -1);
-    __syncthreads();
-
-    // ---- certificate ----
-    // largest row norm seen by the sweep: the per-block maxima reduced by the whole workgroup (a one-thread loop over up to
-    // 512 global loads was most of this kernel's time for a single query)
-    float mx_all = 0.f;
-    for (int b = tid; b < prm.nblk; b += kMergeThreads) mx_all = fmaxf(mx_all, prm.part_maxnorm[b]);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) mx_all = fmaxf(mx_all, __shfl_xor(mx_all, o));
-    if (lane == 0) hist[wave] = (int)__float_as_uint(mx_all);           // (norms are non-negative: their bits order like the values)
-    __syncthreads();
-    if (tid == 0 && prm.thr_out) {
-        // threshold stage: the k-th (= k'-th) exact distance of this sample bounds the store's k'-th smallest distance
-        float mx = 0.f;
-        for (int w = 0; w < kMergeThreads / 64; ++w) mx = fmaxf(mx, __uint_as_float((uint32_t)hist[w]));
-        const double qn2 = dmisc[0], tau = dmisc[1];
-        const double pn = sqrt((double)mx * 1.001), qn = sqrt(qn2);
-        const double E = prm.gamma * (pn + qn) * (pn + qn) + 1e-30;
-        float t = (float)(tau - qn2 + E);
-        if ((double)t < tau - qn2 + E) t = nextafterf(t, INFINITY);
-        // a stage that kept fewer than k' rows for this query has no k'-th distance to offer: the threshold of the stage before it
-        // (still a valid bound) stays; a valid new bound only ever tightens it
-        if (isfinite(tau) && ns >= kout && t < prm.thr_out[q]) prm.thr_out[q] = t;
-    }
-    if (tid == 0) {
-        int ok = 1;
-        if (prm.N > (int64_t)kp) {
-            float mx = 0.f;
-            for (int w = 0; w < kMergeThreads / 64; ++w) mx = fmaxf(mx, __uint_as_float((uint32_t)hist[w]));
-            const double qn2 = dmisc[0];
-            const double pn = sqrt((double)mx * 1.001), qn = sqrt(qn2);
-            // fp32 fma-chain roundoff of |p|^2 - 2 q.p: every term passes through at most
-            // nterms roundings, so |err| <= gamma_n * (|p|^2 + 2 sum|q_i p_i|) <= gamma_n (|p|+|q|)^2
-            const double E = prm.gamma * (pn + qn) * (pn + qn) + 1e-30;
-            const double a_last = (double)fkey_inv((uint32_t)(T64 >> 32));
-            // every row that was NOT re-ranked has sweep value >= a_last, hence exact
-            // distance >= a_last - E + |q|^2.  The k-th re-ranked must beat that strictly.
-            const double kth = dmisc[1];
-            if constexpr (IP) {
-                // inner product: the sweep value is v = -2 (p.q)~, the same fma chain without the |p|^2 terms, so
-                // |v - (-2 p.q)| <= gamma_n * 2 sum|q_i p_i| <= gamma_n * 2 |p||q| <= gamma_n (|p|max + |q|)^2 = E.  Every row that
-                // was NOT re-ranked has v >= a_last, hence -2 p.q >= a_last - E, i.e. p.q <= -(a_last - E) / 2: its key -(p.q) is
-                // >= (a_last - E) / 2 (halving is exact).  The k-th re-ranked key must lie strictly below that, i.e. the k-th exact
-                // inner product strictly above every value an unseen row can have.
-                ok = (ns >= kout) && (kth < 0.5 * (a_last - E)) && !overflow;
-            } else {
-                ok = (ns >= kout) && (kth < a_last - E + qn2) && !overflow;
-            }
-            if (prm.cand_cnt && nreal < kp) ok = 0;      // fewer than k' candidates kept: the "unseen rows >= a_last" premise is gone
-        }
-        int flag = 0;
-        if (!ok) {
-            const int slot = atomicAdd(prm.fb_slotctr, 1);
-            flag = slot < prm.fb_F ? slot + 1 : -1;
-            if (prm.stats) atomicAdd(&prm.stats[0], 1);
-        }
-        prm.flags[q] = flag;
-    }
-}
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    knn_merge_rerank_body<false>(prm, smem);
-}
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank_ip(MergeParams prm) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    knn_merge_rerank_body<true>(prm, smem);
-}
-
-// --------------------------------------------------------------------------------------
-// exact fallback: fp64 sweep for the (rare) queries whose certificate failed.
-// One block per query; exits immediately unless flagged.
-// --------------------------------------------------------------------------------------
-constexpr int kFbThreads = 512;
-constexpr int kFbWaves = kFbThreads / 64;
-constexpr int kFbCap = 1024;          // list capacity (k <= 248 -> prune keeps k)
-constexpr int kFbRound = 32;          // rows per wave between barriers
-
-// grid = (fb_S, nq): block (s, q) scans row slab s of a flagged query and writes its exact top-k to the
-// query's slot; knn_exact_fb_merge then merges the slabs.  A flagged query without a slot (more than fb_F
-// failures in one call) is handled by its s == 0 block alone over the whole store.
-// (round 6: the grid is (fb_S, min(nq, kFbQueryGroups)) and a block walks the queries q = blockIdx.y, + gridDim.y, ...: with
-//  no query flagged -- every call of an ordinary batch -- dispatching fb_S x nq = 16 384 empty 512-thread blocks cost 8.5 us;
-//  fb_S x 8 cost 2.  A device holds <= ~1000 of these blocks at once, so flagged batches lose nothing.)
-constexpr int kFbQueryGroups = 8, kFbMergeGroups = 32;
-template <bool IP>
-__device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm, const int q, const int slab, char* smem) {
-    const int flag = prm.flags[q];
-    if (flag == 0 || (flag < 0 && slab != 0)) return;
-    const bool direct = flag < 0;
-    const int64_t row_lo = direct ? 0 : (prm.N * slab) / prm.fb_S;
-    const int64_t row_hi = direct ? prm.N : (prm.N * (slab + 1)) / prm.fb_S;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double* ld = reinterpret_cast<double*>(smem);                  // [kFbCap]
-    int32_t* li = reinterpret_cast<int32_t*>(ld + kFbCap);         // [kFbCap]
-    float* qrow = reinterpret_cast<float*>(li + kFbCap);           // [Dp]
-    int* misc = reinterpret_cast<int*>(qrow + ac::align_up((size_t)prm.Dp, 4));  // [0] cnt
-    double* tau_d = reinterpret_cast<double*>(misc + 4);
-    int32_t* tau_i = reinterpret_cast<int32_t*>(tau_d + 1);
-
-    for (int c = tid; c < prm.Dp; c += kFbThreads)
-        qrow[c] = c < prm.D ? prm.Q[(size_t)q * prm.ldQ + c] : 0.f;
-    if (tid == 0) { misc[0] = 0; *tau_d = INFINITY; *tau_i = 0x7fffffff; }
-    __syncthreads();
-    const int nc4 = prm.Dp >> 2;
-    const int k = prm.k;
-
-    auto prune = [&]() {
-        // block-wide rank-by-counting over cnt <= kFbCap entries (2 per thread)
-        const int n = misc[0] < kFbCap ? misc[0] : kFbCap;
-        double myd[2]; int32_t myi[2]; int rank[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int s = tid + kFbThreads * e;
-            myd[e] = s < n ? ld[s] : INFINITY;
-            myi[e] = s < n ? li[s] : 0x7fffffff;
-            rank[e] = 0;
-        }
-        for (int s = 0; s < n; ++s) {
-            const double d = ld[s]; const int32_t i = li[s];
-#pragma unroll
-            for (int e = 0; e < 2; ++e) rank[e] += (d < myd[e] || (d == myd[e] && i < myi[e])) ? 1 : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int s = tid + kFbThreads * e;
-            if (s < n && rank[e] < k) {
-                ld[rank[e]] = myd[e]; li[rank[e]] = myi[e];
-                if (rank[e] == k - 1) { *tau_d = myd[e]; *tau_i = myi[e]; }
-            }
-        }
-        if (tid == 0) misc[0] = n < k ? n : k;
-        __syncthreads();
-    };
-
-    for (int64_t base = row_lo; base < row_hi; base += (int64_t)kFbWaves * kFbRound) {
-        const double td = *tau_d; const int32_t ti = *tau_i;
-        for (int m = 0; m < kFbRound; ++m) {
-            const int64_t row = base + (int64_t)m * kFbWaves + wave;
-            if (row >= row_hi) break;
-            const f32x4* prow = reinterpret_cast<const f32x4*>(prm.P + (size_t)row * prm.ldP);
-            double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            for (int c4 = lane; c4 < nc4; c4 += 64) {
-                const f32x4 p = prow[c4];
-                const f32x4 qq = *reinterpret_cast<const f32x4*>(qrow + 4 * c4);
-                a0 = exact_term<IP>(p.x, qq.x, a0); a1 = exact_term<IP>(p.y, qq.y, a1);
-                a2 = exact_term<IP>(p.z, qq.z, a2); a3 = exact_term<IP>(p.w, qq.w, a3);
-            }
-            double a = (a0 + a1) + (a2 + a3);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
-            if (IP) a = -a;                 // (inner product: the key -(p.q); the same bits knn_merge_rerank computes for this row)
-            if (lane == 0 && (a < td || (a == td && (int32_t)row < ti))) {
-                const int s = atomicAdd(&misc[0], 1);
-                if (s < kFbCap) { ld[s] = a; li[s] = (int32_t)row; }
-            }
-        }
-        __syncthreads();
-        const int c_now = misc[0];      // read between two barriers: identical for every thread
-        __syncthreads();
-        if (c_now > kFbCap - kFbWaves * kFbRound) prune();
-    }
-    prune();
-    const int n = misc[0];
-    if (direct) {
-        for (int t = tid; t < k; t += kFbThreads) emit_hit<IP>(prm, (size_t)q * k + t, t < n, ld[t], (int64_t)li[t]);    // (k <= kFbCap)
-    } else {
-        const size_t base = ((size_t)(flag - 1) * prm.fb_S + slab) * k;
-        for (int t = tid; t < k; t += kFbThreads) {
-            prm.fb_d[base + t] = t < n ? ld[t] : INFINITY;
-            prm.fb_i[base + t] = t < n ? li[t] : 0x7fffffff;
-        }
-    }
-}
-__global__ __launch_bounds__(kFbThreads) void knn_exact_fallback(MergeParams prm, int nq) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    for (int q = blockIdx.y; q < nq; q += gridDim.y) {
-        knn_exact_fallback_query<false>(prm, q, blockIdx.x, smem);
-        __syncthreads();                                            // (the next query reuses the lists)
-    }
-}
-__global__ __launch_bounds__(kFbThreads) void knn_exact_fallback_ip(MergeParams prm, int nq) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    for (int q = blockIdx.y; q < nq; q += gridDim.y) {
-        knn_exact_fallback_query<true>(prm, q, blockIdx.x, smem);
-        __syncthreads();
-    }
-}
-
-// merge the fb_S slab results of a flagged query: bitonic sort of fb_S * k (<= 4096) exact entries
-template <bool IP>
-__device__ __forceinline__ void knn_exact_fb_merge_query(const MergeParams& prm, const int npow2, const int q, char* smem) {
-    const int tid = threadIdx.x;
-    const int flag = prm.flags[q];
-    if (flag <= 0) return;
-    double* ds = reinterpret_cast<double*>(smem);
-    int32_t* is = reinterpret_cast<int32_t*>(ds + npow2);
-    const int n = prm.fb_S * prm.k;
-    const size_t base = (size_t)(flag - 1) * n;
-    for (int t = tid; t < npow2; t += 256) {
-        ds[t] = t < n ? prm.fb_d[base + t] : INFINITY;
-        is[t] = t < n ? prm.fb_i[base + t] : 0x7fffffff;
-    }
-    __syncthreads();
-    for (int size = 2; size <= npow2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (npow2 >> 1); t += 256) {
-                const int lo = 2 * t - (t & (stride - 1));
-                const int hi = lo + stride;
-                const bool asc = (lo & size) == 0;
-                const double dl = ds[lo], dh = ds[hi];
-                const int32_t il = is[lo], ih = is[hi];
-                const bool gt = dl > dh || (dl == dh && il > ih);
-                if (gt == asc) { ds[lo] = dh; ds[hi] = dl; is[lo] = ih; is[hi] = il; }
-            }
-            __syncthreads();
-        }
-    for (int t = tid; t < prm.k; t += 256) emit_hit<IP>(prm, (size_t)q * prm.k + t, is[t] != 0x7fffffff, ds[t], (int64_t)is[t]);
-}
-__global__ __launch_bounds__(256) void knn_exact_fb_merge(MergeParams prm, int npow2, int nq) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-        knn_exact_fb_merge_query<false>(prm, npow2, q, smem);
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(256) void knn_exact_fb_merge_ip(MergeParams prm, int npow2, int nq) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    for (int q = blockIdx.x; q < nq; q += gridDim.x) {
-        knn_exact_fb_merge_query<true>(prm, npow2, q, smem);
-        __syncthreads();
-    }
-}
-
-// --------------------------------------------------------------------------------------
-// shard merge and prototype scores
-// --------------------------------------------------------------------------------------
-// DESC = the inner-product form: per-shard DESCENDING lists -> global top-k by (value descending, id ascending); padding
-// (id < 0) comes out as (-FLT_MAX, -1).  Pure selection either way.
-template <typename DT, bool DESC = false>
-__global__ __launch_bounds__(256) void topk_merge_kernel(const DT* Din, const int64_t* Iin,
-                                                         int shards, int nq, int k, float* outD,
-                                                         int64_t* outI) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const int n = shards * k;
-    int64_t* ids = reinterpret_cast<int64_t*>(smem);
-    DT* ds = reinterpret_cast<DT*>(ids + n);
-    for (int t = tid; t < n; t += 256) {
-        const int s = t / k, e = t - s * k;
-        ids[t] = Iin[((size_t)s * nq + q) * k + e];
-        ds[t] = Din[((size_t)s * nq + q) * k + e];
-    }
-    for (int t = tid; t < k; t += 256) { outD[(size_t)q * k + t] = DESC ? -FLT_MAX : FLT_MAX; outI[(size_t)q * k + t] = -1; }
-    __syncthreads();
-    for (int t = tid; t < n; t += 256) {
-        const int64_t it = ids[t];
-        if (it < 0) continue;
-        const DT dt = ds[t];
-        int rank = 0;
-        for (int s = 0; s < n; ++s) {
-            const int64_t is = ids[s];
-            if (is < 0) continue;
-            const DT d = ds[s];
-            rank += ((DESC ? d > dt : d < dt) || (d == dt && (is < it || (is == it && s < t)))) ? 1 : 0;
-        }
-        if (rank < k) { outD[(size_t)q * k + rank] = (float)dt; outI[(size_t)q * k + rank] = it; }
-    }
-}
-
-// memory.py:117 (exp(-d)) and :129-130 (softmax over the hits), one wave per query
-__global__ __launch_bounds__(64) void proto_scores_kernel(const float* D, const int64_t* I, int nq,
-                                                          int k, float* out) {
-    const int q = blockIdx.x, lane = threadIdx.x;
-    float mx = -INFINITY;
-    for (int e = lane; e < k; e += 64)
-        if (I[(size_t)q * k + e] >= 0) mx = fmaxf(mx, expf(-D[(size_t)q * k + e]));
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    float sum = 0.f;
-    for (int e = lane; e < k; e += 64)
-        if (I[(size_t)q * k + e] >= 0) sum += expf(expf(-D[(size_t)q * k + e]) - mx);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) sum += __shfl_xor(sum, o);
-    for (int e = lane; e < k; e += 64) {
-        const bool v = I[(size_t)q * k + e] >= 0;
-        out[(size_t)q * k + e] = v ? expf(expf(-D[(size_t)q * k + e]) - mx) / sum : 0.f;
-    }
-}
-
-// row ids of the hits -> class ids through the row->class map (index_to_label, memory.py:123,174;
-// generalised int32 map of SURVEY 8a M6); padding (id < 0) and out-of-range ids give -1
-__global__ __launch_bounds__(256) void rows_to_class_kernel(const int64_t* I, int64_t n, const int32_t* row_class,
-                                                            int64_t nrows, const int64_t* class_lut, int nlut,
-                                                            int64_t* out) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n) return;
-    const int64_t id = I[t];
-    int64_t c = -1;
-    if (id >= 0 && id < nrows) {
-        c = row_class ? (int64_t)row_class[id] : id;
-        if (class_lut) c = (c >= 0 && c < nlut) ? class_lut[c] : -1;
-    }
-    out[t] = c;
-}
-
-// --------------------------------------------------------------------------------------
-// small-store exact path: N <= kSmallN rows, ANY k <= N and ANY D.  The reference searches with
-// k = #classes (classifier.py:424-425), so k can exceed the fused sweep's limit while N (= #classes,
-// one prototype per class) stays tiny.  One block per query: fp64 distance of every row, full bitonic
-// sort of (distance, id) in LDS, emit the first k.  Exact by construction (no certificate needed).
-// --------------------------------------------------------------------------------------
-constexpr int kSmallN = 8192;
-constexpr int kSmallThreads = 256;
-
-template <bool IP>
-__device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int npow2, char* smem) {
-    double* ds = reinterpret_cast<double*>(smem);                // [npow2]
-    int32_t* is = reinterpret_cast<int32_t*>(ds + npow2);        // [npow2]
-    const int q = blockIdx.x, tid = threadIdx.x;
-    const float* qv = prm.Q + (size_t)q * prm.ldQ;
-    for (int r = tid; r < npow2; r += kSmallThreads) {
-        double a = INFINITY;
-        if (r < prm.N) {
-            const float* p = prm.P + (size_t)r * prm.ldP;
-            double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            int c = 0;
-            for (; c + 3 < prm.D; c += 4) {
-                a0 = exact_term<IP>(p[c], qv[c], a0); a1 = exact_term<IP>(p[c + 1], qv[c + 1], a1);
-                a2 = exact_term<IP>(p[c + 2], qv[c + 2], a2); a3 = exact_term<IP>(p[c + 3], qv[c + 3], a3);
-            }
-            for (; c < prm.D; ++c) a0 = exact_term<IP>(p[c], qv[c], a0);
-            a = (a0 + a1) + (a2 + a3);
-            if (IP) a = -a;                                      // (inner product: the key -(p.q))
-        }
-        ds[r] = a;
-        is[r] = r < prm.N ? r : 0x7fffffff;
-    }
-    __syncthreads();
-    for (int size = 2; size <= npow2; size <<= 1)
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = tid; t < (npow2 >> 1); t += kSmallThreads) {
-                const int lo = 2 * t - (t & (stride - 1));       // index with bit `stride` cleared
-                const int hi = lo + stride;
-                const bool asc = (lo & size) == 0;
-                const double dl = ds[lo], dh = ds[hi];
-                const int32_t il = is[lo], ih = is[hi];
-                const bool gt = dl > dh || (dl == dh && il > ih);
-                if (gt == asc) { ds[lo] = dh; ds[hi] = dl; is[lo] = ih; is[hi] = il; }
-            }
-            __syncthreads();
-        }
-    for (int t = tid; t < prm.k; t += kSmallThreads) {
-        const bool real = t < prm.N;                             // (k may exceed npow2: the lists are read for real hits only)
-        emit_hit<IP>(prm, (size_t)q * prm.k + t, real, real ? ds[t] : 0.0, real ? (int64_t)is[t] : -1);
-    }
-}
-__global__ __launch_bounds__(kSmallThreads) void knn_small_exact(MergeParams prm, int npow2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    knn_small_exact_body<false>(prm, npow2, smem);
-}
-__global__ __launch_bounds__(kSmallThreads) void knn_small_exact_ip(MergeParams prm, int npow2) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    knn_small_exact_body<true>(prm, npow2, smem);
-}
-
 // ---- host-side planning ----
 struct Plan {
     bool small;          // knn_small_exact instead of the fused sweep
@@ -1580,47 +902,38 @@ struct Plan {
     int TQ, kp, cap, ng, Dp, G, nqt;
     int ring;            // 0, or the chunks per wave of knn_sweep_ring (<= 16 queries, D % 32 == 0, D <= 768)
     int64_t ntiles;
-    size_t sweep_lds, merge_lds, fb_lds;
-    size_t off_part_d, off_part_i, off_maxnorm, off_flags, off_zeros, off_fb_d, off_fb_i, off_fb_ctr, total;
-    int fb_S, fb_F;
+    size_t sweep_lds;
+    size_t off_part_d, off_part_i, off_maxnorm, off_zeros, total;
+    ExactPlan ex;
 };
 
-static int next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+// AC_KNN_G (tuning experiments): the sweep grid's row groups; each planner applies its own clamp.  0 = not set
+static int64_t env_knn_g() { const char* e = getenv("AC_KNN_G"); const int64_t v = e ? atoll(e) : 0; return v >= 1 ? v : 0; }
 
 static int make_plan(int64_t N, int D, int nq, int k, Plan* pl) {
     AC_REQUIRE(N >= 0 && N < 2147483647LL, AC_EINVAL, "knn: N=%lld out of range", (long long)N);
     AC_REQUIRE(D >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "knn: bad D=%d nq=%d k=%d", D, nq, k);
-    pl->small = false;
-    pl->ring = 0;
+    *pl = Plan{};
     pl->Dp = (D + 3) / 4 * 4;
-    {   // does the fused sweep cover (D, k)?  LDS: one 16-query tile + its candidate lists
-        const int kp = k + kPad;
-        int cap = next_pow2(2 * kp);
-        if (cap < 64) cap = 64;
-        const int ng = (pl->Dp + 16 * kGroup - 1) / (16 * kGroup);
-        const size_t lds16 = (size_t)ng * kGroup * 64 * 16 + (size_t)16 * cap * 8 + 16 * 8 + kWaves * 4 + 64;
-        if (k > AC_KNN_MAX_K || lds16 > (size_t)kLdsLimit) {
-            AC_REQUIRE(N <= kSmallN, AC_EUNSUPPORTED,
-                       "knn: k=%d, D=%d is outside the fused sweep (k <= %d, query tile + lists <= %d B of LDS) and "
-                       "N=%lld exceeds the small-store path (N <= %d)", k, D, AC_KNN_MAX_K, kLdsLimit, (long long)N,
-                       kSmallN);
-            pl->small = true;
-            pl->small_pow2 = next_pow2((int)(N > 2 ? N : 2));
-            pl->TQ = 16; pl->kp = 0; pl->cap = 0; pl->ng = 0; pl->G = 1; pl->nqt = 1; pl->ntiles = 0;
-            pl->sweep_lds = pl->merge_lds = pl->fb_lds = 0;
-            pl->off_part_d = pl->off_part_i = pl->off_maxnorm = pl->off_flags = pl->off_zeros = 0;
-            pl->off_fb_d = pl->off_fb_i = pl->off_fb_ctr = 0; pl->fb_S = pl->fb_F = 1;
-            pl->total = 256;
-            return AC_OK;
-        }
-    }
     pl->kp = k + kPad;
     pl->cap = next_pow2(2 * pl->kp);
     if (pl->cap < 64) pl->cap = 64;
+    pl->ng = (pl->Dp + 16 * kGroup - 1) / (16 * kGroup);
+    // does the fused sweep cover (D, k)?  LDS: one 16-query tile + its candidate lists
+    const size_t lds16 = (size_t)pl->ng * kGroup * 64 * 16 + (size_t)16 * pl->cap * 8 + 16 * 8 + kWaves * 4 + 64;
+    if (k > AC_KNN_MAX_K || lds16 > (size_t)kLdsLimit) {
+        AC_REQUIRE(N <= ac::kKnnSmallN, AC_EUNSUPPORTED,
+                   "knn: k=%d, D=%d is outside the fused sweep (k <= %d, query tile + lists <= %d B of LDS) and "
+                   "N=%lld exceeds the small-store path (N <= %d)", k, D, AC_KNN_MAX_K, kLdsLimit, (long long)N,
+                   ac::kKnnSmallN);
+        pl->small = true;
+        pl->small_pow2 = next_pow2((int)(N > 2 ? N : 2));
+        pl->TQ = 16; pl->G = 1; pl->nqt = 1;
+        pl->total = 256;
+        return AC_OK;
+    }
     int TQ = nq > 16 ? 32 : 16;
     for (;;) {
-        const int kcols = 16;
-        pl->ng = (pl->Dp + kcols * kGroup - 1) / (kcols * kGroup);
         pl->sweep_lds = (size_t)(TQ / 16) * pl->ng * kGroup * 64 * 16 + (size_t)TQ * pl->cap * 8 + TQ * 8 +
                         kWaves * 4 + 64;
         if (pl->sweep_lds <= (size_t)kLdsLimit) break;
@@ -1658,32 +971,21 @@ static int make_plan(int64_t N, int D, int nq, int k, Plan* pl) {
         G = kMergeMaxCand / pl->kp;
         if (pl->nqt == 1 && G > di.cus) G = G / di.cus * di.cus;
     }
-    if (const char* e = getenv("AC_KNN_G")) { int64_t v = atoll(e); if (v >= 1) G = v; }   // tuning experiments
+    if (const int64_t v = env_knn_g()) G = v;
     if (G > pl->ntiles) G = pl->ntiles;
     if (G > kMergeMaxCand / pl->kp) G = kMergeMaxCand / pl->kp;
     if (G < 1) G = 1;
     pl->G = (int)G;
     const size_t nqpad = (size_t)pl->nqt * TQ;
     const size_t ncand = nqpad * pl->G * pl->kp;
-    size_t off = 0;
-    pl->off_part_d = off; off += ac::align_up(ncand * 4, 256);
-    pl->off_part_i = off; off += ac::align_up(ncand * 4, 256);
-    pl->off_maxnorm = off; off += ac::align_up((size_t)pl->G * pl->nqt * 4, 256);
-    pl->off_flags = off; off += ac::align_up((size_t)(nq > 0 ? nq : 1) * 4, 256);
-    pl->off_zeros = off; off += 256;
-    // slab-parallel exact fallback: fb_S * k <= 4096 entries per slot, up to 64 slots
-    pl->fb_S = 4096 / next_pow2(k);
-    if (pl->fb_S > 64) pl->fb_S = 64;
-    if (pl->fb_S < 1) pl->fb_S = 1;
-    pl->fb_F = nq < 64 ? (nq > 0 ? nq : 1) : 64;
-    const size_t fb_entries = (size_t)pl->fb_F * pl->fb_S * k;
-    pl->off_fb_d = off; off += ac::align_up(fb_entries * 8, 256);
-    pl->off_fb_i = off; off += ac::align_up(fb_entries * 4, 256);
-    pl->off_fb_ctr = off; off += 256;
-    pl->total = off;
-    pl->merge_lds = ac::align_up((size_t)pl->G * pl->kp * 4, 16) + ac::align_up((size_t)pl->Dp * 4, 16) +
-                    (size_t)pl->kp * 16 + 256 * 4 + 64;
-    pl->fb_lds = (size_t)kFbCap * 12 + ac::align_up((size_t)pl->Dp, 4) * 4 + 64;
+    ac::WsTake take;
+    pl->off_part_d = take(ncand * 4);
+    pl->off_part_i = take(ncand * 4);
+    pl->off_maxnorm = take((size_t)pl->G * pl->nqt * 4);
+    pl->ex.off_flags = take((size_t)(nq > 0 ? nq : 1) * 4);
+    pl->off_zeros = take(256);
+    ac::knn_exact_plan(&pl->ex, take, k, pl->kp, pl->Dp, ac::align_up((size_t)pl->G * pl->kp * 4, 16), nq < 64 ? (nq > 0 ? nq : 1) : 64);
+    pl->total = take.off;
     return AC_OK;
 }
 
@@ -1738,41 +1040,25 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
     if (d_stats && (pl.small || N == 0)) AC_HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(int32_t), stream));
     if (pl.small) {
         MergeParams sp;
-        memset(&sp, 0, sizeof(sp));
         sp.P = d_P; sp.N = N; sp.ldP = ldP; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.k = k; sp.row_offset = row_offset;
         sp.outD = d_outD; sp.outD64 = d_outD64; sp.outI = d_outI;
-        const size_t lds = (size_t)pl.small_pow2 * 12;
-        void (*small_fn)(MergeParams, int) = ip ? knn_small_exact_ip : knn_small_exact;
-        (void)hipFuncSetAttribute((const void*)small_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(small_fn, dim3(nq), dim3(kSmallThreads), lds, stream, sp, pl.small_pow2);
-        AC_LAUNCH_CHECK();
-        return AC_OK;
+        return ac::knn_small_exact_launch(ip, sp, nq, pl.small_pow2, stream);
     }
 
-    MergeParams mp;
-    mp.P = d_P; mp.N = N; mp.ldP = ldP; mp.Q = d_Q; mp.ldQ = ldQ; mp.D = D; mp.Dp = pl.Dp;
-    mp.k = k; mp.kp = pl.kp; mp.G = pl.G; mp.nblk = pl.G * pl.nqt;
+    MergeParams mp = ac::knn_merge_params(d_P, N, ldP, d_Q, ldQ, D, pl.Dp, k, pl.kp, row_offset, d_outD, d_outD64, d_outI, d_stats, ws, pl.ex);
+    mp.G = pl.G; mp.nblk = pl.G * pl.nqt;
     mp.gamma = 1.01 * (double)(pl.ng * kGroup * 16 + 16) * 5.9604644775390625e-08;    // n * 2^-24, n roundings per term
-    mp.cand_cnt = nullptr; mp.cand_cap = 0; mp.cand_segs = 1; mp.run_stride = 0; mp.cand_cnt_clear = nullptr; mp.thr_out = nullptr;
-    mp.row_offset = row_offset;
     mp.part_d = (const float*)(ws + pl.off_part_d);
     mp.part_i = (const int32_t*)(ws + pl.off_part_i);
     mp.part_maxnorm = (const float*)(ws + pl.off_maxnorm);
-    mp.outD = d_outD; mp.outD64 = d_outD64; mp.outI = d_outI;
-    mp.flags = (int32_t*)(ws + pl.off_flags);
-    mp.stats = d_stats;
-    mp.fb_S = pl.fb_S; mp.fb_F = pl.fb_F;
-    mp.fb_d = (double*)(ws + pl.off_fb_d);
-    mp.fb_i = (int32_t*)(ws + pl.off_fb_i);
-    mp.fb_slotctr = (int32_t*)(ws + pl.off_fb_ctr);
-    if (N == 0) AC_HIP_CHECK(hipMemsetAsync(ws + pl.off_fb_ctr, 0, 256, stream));      // (otherwise the sweep's workgroup 0 clears it)
 
     if (N == 0) {
         // empty shard: everything is padding; reuse the merge kernel with all-padding partials
+        AC_HIP_CHECK(hipMemsetAsync(ws + pl.ex.off_fb_ctr, 0, 256, stream));      // (otherwise the sweep's workgroup 0 clears it)
         AC_HIP_CHECK(hipMemsetAsync(ws + pl.off_part_i, 0xff, (size_t)pl.nqt * pl.TQ * pl.G * pl.kp * 4, stream));
         AC_HIP_CHECK(hipMemsetAsync(ws + pl.off_maxnorm, 0, (size_t)pl.G * pl.nqt * 4, stream));
     } else {
-        SweepParams sp;
+        SweepParams sp{};
         sp.P = d_P; sp.N = N; sp.ldP = ldP; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.Dp = pl.Dp;
         sp.ng = pl.ng; sp.nq = nq; sp.kp = pl.kp; sp.cap = pl.cap; sp.G = pl.G; sp.nqt = pl.nqt;
         sp.ntiles = pl.ntiles;
@@ -1780,7 +1066,7 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
         sp.part_i = (int32_t*)(ws + pl.off_part_i);
         sp.part_maxnorm = (float*)(ws + pl.off_maxnorm);
         sp.zeros = zeros_device();                    // a zero-initialised __device__ array: no memset launch per call
-        sp.clear_ctr = (int32_t*)(ws + pl.off_fb_ctr);
+        sp.clear_ctr = (int32_t*)(ws + pl.ex.off_fb_ctr);
         sp.clear_stats = d_stats;
         const int nblk = pl.G * pl.nqt;
         if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
@@ -1798,22 +1084,7 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
         AC_LAUNCH_CHECK();
         if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
     }
-    void (*merge_fn)(MergeParams) = ip ? knn_merge_rerank_ip : knn_merge_rerank;
-    (void)hipFuncSetAttribute((const void*)merge_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.merge_lds);
-    hipLaunchKernelGGL(merge_fn, dim3(nq), dim3(kMergeThreads), pl.merge_lds, stream, mp);
-    AC_LAUNCH_CHECK();
-    if (N > 0) {
-        void (*fb_fn)(MergeParams, int) = ip ? knn_exact_fallback_ip : knn_exact_fallback;
-        (void)hipFuncSetAttribute((const void*)fb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.fb_lds);
-        hipLaunchKernelGGL(fb_fn, dim3(pl.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups), dim3(kFbThreads), pl.fb_lds, stream, mp, nq);
-        AC_LAUNCH_CHECK();
-        const int np2 = next_pow2(pl.fb_S * k > 2 ? pl.fb_S * k : 2);
-        void (*fbm_fn)(MergeParams, int, int) = ip ? knn_exact_fb_merge_ip : knn_exact_fb_merge;
-        (void)hipFuncSetAttribute((const void*)fbm_fn, hipFuncAttributeMaxDynamicSharedMemorySize, np2 * 12);
-        hipLaunchKernelGGL(fbm_fn, dim3(nq < kFbMergeGroups ? nq : kFbMergeGroups), dim3(256), (size_t)np2 * 12, stream, mp, np2, nq);
-        AC_LAUNCH_CHECK();
-    }
-    return AC_OK;
+    return ac::knn_exact_tail(ip, mp, pl.ex, nq, pl.ex.merge_lds, stream);
 }
 
 extern "C" int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
@@ -1844,7 +1115,7 @@ extern "C" int ac_knn_ip_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
 
 // ---------------------------------------------------------------------------------------------------------
 // batched search with a prepared store (fp16 plane + row norms): sample -> thresholds -> GEMM-form filter ->
-// the same merge / fp64 re-rank / certificate / exact fallback as above (knn_batch.hip explains the scheme)
+// the same merge / fp64 re-rank / certificate / exact fallback (knn_exact.hip; knn_batch.hip explains the scheme)
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
@@ -1857,10 +1128,8 @@ struct BatchPlan {
     int kp, cap, Dp;
     int64_t stride, stride_a, S, q_rows;
     int segs;
-    size_t off_sD32, off_sD64, off_sI, off_thr, off_qfac, off_cnt, off_ctl, off_wgmin, off_qp, off_cd, off_ci, off_flags, off_fb_d, off_fb_i,
-        off_fb_ctr, off_sub, sub_bytes, total;
-    int fb_S, fb_F;
-    size_t merge_lds, fb_lds;
+    size_t off_sD32, off_sD64, off_sI, off_thr, off_qfac, off_cnt, off_ctl, off_wgmin, off_qp, off_cd, off_ci, off_sub, sub_bytes, total;
+    ExactPlan ex;
 };
 
 int make_batch_plan(int64_t N, int D, int nq, int k, BatchPlan* bp) {
@@ -1914,8 +1183,7 @@ int make_batch_plan(int64_t N, int D, int nq, int k, BatchPlan* bp) {
     bp->q_rows = ((int64_t)nq + 255) / 256 * 256;
     const size_t sub = 256;                                // (the exact sample search of round 2 needed a workspace of its own)
     bp->sub_bytes = sub;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += ac::align_up(n, 256); return o; };
+    ac::WsTake take;
     bp->off_sD32 = take((size_t)nq * bp->kp * 4);
     bp->off_sD64 = take((size_t)nq * bp->kp * 8);
     bp->off_sI = take((size_t)nq * bp->kp * 8);
@@ -1927,19 +1195,11 @@ int make_batch_plan(int64_t N, int D, int nq, int k, BatchPlan* bp) {
     bp->off_qp = take(ac::knn_planes_bytes(nq, D));
     bp->off_cd = take((size_t)bp->q_rows * cap * 4);
     bp->off_ci = take((size_t)bp->q_rows * cap * 4);
-    bp->off_flags = take((size_t)nq * 4);
-    bp->fb_S = 4096 / next_pow2(k);
-    if (bp->fb_S > 64) bp->fb_S = 64;
-    if (bp->fb_S < 1) bp->fb_S = 1;
-    bp->fb_F = nq < 64 ? nq : 64;
-    bp->off_fb_d = take((size_t)bp->fb_F * bp->fb_S * k * 8);
-    bp->off_fb_i = take((size_t)bp->fb_F * bp->fb_S * k * 4);
-    bp->off_fb_ctr = take(256);
+    bp->ex.off_flags = take((size_t)nq * 4);
+    // (the merge's LDS in its segmented form: keys + ids; one segment needs cap * 4 less)
+    ac::knn_exact_plan(&bp->ex, take, k, bp->kp, bp->Dp, 2 * ac::align_up((size_t)cap * 4, 16), nq < 64 ? nq : 64);
     bp->off_sub = take(sub);
-    bp->total = off;
-    // (the static LDS of the merge kernel -- segment offsets, scan totals -- is ~1.1 KB)
-    bp->merge_lds = 2 * ac::align_up((size_t)cap * 4, 16) + ac::align_up((size_t)bp->Dp * 4, 16) + (size_t)bp->kp * 16 + 256 * 4 + 64;   // (segmented form; one segment needs cap * 4 less)
-    bp->fb_lds = (size_t)kFbCap * 12 + ac::align_up((size_t)bp->Dp, 4) * 4 + 64;
+    bp->total = take.off;
     return AC_OK;
 }
 
@@ -1950,9 +1210,9 @@ constexpr int kPlaneMaxQueries = 64;
 struct PlanePlan {
     int TQ, nqt, kp, cap, G, Dp, Kp;
     int64_t ntiles, q_rows;
-    size_t sweep_lds, merge_lds, fb_lds;
-    size_t off_part_d, off_part_i, off_flags, off_qp, off_qfac, off_thr, off_fb_d, off_fb_i, off_fb_ctr, total;
-    int fb_S, fb_F;
+    size_t sweep_lds;
+    size_t off_part_d, off_part_i, off_qp, off_qfac, off_thr, total;
+    ExactPlan ex;
 };
 
 // false: the shape does not fit (LDS) or the form is switched off -- the caller uses the GEMM-form path instead
@@ -1979,28 +1239,19 @@ bool make_plane_plan(int64_t N, int D, int nq, int k, PlanePlan* pp) {
     int64_t G = ac::dev_info().cus;                       // one 8-wave workgroup per CU: exactly one residency round
     if (G > pp->ntiles) G = pp->ntiles;
     if (G > kMergeMaxCand / pp->kp) G = kMergeMaxCand / pp->kp;
-    if (const char* e = getenv("AC_KNN_G")) { int64_t v = atoll(e); if (v >= 1 && v <= G) G = v; }   // tuning experiments
+    if (const int64_t v = env_knn_g()) { if (v <= G) G = v; }
     pp->G = (int)G;
     pp->q_rows = 256;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += ac::align_up(n, 256); return o; };
+    ac::WsTake take;
     const size_t ncand = (size_t)pp->nqt * pp->TQ * pp->G * pp->kp;
     pp->off_part_d = take(ncand * 4);
     pp->off_part_i = take(ncand * 4);
-    pp->off_flags = take((size_t)nq * 4);
+    pp->ex.off_flags = take((size_t)nq * 4);
     pp->off_qp = take(ac::knn_planes_bytes(nq, D));
     pp->off_qfac = take((size_t)pp->q_rows * 4);
     pp->off_thr = take((size_t)pp->q_rows * 4);
-    pp->fb_S = 4096 / next_pow2(k);
-    if (pp->fb_S > 64) pp->fb_S = 64;
-    if (pp->fb_S < 1) pp->fb_S = 1;
-    pp->fb_F = nq;
-    pp->off_fb_d = take((size_t)pp->fb_F * pp->fb_S * k * 8);
-    pp->off_fb_i = take((size_t)pp->fb_F * pp->fb_S * k * 4);
-    pp->off_fb_ctr = take(256);
-    pp->total = off;
-    pp->merge_lds = ac::align_up((size_t)pp->G * pp->kp * 4, 16) + ac::align_up((size_t)pp->Dp * 4, 16) + (size_t)pp->kp * 16 + 256 * 4 + 64;
-    pp->fb_lds = (size_t)kFbCap * 12 + ac::align_up((size_t)pp->Dp, 4) * 4 + 64;
+    ac::knn_exact_plan(&pp->ex, take, k, pp->kp, pp->Dp, ac::align_up((size_t)pp->G * pp->kp * 4, 16), nq);
+    pp->total = take.off;
     return true;
 }
 
@@ -2016,7 +1267,7 @@ int plane_search(const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, 
                                      (float*)(ws + pp.off_thr), (float*)(ws + pp.off_qfac), stream);
     if (rc != AC_OK) return rc;
     // 2. one pass over the plane per query tile
-    PlaneSweepParams sp;
+    PlaneSweepParams sp{};
     sp.Pp = d_planes; sp.pnorm = d_norms; sp.Qp = (const uint16_t*)(ws + pp.off_qp); sp.q_rows = pp.q_rows;
     sp.qfac = (const float*)(ws + pp.off_qfac); sp.N = N; sp.ntiles = pp.ntiles; sp.Kp = pp.Kp;
     sp.kp = pp.kp; sp.cap = pp.cap; sp.G = pp.G;
@@ -2024,7 +1275,7 @@ int plane_search(const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, 
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
     for (int qt = 0; qt < pp.nqt; ++qt) {
         sp.q0 = qt * pp.TQ; sp.nq = nq - sp.q0 < pp.TQ ? nq - sp.q0 : pp.TQ;
-        sp.clear_ctr = qt == 0 ? (int32_t*)(ws + pp.off_fb_ctr) : nullptr;
+        sp.clear_ctr = qt == 0 ? (int32_t*)(ws + pp.ex.off_fb_ctr) : nullptr;
         sp.clear_stats = qt == 0 ? d_stats : nullptr;
         if (pp.TQ == 64) {
             AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_plane_sweep<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
@@ -2037,29 +1288,11 @@ int plane_search(const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, 
     }
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
     // 3. merge of the G per-workgroup lists + exact fp64 re-rank + certificate with the fp16 bound, then the exact fallback
-    MergeParams mp;
-    mp.P = d_P; mp.N = N; mp.ldP = ldP; mp.Q = d_Q; mp.ldQ = ldQ; mp.D = D; mp.Dp = pp.Dp;
-    mp.k = k; mp.kp = pp.kp; mp.G = pp.G; mp.nblk = 1; mp.gamma = gamma;
-    mp.cand_cnt = nullptr; mp.cand_cap = 0; mp.cand_segs = 1; mp.run_stride = 0; mp.cand_cnt_clear = nullptr; mp.thr_out = nullptr;
-    mp.row_offset = row_offset;
+    MergeParams mp = ac::knn_merge_params(d_P, N, ldP, d_Q, ldQ, D, pp.Dp, k, pp.kp, row_offset, d_outD, d_outD64, d_outI, d_stats, ws, pp.ex);
+    mp.G = pp.G; mp.nblk = 1; mp.gamma = gamma;
     mp.part_d = (const float*)(ws + pp.off_part_d); mp.part_i = (const int32_t*)(ws + pp.off_part_i);
     mp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    mp.outD = d_outD; mp.outD64 = d_outD64; mp.outI = d_outI;
-    mp.flags = (int32_t*)(ws + pp.off_flags);
-    mp.stats = d_stats;
-    mp.fb_S = pp.fb_S; mp.fb_F = pp.fb_F;
-    mp.fb_d = (double*)(ws + pp.off_fb_d); mp.fb_i = (int32_t*)(ws + pp.off_fb_i); mp.fb_slotctr = (int32_t*)(ws + pp.off_fb_ctr);
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_merge_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.merge_lds));
-    hipLaunchKernelGGL(knn_merge_rerank, dim3(nq), dim3(kMergeThreads), pp.merge_lds, stream, mp);
-    AC_LAUNCH_CHECK();
-    (void)hipFuncSetAttribute((const void*)knn_exact_fallback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.fb_lds);
-    hipLaunchKernelGGL(knn_exact_fallback, dim3(pp.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups), dim3(kFbThreads), pp.fb_lds, stream, mp, nq);
-    AC_LAUNCH_CHECK();
-    const int np2 = next_pow2(pp.fb_S * k > 2 ? pp.fb_S * k : 2);
-    (void)hipFuncSetAttribute((const void*)knn_exact_fb_merge, hipFuncAttributeMaxDynamicSharedMemorySize, np2 * 12);
-    hipLaunchKernelGGL(knn_exact_fb_merge, dim3(nq < kFbMergeGroups ? nq : kFbMergeGroups), dim3(256), (size_t)np2 * 12, stream, mp, np2, nq);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
+    return ac::knn_exact_tail(false, mp, pp.ex, nq, pp.ex.merge_lds, stream);
 }
 
 }  // namespace
@@ -2145,21 +1378,19 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
     if (rc != AC_OK) return rc;
     // 2. threshold stages: sweep a strided sample, re-rank its k' best exactly (knn_merge_rerank in candidate mode, asked for
     //    k' results; its certificate is irrelevant here -- ANY k' rows bound the k'-th smallest distance from above)
-    MergeParams sp;
-    sp.P = d_P; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.Dp = bp.Dp;
-    sp.k = bp.kp; sp.kp = bp.kp; sp.G = 1; sp.nblk = 1; sp.gamma = gamma;
-    sp.cand_cnt = (const int32_t*)(ws + bp.off_cnt); sp.cand_cap = bp.cap; sp.cand_segs = bp.segs; sp.row_offset = 0;
+    //    (N = the stage's sample rows and run_stride are set per stage; no fallback slots: fb_F = 0, a counter word of its own)
+    MergeParams sp = ac::knn_merge_params(d_P, 0, ldP, d_Q, ldQ, D, bp.Dp, bp.kp, bp.kp, 0, (float*)(ws + bp.off_sD32), (double*)(ws + bp.off_sD64),
+                                          (int64_t*)(ws + bp.off_sI), nullptr, ws, bp.ex);
+    sp.G = 1; sp.nblk = 1; sp.gamma = gamma;
+    sp.cand_cnt = (const int32_t*)(ws + bp.off_cnt); sp.cand_cap = bp.cap;
     // a threshold stage's merge writes the new threshold itself and zeroes the counters it has read (the next sweep appends
     // into them): round 3 spent a knn_thr_kernel launch and a memset launch per stage on that
     sp.cand_cnt_clear = (int32_t*)(ws + bp.off_cnt); sp.thr_out = (float*)(ws + bp.off_thr);
     sp.part_d = (const float*)(ws + bp.off_cd); sp.part_i = (const int32_t*)(ws + bp.off_ci);
     sp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    sp.outD = (float*)(ws + bp.off_sD32); sp.outD64 = (double*)(ws + bp.off_sD64); sp.outI = (int64_t*)(ws + bp.off_sI);
-    sp.flags = (int32_t*)(ws + bp.off_flags); sp.stats = nullptr;
-    sp.fb_S = bp.fb_S; sp.fb_F = 0; sp.fb_d = nullptr; sp.fb_i = nullptr; sp.fb_slotctr = (int32_t*)(ws + bp.off_fb_ctr) + 8;
+    sp.fb_F = 0; sp.fb_d = nullptr; sp.fb_i = nullptr; sp.fb_slotctr += 8;
     static const bool thr_exact = [] { const char* e = getenv("AC_KNN_THR_EXACT"); return e && atoi(e) != 0; }();     // (A/B: the re-ranked form)
     sp.thr_only = thr_exact ? 0 : 1;
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_merge_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.merge_lds));
     static const bool dbg = getenv("AC_KNN_BATCH_DEBUG") != nullptr;
     const int64_t stage_stride[2] = {bp.stride_a, bp.stride};
     // the main sweep takes its thresholds from its own first tile round where it can (knn_batch.hip two_phase): no sample stages
@@ -2168,15 +1399,15 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
     for (int st = 0; st < nstages; ++st) {
         const int64_t sst = stage_stride[st];
         const int segs = batch_segs(bp, ac::knn_sample_rows(N, sst), nq);
-        const size_t mlds = bp.merge_lds - (segs > 1 ? 0 : ac::align_up((size_t)bp.cap * 4, 16));
+        const size_t mlds = bp.ex.merge_lds - (segs > 1 ? 0 : ac::align_up((size_t)bp.cap * 4, 16));
         sp.cand_segs = segs;
         rc = ac::knn_batch_launch(d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
                                   (const float*)(ws + bp.off_qfac), (float*)(ws + bp.off_cd), (int32_t*)(ws + bp.off_ci),
                                   (int32_t*)(ws + bp.off_cnt), bp.cap, segs, sst, st == 0 ? 1 : 0, stream);
         if (rc != AC_OK) return rc;
-        sp.N = ac::knn_sample_rows(N, sst); sp.ldP = ldP; sp.run_stride = sst > 1 ? 8 * sst : 0;   // sample row i = store row (i >> 3) * 8 sst + (i & 7)
-        hipLaunchKernelGGL(knn_merge_rerank, dim3(nq), dim3(kMergeThreads), mlds, stream, sp);
-        AC_LAUNCH_CHECK();
+        sp.N = ac::knn_sample_rows(N, sst); sp.run_stride = sst > 1 ? 8 * sst : 0;   // sample row i = store row (i >> 3) * 8 sst + (i & 7)
+        rc = ac::knn_merge_launch(false, sp, nq, st == 0 ? bp.ex.merge_lds : 0, mlds, stream);      // (the opt-in covers the later stages)
+        if (rc != AC_OK) return rc;
         if (dbg) {
             AC_HIP_CHECK(hipStreamSynchronize(stream));
             int32_t cnt[4]; float thr[4]; double tau[4];
@@ -2189,103 +1420,20 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
         }
     }
     const int msegs = batch_segs(bp, N, nq);
-    const size_t mlds = bp.merge_lds - (msegs > 1 ? 0 : ac::align_up((size_t)bp.cap * 4, 16));
+    const size_t mlds = bp.ex.merge_lds - (msegs > 1 ? 0 : ac::align_up((size_t)bp.cap * 4, 16));
     // 3. the GEMM-form sweep: candidates (row, v) with v below the query's threshold (its workgroup 0 also zeroes the caller's
     //    d_stats and the fallback's slot counter, which the merge after it increments)
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
     rc = ac::knn_batch_launch(d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
                               (const float*)(ws + bp.off_qfac), (float*)(ws + bp.off_cd), (int32_t*)(ws + bp.off_ci), (int32_t*)(ws + bp.off_cnt), bp.cap, msegs, 1, 0, stream,
-                              (int32_t*)(ws + bp.off_fb_ctr), d_stats, two_phase ? bp.kp : 0, (unsigned*)(ws + bp.off_wgmin), ws + bp.off_ctl);
+                              (int32_t*)(ws + bp.ex.off_fb_ctr), d_stats, two_phase ? bp.kp : 0, (unsigned*)(ws + bp.off_wgmin), ws + bp.off_ctl);
     if (rc != AC_OK) return rc;
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
     // 4. merge + exact re-rank + certificate, then the exact fallback for uncertified queries
-    MergeParams mp;
-    mp.P = d_P; mp.N = N; mp.ldP = ldP; mp.Q = d_Q; mp.ldQ = ldQ; mp.D = D; mp.Dp = bp.Dp;
-    mp.k = k; mp.kp = bp.kp; mp.G = 1; mp.nblk = 1; mp.gamma = gamma;
-    mp.cand_cnt = (const int32_t*)(ws + bp.off_cnt); mp.cand_cap = bp.cap; mp.cand_segs = msegs; mp.run_stride = 0;
-    mp.cand_cnt_clear = nullptr; mp.thr_out = nullptr;
-    mp.row_offset = row_offset;
+    MergeParams mp = ac::knn_merge_params(d_P, N, ldP, d_Q, ldQ, D, bp.Dp, k, bp.kp, row_offset, d_outD, d_outD64, d_outI, d_stats, ws, bp.ex);
+    mp.G = 1; mp.nblk = 1; mp.gamma = gamma;
+    mp.cand_cnt = (const int32_t*)(ws + bp.off_cnt); mp.cand_cap = bp.cap; mp.cand_segs = msegs;
     mp.part_d = (const float*)(ws + bp.off_cd); mp.part_i = (const int32_t*)(ws + bp.off_ci);
     mp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    mp.outD = d_outD; mp.outD64 = d_outD64; mp.outI = d_outI;
-    mp.flags = (int32_t*)(ws + bp.off_flags);
-    mp.stats = d_stats;
-    mp.fb_S = bp.fb_S; mp.fb_F = bp.fb_F;
-    mp.fb_d = (double*)(ws + bp.off_fb_d); mp.fb_i = (int32_t*)(ws + bp.off_fb_i); mp.fb_slotctr = (int32_t*)(ws + bp.off_fb_ctr);
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_merge_rerank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.merge_lds));
-    hipLaunchKernelGGL(knn_merge_rerank, dim3(nq), dim3(kMergeThreads), mlds, stream, mp);
-    AC_LAUNCH_CHECK();
-    (void)hipFuncSetAttribute((const void*)knn_exact_fallback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.fb_lds);
-    hipLaunchKernelGGL(knn_exact_fallback, dim3(bp.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups), dim3(kFbThreads), bp.fb_lds, stream, mp, nq);
-    AC_LAUNCH_CHECK();
-    const int np2 = next_pow2(bp.fb_S * k > 2 ? bp.fb_S * k : 2);
-    (void)hipFuncSetAttribute((const void*)knn_exact_fb_merge, hipFuncAttributeMaxDynamicSharedMemorySize, np2 * 12);
-    hipLaunchKernelGGL(knn_exact_fb_merge, dim3(nq < kFbMergeGroups ? nq : kFbMergeGroups), dim3(256), (size_t)np2 * 12, stream, mp, np2, nq);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-extern "C" int ac_topk_merge(const float* d_D_in, const int64_t* d_I_in, int shards, int nq, int k,
-                             float* d_outD, int64_t* d_outI, ac_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AC_REQUIRE(shards >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "topk_merge: bad shape");
-    AC_REQUIRE(d_D_in && d_I_in && d_outD && d_outI, AC_EINVAL, "topk_merge: null pointer");
-    if (nq == 0) return AC_OK;
-    const size_t lds = (size_t)shards * k * 12;
-    AC_REQUIRE(lds <= 96 * 1024, AC_EUNSUPPORTED, "topk_merge: shards*k=%d too large", shards * k);
-    (void)hipFuncSetAttribute((const void*)topk_merge_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(topk_merge_kernel<float>, dim3(nq), dim3(256), lds, stream, d_D_in, d_I_in, shards, nq, k,
-                       d_outD, d_outI);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-extern "C" int ac_topk_merge_f64(const double* d_D_in, const int64_t* d_I_in, int shards, int nq, int k,
-                                 float* d_outD, int64_t* d_outI, ac_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AC_REQUIRE(shards >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "topk_merge_f64: bad shape");
-    AC_REQUIRE(d_D_in && d_I_in && d_outD && d_outI, AC_EINVAL, "topk_merge_f64: null pointer");
-    if (nq == 0) return AC_OK;
-    const size_t lds = (size_t)shards * k * 16;
-    AC_REQUIRE(lds <= 128 * 1024, AC_EUNSUPPORTED, "topk_merge_f64: shards*k=%d too large", shards * k);
-    (void)hipFuncSetAttribute((const void*)topk_merge_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(topk_merge_kernel<double>, dim3(nq), dim3(256), lds, stream, d_D_in, d_I_in, shards, nq, k,
-                       d_outD, d_outI);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-extern "C" int ac_topk_merge_ip_f64(const double* d_D_in, const int64_t* d_I_in, int shards, int nq, int k,
-                                    float* d_outD, int64_t* d_outI, ac_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AC_REQUIRE(shards >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "topk_merge_ip_f64: bad shape");
-    AC_REQUIRE(d_D_in && d_I_in && d_outD && d_outI, AC_EINVAL, "topk_merge_ip_f64: null pointer");
-    if (nq == 0) return AC_OK;
-    const size_t lds = (size_t)shards * k * 16;
-    AC_REQUIRE(lds <= 128 * 1024, AC_EUNSUPPORTED, "topk_merge_ip_f64: shards*k=%d too large", shards * k);
-    (void)hipFuncSetAttribute((const void*)topk_merge_kernel<double, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((topk_merge_kernel<double, true>), dim3(nq), dim3(256), lds, stream, d_D_in, d_I_in, shards, nq, k,
-                       d_outD, d_outI);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-extern "C" int ac_rows_to_class(const int64_t* d_I, int64_t n, const int32_t* d_row_class, int64_t nrows,
-                                const int64_t* d_class_lut, int nlut, int64_t* d_out, ac_stream_t stream_) {
-    AC_REQUIRE(d_I && d_out && n >= 0 && nrows >= 0, AC_EINVAL, "rows_to_class: bad arguments");
-    if (n == 0) return AC_OK;
-    hipLaunchKernelGGL(rows_to_class_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
-                       d_I, n, d_row_class, nrows, d_class_lut, nlut, d_out);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-extern "C" int ac_proto_scores(const float* d_D, const int64_t* d_I, int nq, int k, float* d_out,
-                               ac_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    AC_REQUIRE(nq >= 0 && k >= 1 && d_D && d_I && d_out, AC_EINVAL, "proto_scores: bad arguments");
-    if (nq == 0) return AC_OK;
-    hipLaunchKernelGGL(proto_scores_kernel, dim3(nq), dim3(64), 0, stream, d_D, d_I, nq, k, d_out);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
+    return ac::knn_exact_tail(false, mp, bp.ex, nq, mlds, stream);
 }

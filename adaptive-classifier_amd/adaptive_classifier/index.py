@@ -9,6 +9,8 @@ leading dimension (growth by doubling, so `add` is amortised O(1) like faiss's v
 search() is one call into the C ABI (`ac_knn_l2_topk`): exact squared L2, ascending, ties to
 the lower id.  HipFlatIPIndex is the same store searched by inner product (`ac_knn_ip_topk`,
 faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.
+Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `ac_knn_l2_topk_batch` /
+`ac_knn_ip_topk_batch`.
 """
 import ctypes
 
@@ -76,8 +78,8 @@ def prepare_store(P, N, D, capacity=None):
 
 
 def batch_applies(N, nq, k, auto=False):
-    """Library limits of ac_knn_l2_topk_batch (any number of queries: below 64 it runs the fp16-plane sweep); auto=True adds the
-    size heuristic the index uses to pick a path."""
+    """Library limits of ac_knn_l2_topk_batch / ac_knn_ip_topk_batch (any number of queries: below 64 they run the fp16-plane
+    sweep); auto=True adds the size heuristic the index uses to pick a path."""
     ok = nq >= 1 and N >= BATCH_MIN_ROWS and k <= BATCH_MAX_K
     if not ok or not auto:
         return ok
@@ -94,7 +96,7 @@ def knn_l2_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=Non
               on) -- same exact result, half the bytes / several times the throughput.
     """
     if prepared is not None and batch_applies(N, Q.shape[0], k):
-        return _knn_l2_topk_batch(P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out)
+        return _knn_topk_batch("ac_knn_l2_topk_batch", P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out)
     return _knn_topk_x("ac_knn_l2_topk_x", P, N, D, Q, k, row_offset, out, workspace, stats, exact_out)
 
 
@@ -122,21 +124,26 @@ def _knn_topk_x(entry, P, N, D, Q, k, row_offset, out, workspace, stats, exact_o
     return outD, outI
 
 
-def knn_ip_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=None, exact_out=None):
+def knn_ip_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=None, exact_out=None, prepared=None):
     """Exact inner-product top-k (`ac_knn_ip_topk_x`, faiss.IndexFlatIP.search): the k rows with the largest p.q per query,
-    descending, ties to the lower id; rows need not be normalised.  Arguments and workspace as `knn_l2_topk` (the fp32 sweeps
-    serve every shape: there is no prepared form).  Returns (values fp32 [nq,k], ids int64 [nq,k]); k > N pads with (-FLT_MAX, -1)."""
+    descending, ties to the lower id; rows need not be normalised.  Arguments and workspace as `knn_l2_topk`, `prepared`
+    included: the SAME (planes, norms) of `prepare_store` serve both metrics (`ac_knn_ip_topk_batch`, same exact result).
+    Returns (values fp32 [nq,k], ids int64 [nq,k]); k > N pads with (-FLT_MAX, -1)."""
+    if prepared is not None and batch_applies(N, Q.shape[0], k):
+        return _knn_topk_batch("ac_knn_ip_topk_batch", P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out)
     return _knn_topk_x("ac_knn_ip_topk_x", P, N, D, Q, k, row_offset, out, workspace, stats, exact_out)
 
 
-def knn_ip_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None):
+def knn_ip_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, prepared=None):
     """(exact fp64 inner products [nq,k] descending, ids [nq,k]): what a row shard contributes to a sharded IP search."""
     ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
-    _, I = knn_ip_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex)
+    _, I = knn_ip_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex, prepared=prepared)
     return ex, I
 
 
-def _knn_l2_topk_batch(P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out):
+def _knn_topk_batch(entry, P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out):
+    """the prepared-store search of either metric: `entry` = ac_knn_l2_topk_batch or ac_knn_ip_topk_batch (same arguments; the
+    workspace planners return the same value)"""
     nv.require_gpu()
     planes, norms = prepared
     nq, dev = Q.shape[0], Q.device
@@ -146,15 +153,15 @@ def _knn_l2_topk_batch(P, N, D, Q, k, prepared, row_offset, out, workspace, stat
     else:
         outD, outI = out
     b = ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_l2_topk_batch_workspace(N, D, nq, k, ctypes.byref(b)), "ac_knn_l2_topk_batch_workspace")
+    nv.check(getattr(nv.lib(), entry + "_workspace")(N, D, nq, k, ctypes.byref(b)), entry + "_workspace")
     if workspace is None or workspace.numel() < b.value:
         workspace = torch.empty(b.value, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        rc = nv.lib().ac_knn_l2_topk_batch(
+        rc = getattr(nv.lib(), entry)(
             nv.ptr(P), N, P.stride(0), D, nv.ptr(planes), nv.ptr(norms), nv.ptr(Q), nq, Q.stride(0), k, row_offset,
             nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(), nv.ptr(stats),
             nv.stream_ptr(dev))
-    nv.check(rc, "ac_knn_l2_topk_batch")
+    nv.check(rc, entry)
     return outD, outI
 
 
@@ -173,7 +180,14 @@ def knn_l2_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, p
 
 class _HipFlatIndex:
     """The flat store both metrics share: resident rows, lazy upload, compaction, in-place updates.  `metric` ("l2" / "ip")
-    picks the search entry point; only the L2 index ever prepares an fp16 plane.
+    picks the search entry points; both metrics search the same kind of prepared store (one fp16 plane + norms).
+
+    When the plane is prepared (two passes over the rows, 2 B per element): a many-query search (>= BATCH_MIN_QUERIES queries
+    and N * nq >= BATCH_MIN_PAIRS) prepares it at once -- it pays within the call.  The L2 index also prepares it for a small
+    batch on >= PLANE_MIN_ROWS rows once the store has served one search since it was last rebuilt.  The IP index NEVER
+    prepares from small searches: an index that only ever answers few-query searches keeps to the fp32 sweeps and holds no
+    plane.  Once a plane exists -- for either metric -- small batches on >= PLANE_MIN_ROWS rows use the fp16-plane sweep; the
+    plane follows `add` / `update_rows` incrementally and is dropped by `remove_ids` / `reset`.
 
     Host-side bookkeeping (add / ntotal / remove_ids) works without a GPU: added rows are queued on
     the host and uploaded in one copy when the device matrix is first needed.  search() has no CPU
@@ -346,17 +360,13 @@ class _HipFlatIndex:
             q = q.unsqueeze(0)
         if q.stride(-1) != 1:
             q = q.contiguous()
-        if self.metric == "ip":                 # the fp32 sweeps for every shape; no plane is ever prepared
-            need = knn_workspace_bytes(self._n, self.d, q.shape[0], k)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-            return knn_ip_topk(self._store, self._n, self.d, q, k, workspace=self._ws, stats=self._stats)
         batch = batch_applies(self._n, q.shape[0], k, auto=True)
         if batch and self._prepared is None:
             # preparing costs two passes over the rows (~0.14 s at 10M x 768): at once for a many-query search (it pays within
             # the call); for a small batch only when the store has already served a search since it was last rebuilt / compacted
-            # (appends and in-place updates do not count: once prepared, the plane follows them incrementally)
-            if q.shape[0] >= BATCH_MIN_QUERIES or self._searches_since_change >= 1:
+            # (appends and in-place updates do not count: once prepared, the plane follows them incrementally); the IP index
+            # never prepares from small searches (class docstring)
+            if q.shape[0] >= BATCH_MIN_QUERIES or (self.metric == "l2" and self._searches_since_change >= 1):
                 # (sized for the store's CAPACITY: the first append after the preparation then updates the plane in place
                 #  instead of allocating capacity-sized buffers and copying the whole old plane beside them)
                 self._prepared = prepare_store(self._store, self._n, self.d, capacity=self._store.shape[0])
@@ -366,8 +376,9 @@ class _HipFlatIndex:
         need = knn_batch_workspace_bytes(self._n, self.d, q.shape[0], k) if batch else knn_workspace_bytes(self._n, self.d, q.shape[0], k)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return knn_l2_topk(self._store, self._n, self.d, q, k, workspace=self._ws, stats=self._stats,
-                           prepared=self._prepared if batch else None)
+        search = knn_ip_topk if self.metric == "ip" else knn_l2_topk
+        return search(self._store, self._n, self.d, q, k, workspace=self._ws, stats=self._stats,
+                      prepared=self._prepared if batch else None)
 
     def search(self, x, k):
         """faiss signature: numpy in, (float32 [nq,k], int64 [nq,k]) numpy out."""
@@ -388,7 +399,8 @@ class HipFlatL2Index(_HipFlatIndex):
 
 class HipFlatIPIndex(_HipFlatIndex):
     """Drop-in for faiss.IndexFlatIP: exact inner product, descending, ties to the lower id (`ac_knn_ip_topk`).  Rows need not
-    be normalised; for L2-normalised rows this is the cosine search.  Same protocol and storage as HipFlatL2Index."""
+    be normalised; for L2-normalised rows this is the cosine search.  Same protocol and storage as HipFlatL2Index; its fp16
+    plane is prepared by many-query searches only (`_HipFlatIndex`)."""
     metric = "ip"
 
 

@@ -51,7 +51,8 @@ class ShardedSearch:
     def __init__(self, local_rows, n_local, dim, row_offset, group=None, local_search=None, merge=None,
                  force_collectives=False, equal_blocks=False, block_rows=None, metric="l2"):
         """metric: "l2" (default) or "ip" -- which search and merge are wired when none is injected: squared L2 ascending
-        (`knn_l2_topk_exact` + `topk_merge`) or inner product descending (`knn_ip_topk_exact` + `topk_merge_ip`); the exchange
+        (`knn_l2_topk_exact` + `topk_merge`) or inner product descending (`knn_ip_topk_exact` + `topk_merge_ip`); either
+        search prepares the local shard's fp16 plane on first use where `batch_applies(..., auto=True)` holds; the exchange
         itself (exact fp64 values and ids on the wire) is the same.
         force_collectives: run the collectives even on a one-rank group (tests: executes the RCCL calls on one GPU).
         equal_blocks: the caller guarantees that every rank passes the same number of queries to every search_block /
@@ -73,7 +74,7 @@ class ShardedSearch:
             raise ValueError("block_rows must be >= 1")
         self._bufs = {}                # fixed-batch path: (name, shape, dtype) -> tensor, allocated once
         self.stats = {"size_exchanges": 0, "buffer_allocations": 0, "prefetched_gathers": 0}
-        self._prepared = None          # bf16 planes + norms of the local shard (batched searches), built on first use
+        self._prepared = None          # fp16 plane + norms of the local shard (batched searches, either metric), built on first use
         if local_search is None or merge is None:
             from . import index as ix
 
@@ -86,6 +87,10 @@ class ShardedSearch:
                 return ix.knn_l2_topk_exact(P, n, D, Q, k, row_offset=off)
 
             def _hip_search_ip(P, n, D, Q, k, off):
+                if ix.batch_applies(n, Q.shape[0], k, auto=True):            # the same prepared store, searched by inner product
+                    if self._prepared is None:
+                        self._prepared = ix.prepare_store(P, n, D)
+                    return ix.knn_ip_topk_exact(P, n, D, Q, k, row_offset=off, prepared=self._prepared)
                 return ix.knn_ip_topk_exact(P, n, D, Q, k, row_offset=off)
 
             local_search = local_search or (_hip_search_ip if metric == "ip" else _hip_search)

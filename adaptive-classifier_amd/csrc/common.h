@@ -279,7 +279,7 @@ int knn_prepare_queries(const double* sampleD, int kp, const float* Q, int64_t l
                         double gamma, uint16_t* qplane, float* thr, float* qfac, hipStream_t stream, int32_t* zero_ints = nullptr,
                         int64_t zero_count = 0);             // zero_ints: device ints the same launch clears (the candidate counters)
 int64_t knn_sample_rows(int64_t N, int64_t stride);
-int knn_batch_launch(const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
+int knn_batch_launch(bool ip, const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
                      const float* qfac, float* cand_d, int32_t* cand_i, int32_t* cand_cnt, int cap, int segs, int64_t row_stride,
                      int best_only, hipStream_t stream, int32_t* clear_ctr = nullptr, int32_t* clear_stats = nullptr,
                      int two_phase_kp = 0, unsigned* wgmin = nullptr, void* ctl = nullptr);

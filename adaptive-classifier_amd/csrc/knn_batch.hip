@@ -28,6 +28,10 @@
 // kernel radix-selects the k' best by v, re-ranks them in fp64 and certifies exactly as for the sweep (rows that
 // were filtered out have v >= the k'-th kept v).  A candidate buffer that overflows sends its query to the exact
 // fp64 fallback.
+// Inner product (ac_knn_ip_topk_batch; template flag IP of knn_batch_sweep, the last one): the same sweep over the same prepared
+// store with v = f_q (h_p . h_q) ~ -2 p.q -- no |p|^2 term, no norm loads, the same bound E a fortiori (include/acamd.h).  Rows
+// past the end are bound-checked (the L2 form relies on +inf norms); thresholds, lists and the merge's certificate
+// (knn_merge_rerank<true>: key -(p.q) >= (a_last - E) / 2 for every row not re-ranked) work on v as they do for L2.
 #include "common.h"
 #include "gemm_common.h"
 #include "grid_sync.h"
@@ -174,7 +178,12 @@ template <int N> __device__ __forceinline__ void bwait_vm() { asm volatile("s_wa
 // (Measured and dropped in round 6, profiles/r06/knn_batch_nt_pmc_rejected.json, knn_batch_qplane_pmc_rejected.json: the store
 //  plane's DMA with the non-temporal bit -- the workgroups that share a row tile then each fetch it themselves, 159 / 130 GB of
 //  fabric reads at 4096 x 10M against 75 / 80 -- and a tile-major QUERY plane, 106 / 90 GB.)
-template <int BNS, int NWV, bool BURST, bool TWO_PHASE = false>        // ring depth, waves; TWO_PHASE: BatchParams::two_phase (its own instantiation)
+// IP (the LAST parameter: the L2 forms keep their names): the inner-product proposal v = f_q (h_p . h_q) ~ -2 p.q -- no |p|^2 term
+// and no norm loads.  Smaller is still better, so lists, segments, thr, best_only and the two-phase minima keep their meaning; what
+// the norms' +inf padding did for L2 -- rows past the end never qualify and are never published as a minimum -- is a bound check
+// of the LOGICAL row against BatchParams::N here (a zero plane row, or the clamped DMA's copy of the last row, gives a v that
+// would beat every real row when all products are negative).
+template <int BNS, int NWV, bool BURST, bool TWO_PHASE = false, bool IP = false>        // ring depth, waves; TWO_PHASE: BatchParams::two_phase (its own instantiation)
 __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams prm) {
     constexpr int WMW = NWV / 2, TM = BBM / (32 * WMW), TN = 4;    // wave grid WMW x 2, wave tile (32 TM) x 128
     constexpr int GPW = BGA / NWV;                                  // store / query groups each wave stages
@@ -311,7 +320,9 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
         const int rs8 = 8 * (int)ka->row_stride, nr = (int)ka->N;
         auto load_pn = [&](int mi, float (&pn)[16]) {
             const int l0 = row0 + mi * 32;                          // multiple of 32
-            if constexpr (!BURST) {                                 // the whole store: contiguous, padded with +inf -- nothing to check
+            if constexpr (IP) {                                     // no norm term: nothing to load (sweep_val never reads pn)
+                (void)l0; (void)pn;
+            } else if constexpr (!BURST) {                          // the whole store: contiguous, padded with +inf -- nothing to check
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const f32x4 t = *reinterpret_cast<const f32x4*>(f_pnorm + l0 + 8 * r4 + 4 * kg);
@@ -331,6 +342,37 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
         float thr[4], qf[4];
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) qf[ni] = f_qfac[qcol0 + 32 * ni];
+        // the sweep value of accumulator element (mi, ni, r): |p|^2 + f_q acc, or (IP) f_q acc -- taken IN PLACE below, once per tile
+        // (left as an expression, hipcc computes the 128 products once, keeps them live beside the accumulators through the
+        //  passes of this filter and spills)
+        auto sweep_val = [&](int mi, int ni, int r, const float (&pn)[16]) -> float {
+            if constexpr (IP) return acc[mi][ni][r];
+            else return fmaf(acc[mi][ni][r], qf[ni], pn[r]);
+        };
+        if constexpr (IP) {
+#pragma unroll
+            for (int mi = 0; mi < TM; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[mi][ni][r] *= qf[ni];
+            // Rows past the end of the sweep (LOGICAL rows against BatchParams::N: the zero rows of the plane's tile padding, the
+            // clamped DMA's copies of the last row) must not qualify in any branch below, nor be published as a two-phase
+            // minimum: the L2 form has +inf norms for that, this one sets their values to +inf.  Only the last row tile has any
+            // (a wave-uniform test).
+            if (row0 + 32 * TM > nr) {
+                const int left = nr - row0 - 4 * kg;                 // this lane's rows 32 mi + (r & 3) + 8 (r >> 2) below it exist
+#pragma unroll
+                for (int mi = 0; mi < TM; ++mi) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (32 * mi + (r & 3) + 8 * (r >> 2) >= left) {
+#pragma unroll
+                            for (int ni = 0; ni < 4; ++ni) acc[mi][ni][r] = INFINITY;
+                        }
+                }
+            }
+        }
         if constexpr (BURST && TWO_PHASE) {
             if (it == 0) {
                 // (1) this lane's smallest value per query column over its 32 * TM rows -> the workgroup's, through LDS
@@ -344,7 +386,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
 #pragma unroll
                     for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) best[ni] = fminf(best[ni], fmaf(acc[mi][ni][r], qf[ni], pn[r]));
+                        for (int r = 0; r < 16; ++r) best[ni] = fminf(best[ni], sweep_val(mi, ni, r, pn));
                 }
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni) atomicMin(&tp_min[wn * 128 + i32 + 32 * ni], tp_key(best[ni]));
@@ -398,7 +440,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
                 for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const float val = fmaf(acc[mi][ni][r], qf[ni], pn[r]);
+                        const float val = sweep_val(mi, ni, r, pn);
                         if (val < best[ni]) { best[ni] = val; bidx[ni] = 16 * mi + r; }
                     }
             }
@@ -428,7 +470,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
                 for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        mask[h][ni] |= (fmaf(acc[2 * h + m2][ni][r], qf[ni], pn[r]) < thr[ni] ? 1u : 0u) << (16 * m2 + r);
+                        mask[h][ni] |= (sweep_val(2 * h + m2, ni, r, pn) < thr[ni] ? 1u : 0u) << (16 * m2 + r);
             }
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) any |= mask[h][ni];
@@ -458,7 +500,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
                         const int slot = base[ni]++;
                         if (slot < f_segcap) {
                             const size_t e = (size_t)(qcol0 + 32 * ni) * f_cap + (unsigned)(sbase + slot);
-                            f_cand_d[e] = fmaf(acc[mi][ni][r], qf[ni], pn[r]);
+                            f_cand_d[e] = sweep_val(mi, ni, r, pn);
                             f_cand_i[e] = (int32_t)(row0 + mi * 32 + acc_row32(r, lane));
                         }
                     }
@@ -614,7 +656,8 @@ bool knn_batch_two_phase_applies(int64_t N, int nq, int kp, int segs) {
 }
 size_t knn_batch_two_phase_bytes() { return (size_t)64 * 8 * 256 * sizeof(unsigned); }       // wgmin for the largest grid
 
-int knn_batch_launch(const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
+template <bool IP>
+static int knn_batch_launch_t(const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
                      const float* qfac, float* cand_d, int32_t* cand_i, int32_t* cand_cnt, int cap, int segs, int64_t row_stride,
                      int best_only, hipStream_t stream, int32_t* clear_ctr, int32_t* clear_stats, int two_phase_kp, unsigned* wgmin,
                      void* ctl) {
@@ -624,9 +667,9 @@ int knn_batch_launch(const uint16_t* Pp, const float* pnorm, int64_t N, int D, c
     constexpr int ns = 4, nwv = 8;
     const size_t lds = (size_t)ns * BSLOT * 16;
     // (per call, like the launch sites of knn_l2.hip and knn_exact.hip: function attributes are per device, and a cached flag is neither)
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, false, IP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, false, false, IP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, true, IP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     BatchParams p{};
     p.Pp = Pp; p.p_rows = (N + 255) / 256 * 256; p.pnorm = pnorm;
     p.q_rows = ((int64_t)nq + 255) / 256 * 256;
@@ -664,12 +707,23 @@ int knn_batch_launch(const uint16_t* Pp, const float* pnorm, int64_t N, int D, c
         p.cand_d = cand_d + qoff * cap; p.cand_i = cand_i + qoff * cap; p.cand_cnt = cand_cnt + qoff * segs;
         p.clear_ctr = t0 == 0 ? clear_ctr : nullptr; p.clear_stats = t0 == 0 ? clear_stats : nullptr;
         const dim3 grid((unsigned)nblk), block(64 * nwv);
-        if (p.two_phase) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, true>), grid, block, lds, stream, p);
-        else if (segs > 1 || p.row_stride > 1 || best_only) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true>), grid, block, lds, stream, p);
-        else hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, false>), grid, block, lds, stream, p);
+        if (p.two_phase) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, true, IP>), grid, block, lds, stream, p);
+        else if (segs > 1 || p.row_stride > 1 || best_only) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, false, IP>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, false, false, IP>), grid, block, lds, stream, p);
         AC_LAUNCH_CHECK();
     }
     return AC_OK;
+}
+
+// ip: the inner-product instantiations (pnorm is not read then)
+int knn_batch_launch(bool ip, const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
+                     const float* qfac, float* cand_d, int32_t* cand_i, int32_t* cand_cnt, int cap, int segs, int64_t row_stride,
+                     int best_only, hipStream_t stream, int32_t* clear_ctr, int32_t* clear_stats, int two_phase_kp, unsigned* wgmin,
+                     void* ctl) {
+    return ip ? knn_batch_launch_t<true>(Pp, pnorm, N, D, Qp, nq, thr, qfac, cand_d, cand_i, cand_cnt, cap, segs, row_stride, best_only, stream,
+                                         clear_ctr, clear_stats, two_phase_kp, wgmin, ctl)
+              : knn_batch_launch_t<false>(Pp, pnorm, N, D, Qp, nq, thr, qfac, cand_d, cand_i, cand_cnt, cap, segs, row_stride, best_only, stream,
+                                          clear_ctr, clear_stats, two_phase_kp, wgmin, ctl);
 }
 
 }  // namespace ac

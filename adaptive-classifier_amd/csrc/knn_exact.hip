@@ -306,8 +306,11 @@ __device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, ch
         const double qn2 = dmisc[0], tau = dmisc[1];
         const double pn = sqrt((double)mx * 1.001), qn = sqrt(qn2);
         const double E = prm.gamma * (pn + qn) * (pn + qn) + 1e-30;
-        float t = (float)(tau - qn2 + E);
-        if ((double)t < tau - qn2 + E) t = nextafterf(t, INFINITY);
+        // (inner product: tau is the k'-th smallest exact KEY -(p.q) of the sample; a row with key <= tau has -2 p.q = 2 key <= 2 tau,
+        //  so its sweep value is <= 2 tau + E: at least k' rows of the store pass that threshold.  No |q|^2 term.)
+        const double bound = IP ? 2.0 * tau + E : tau - qn2 + E;
+        float t = (float)bound;
+        if ((double)t < bound) t = nextafterf(t, INFINITY);
         // a stage that kept fewer than k' rows for this query has no k'-th distance to offer: the threshold of the stage before it
         // (still a valid bound) stays; a valid new bound only ever tightens it
         if (isfinite(tau) && ns >= kout && t < prm.thr_out[q]) prm.thr_out[q] = t;

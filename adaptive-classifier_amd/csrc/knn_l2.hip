@@ -696,7 +696,10 @@ typedef uint32_t ku32x4 __attribute__((ext_vector_type(4)));
 // C/D layout of v_mfma_f32_32x32x16_f16: lane owns column (lane & 31) and these 16 rows
 __device__ __forceinline__ int plane_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
-template <int TQ>
+// IP (the last parameter): the inner-product proposal v = f_q acc ~ -2 p.q.  No norm is loaded; the rows past N, which the L2
+// form keeps out through the +inf padding of the norms, are bound-checked here (a zero plane row gives v = 0: the best value
+// of all when every product is negative).
+template <int TQ, bool IP = false>
 __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams prm) {
     constexpr int NJ = TQ / 32;                       // 32-column sub-tiles of the query tile
     constexpr int NB = 4, GK = 4;                     // register buffers x k-steps per buffer (16 loads in flight)
@@ -766,10 +769,16 @@ __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams 
         typedef const float __attribute__((address_space(4)))* cfp;
         const cfp pn = (cfp)(uintptr_t)(prm.pnorm + __builtin_amdgcn_readfirstlane(row0));
         bool maybe = false;
+        const int left = (int)prm.N - row0 - 4 * kg;                           // (IP) rows (r & 3) + 8 (r >> 2) below it exist
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float lo = pn[(r & 3) + 8 * (r >> 2)], hi = pn[(r & 3) + 8 * (r >> 2) + 4];
-            const float pnr = kg ? hi : lo;
+            float pnr;
+            if constexpr (IP) {
+                pnr = (r & 3) + 8 * (r >> 2) < left ? 0.f : INFINITY;
+            } else {
+                const float lo = pn[(r & 3) + 8 * (r >> 2)], hi = pn[(r & 3) + 8 * (r >> 2) + 4];
+                pnr = kg ? hi : lo;
+            }
 #pragma unroll
             for (int jj = 0; jj < NJ; ++jj) {
                 acc[jj][r] = fmaf(acc[jj][r], qf[jj], pnr);                    // the sweep value, in place
@@ -788,7 +797,7 @@ __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams 
                     for (int r = 0; r < 16; ++r) {
                         const float d = acc[jj][r];
                         const unsigned bit = 1u << (16 * jj + r);
-                        if (!(done & bit) && d < tau[jj]) {                    // (rows past N carry +inf norms: never below tau)
+                        if (!(done & bit) && d < tau[jj]) {                    // (rows past N carry +inf: never below tau)
                             const int slot = atomicAdd(&cnt[q], 1);
                             if (slot < prm.cap) {
                                 list_d[q * prm.cap + slot] = d;
@@ -1255,7 +1264,7 @@ bool make_plane_plan(int64_t N, int D, int nq, int k, PlanePlan* pp) {
     return true;
 }
 
-int plane_search(const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+int plane_search(bool ip, const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
                  const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64, int64_t* d_outI,
                  char* ws, int32_t* d_stats, hipStream_t stream) {
     const int64_t np = (N + 255) / 256 * 256;
@@ -1277,13 +1286,11 @@ int plane_search(const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, 
         sp.q0 = qt * pp.TQ; sp.nq = nq - sp.q0 < pp.TQ ? nq - sp.q0 : pp.TQ;
         sp.clear_ctr = qt == 0 ? (int32_t*)(ws + pp.ex.off_fb_ctr) : nullptr;
         sp.clear_stats = qt == 0 ? d_stats : nullptr;
-        if (pp.TQ == 64) {
-            AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_plane_sweep<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
-            hipLaunchKernelGGL(knn_plane_sweep<64>, dim3(pp.G), dim3(kThreads), pp.sweep_lds, stream, sp);
-        } else {
-            AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_plane_sweep<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
-            hipLaunchKernelGGL(knn_plane_sweep<32>, dim3(pp.G), dim3(kThreads), pp.sweep_lds, stream, sp);
-        }
+        void (*sweep_fn)(PlaneSweepParams);
+        if (pp.TQ == 64) sweep_fn = ip ? knn_plane_sweep<64, true> : knn_plane_sweep<64, false>;
+        else sweep_fn = ip ? knn_plane_sweep<32, true> : knn_plane_sweep<32, false>;
+        AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
+        hipLaunchKernelGGL(sweep_fn, dim3(pp.G), dim3(kThreads), pp.sweep_lds, stream, sp);
         AC_LAUNCH_CHECK();
     }
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
@@ -1292,7 +1299,7 @@ int plane_search(const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, 
     mp.G = pp.G; mp.nblk = 1; mp.gamma = gamma;
     mp.part_d = (const float*)(ws + pp.off_part_d); mp.part_i = (const int32_t*)(ws + pp.off_part_i);
     mp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    return ac::knn_exact_tail(false, mp, pp.ex, nq, pp.ex.merge_lds, stream);
+    return ac::knn_exact_tail(ip, mp, pp.ex, nq, pp.ex.merge_lds, stream);
 }
 
 }  // namespace
@@ -1344,10 +1351,13 @@ static int batch_segs(const BatchPlan& bp, int64_t rows, int nq) {
     return per_wg <= 8 ? bp.segs : 1;
 }
 
-extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
-                                    const float* d_norms, const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset,
-                                    float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
-                                    int32_t* d_stats, ac_stream_t stream_) {
+// the prepared-store search of both metrics: ip = false squared L2 (ac_knn_l2_topk_batch), true inner product
+// (ac_knn_ip_topk_batch).  One plan, one workspace layout, one launch sequence over the SAME prepared store; the metric only
+// picks the instantiation of the sweeps and of the exact stages.
+static int knn_topk_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
+                          const float* d_norms, const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset,
+                          float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
+                          int32_t* d_stats, ac_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     BatchPlan bp;
     int rc = make_batch_plan(N, D, nq, k, &bp);
@@ -1360,7 +1370,7 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
         PlanePlan pp;
         if (make_plane_plan(N, D, nq, k, &pp)) {
             AC_REQUIRE(ws_bytes >= pp.total, AC_EWORKSPACE, "knn batch: workspace %zu < required %zu", ws_bytes, pp.total);
-            return plane_search(pp, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, ws,
+            return plane_search(ip, pp, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, ws,
                                 d_stats, stream);
         }
     }
@@ -1401,12 +1411,12 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
         const int segs = batch_segs(bp, ac::knn_sample_rows(N, sst), nq);
         const size_t mlds = bp.ex.merge_lds - (segs > 1 ? 0 : ac::align_up((size_t)bp.cap * 4, 16));
         sp.cand_segs = segs;
-        rc = ac::knn_batch_launch(d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
+        rc = ac::knn_batch_launch(ip, d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
                                   (const float*)(ws + bp.off_qfac), (float*)(ws + bp.off_cd), (int32_t*)(ws + bp.off_ci),
                                   (int32_t*)(ws + bp.off_cnt), bp.cap, segs, sst, st == 0 ? 1 : 0, stream);
         if (rc != AC_OK) return rc;
         sp.N = ac::knn_sample_rows(N, sst); sp.run_stride = sst > 1 ? 8 * sst : 0;   // sample row i = store row (i >> 3) * 8 sst + (i & 7)
-        rc = ac::knn_merge_launch(false, sp, nq, st == 0 ? bp.ex.merge_lds : 0, mlds, stream);      // (the opt-in covers the later stages)
+        rc = ac::knn_merge_launch(ip, sp, nq, st == 0 ? bp.ex.merge_lds : 0, mlds, stream);      // (the opt-in covers the later stages)
         if (rc != AC_OK) return rc;
         if (dbg) {
             AC_HIP_CHECK(hipStreamSynchronize(stream));
@@ -1424,7 +1434,7 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
     // 3. the GEMM-form sweep: candidates (row, v) with v below the query's threshold (its workgroup 0 also zeroes the caller's
     //    d_stats and the fallback's slot counter, which the merge after it increments)
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
-    rc = ac::knn_batch_launch(d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
+    rc = ac::knn_batch_launch(ip, d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
                               (const float*)(ws + bp.off_qfac), (float*)(ws + bp.off_cd), (int32_t*)(ws + bp.off_ci), (int32_t*)(ws + bp.off_cnt), bp.cap, msegs, 1, 0, stream,
                               (int32_t*)(ws + bp.ex.off_fb_ctr), d_stats, two_phase ? bp.kp : 0, (unsigned*)(ws + bp.off_wgmin), ws + bp.off_ctl);
     if (rc != AC_OK) return rc;
@@ -1435,5 +1445,26 @@ extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
     mp.cand_cnt = (const int32_t*)(ws + bp.off_cnt); mp.cand_cap = bp.cap; mp.cand_segs = msegs;
     mp.part_d = (const float*)(ws + bp.off_cd); mp.part_i = (const int32_t*)(ws + bp.off_ci);
     mp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    return ac::knn_exact_tail(false, mp, bp.ex, nq, mlds, stream);
+    return ac::knn_exact_tail(ip, mp, bp.ex, nq, mlds, stream);
+}
+
+extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
+                                    const float* d_norms, const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset,
+                                    float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
+                                    int32_t* d_stats, ac_stream_t stream_) {
+    return knn_topk_batch(false, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes,
+                          d_stats, stream_);
+}
+
+// inner product over the same prepared store: the plan, and hence the workspace, is the L2 batch search's
+extern "C" int ac_knn_ip_topk_batch_workspace(int64_t N, int D, int nq, int k, size_t* bytes) {
+    return ac_knn_l2_topk_batch_workspace(N, D, nq, k, bytes);
+}
+
+extern "C" int ac_knn_ip_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
+                                    const float* d_norms, const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset,
+                                    float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
+                                    int32_t* d_stats, ac_stream_t stream_) {
+    return knn_topk_batch(true, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes,
+                          d_stats, stream_);
 }

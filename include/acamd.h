@@ -114,7 +114,7 @@ int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
  * for each query the k rows with the LARGEST p.q, in DESCENDING order, ties to the lower row id.  Values may be negative.
  * Argument lists, alignment / ldP / ldQ rules, error codes, limits (k <= AC_KNN_MAX_K and the LDS bound on D for big
  * stores, the small-store exact path for N <= 8192, AC_EUNSUPPORTED beyond), workspace size and d_stats are those of the L2
- * namesakes; the fp32 sweeps serve every shape (there is no prepared-store form).
+ * namesakes; these entry points run the fp32 sweeps for every shape (the prepared-store form is ac_knn_ip_topk_batch below).
  *
  * Exactness contract: the ids are the top-k under the exactly computed inner product (fp64 accumulation of the fp32
  * products, each of which is exact in fp64), d_outD is that value rounded once to fp32, d_outD64 (may be NULL) the fp64
@@ -176,6 +176,40 @@ int ac_knn_update_store(const float* d_P, int64_t N_old, int64_t N_new, int64_t 
                         int32_t* d_exponent_changed, ac_stream_t stream);
 int ac_knn_l2_topk_batch_workspace(int64_t N, int D, int nq, int k, size_t* bytes);
 int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D,
+                         const uint16_t* d_planes, const float* d_norms,
+                         const float* d_Q, int nq, int64_t ldQ, int k,
+                         int64_t row_offset,
+                         float* d_outD, double* d_outD64, int64_t* d_outI,
+                         void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                         ac_stream_t stream);
+
+/*
+ * Inner-product search over the SAME prepared store (ac_knn_prepare_store / ac_knn_update_store, unchanged: one plane serves
+ * both metrics; of d_norms only the maximum |p|^2 is read).  Argument list, limits (N >= 65536, k <= 100, AC_EUNSUPPORTED
+ * otherwise: use ac_knn_ip_topk_x), workspace (the L2 batch planner's value) and d_stats ([0] fallback queries, [1] = 2 when
+ * knn_plane_sweep ran) are those of ac_knn_l2_topk_batch; the result contract is ac_knn_ip_topk_x's: descending, ties to the
+ * lower id, (-FLT_MAX, -1) padding, -inf in d_outD64, row_offset added to real ids only -- bit for bit what ac_knn_ip_topk_x
+ * returns.
+ * Proposal value: v = f_q (h_p . h_q), f_q = -2 2^(e_p + e_q), i.e. ~ -2 p.q -- the L2 form without its |p|^2 term (no norm is
+ * loaded; rows past N are bound-checked instead of carrying +inf norms).  Smaller is better, as for L2, so candidate lists,
+ * thresholds and the two-phase minima keep their meaning.
+ * Error bound: the bound derived above for |p|^2 - 2 p.q charges (a) the fp16 roundings of both operands, 2^-10 (1 + 2^-10)
+ * |p^||q^| + 2^-25 sqrt(K) (|p^| + |q^|), (b) 2 ulp for each of the K + 16 fp32 additions of the accumulator, both times
+ * 2 2^(e_p+e_q), and (c) the roundings of |p|^2 and of the final fma.  v has the same operands, the same accumulation and ONE
+ * final rounding (the product f_q acc, f_q a power of two: exact short of underflow) in place of (c), and its exact value
+ * -2 p.q satisfies 2 |p.q| <= 2 |p||q| <= (|p| + |q|)^2.  Hence |v - (-2 p.q)| <= E = gamma (|p|max + |q|)^2 with the same
+ * gamma = 1.01 (2^-11 + (K + 18 + sqrt K) 2^-24), a fortiori.
+ * Certificate (knn_merge_rerank<IP>, as for ac_knn_ip_topk_x with this gamma): a row that was not re-ranked has v >= a_last (the
+ * largest selected sweep value; in candidate mode also every row the filter dropped, since thr >= a_last whenever at least k'
+ * rows were kept -- hence the extra condition nreal >= k'), so its key -(p.q) >= (a_last - E) / 2; a query is certified when
+ * its k-th exact key is strictly below that, its list is full and nothing overflowed.  Every other query is redone by the exact
+ * fp64 sweep inside the call.
+ * Thresholds: by default the k'-th smallest sweep value of a sample stage (or of the main sweep's first tile round), one ulp up:
+ * metric-agnostic.  The A/B form AC_KNN_THR_EXACT=1 re-ranks the sample: thr = 2 tau + E rounded up, tau = the k'-th smallest
+ * exact key of the sample (a row with key <= tau has v <= 2 key + E <= 2 tau + E, so at least k' rows of the store pass).
+ */
+int ac_knn_ip_topk_batch_workspace(int64_t N, int D, int nq, int k, size_t* bytes);
+int ac_knn_ip_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D,
                          const uint16_t* d_planes, const float* d_norms,
                          const float* d_Q, int nq, int64_t ldQ, int k,
                          int64_t row_offset,

@@ -107,6 +107,15 @@ _SIGNATURES = {
     "ac_knn_ip_topk_batch_workspace": (c_int, [c_int64, c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_knn_ip_topk_batch": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int,
                                      c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_range_workspace": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ac_knn_l2_range_count": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_l2_range_fill": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_ip_range_count": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_ip_range_fill": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ac_knn_set_profile_events": (c_int, [c_void_p, c_void_p]),
     "ac_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ac_topk_merge_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -10,7 +10,8 @@ search() is one call into the C ABI (`ac_knn_l2_topk`): exact squared L2, ascend
 the lower id.  HipFlatIPIndex is the same store searched by inner product (`ac_knn_ip_topk`,
 faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.
 Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `ac_knn_l2_topk_batch` /
-`ac_knn_ip_topk_batch`.
+`ac_knn_ip_topk_batch`.  range_search() (faiss range_search: every row within a radius) is `ac_knn_*_range_count` / `_fill` over
+the fp32 rows.
 """
 import ctypes
 
@@ -176,6 +177,82 @@ def knn_l2_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, p
     ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
     _, I = knn_l2_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex, prepared=prepared)
     return ex, I
+
+
+def knn_range_workspace_bytes(N, D, nq):
+    b = ctypes.c_size_t(0)
+    nv.check(nv.lib().ac_knn_range_workspace(N, D, nq, ctypes.byref(b)), "ac_knn_range_workspace")
+    return b.value
+
+
+def range_query_chunk(N, D, nq, max_ws_bytes):
+    """Queries per call of a range search of nq queries: the largest count whose workspace (the membership bitmap grows as
+    nq * N / 8) stays within max_ws_bytes; at least 1.  Raises for an (N, D) the library does not cover."""
+    chunk = max(1, min(nq, max_ws_bytes // max(knn_range_workspace_bytes(N, D, 1), 1)))
+    while chunk > 1 and knn_range_workspace_bytes(N, D, chunk) > max_ws_bytes:
+        chunk = max(1, chunk // 2)
+    return chunk
+
+
+def stitch_range_chunks(parts, device=None):
+    """[(lims [c_i + 1], D, I), ...] of consecutive query chunks -> one (lims [sum c_i + 1], D, I): every chunk's lims shifted by
+    the hits before it.  Tensors on any one device; no host synchronisation."""
+    if len(parts) == 1:
+        return parts[0]
+    if not parts:
+        return (torch.zeros(1, dtype=torch.int64, device=device), torch.empty(0, dtype=torch.float32, device=device),
+                torch.empty(0, dtype=torch.int64, device=device))
+    lims, base = [parts[0][0][:1]], parts[0][0][:1]
+    for l, _, _ in parts:
+        lims.append(l[1:] + base)
+        base = base + l[-1:]
+    return (torch.cat(lims), torch.cat([d for _, d, _ in parts]), torch.cat([i for _, _, i in parts]))
+
+
+def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=False, max_ws_bytes=256 << 20, stats=None):
+    """Exact range search (`ac_knn_l2_range_count` / `_fill`, or the `ip` pair): every row of P[:N] with float32(exact squared
+    distance) < radius (metric "l2"), or float32(exact inner product) > radius ("ip"); faiss range_search semantics, strict.
+
+    radius: a float or a [nq] tensor (one radius per query).  Returns (lims int64 [nq + 1], D fp32, I int64) device tensors: the
+    hits of query q are D / I[lims[q]:lims[q + 1]], by ascending row id (+ row_offset); exact_out=True appends the exact fp64
+    values.  Queries go in chunks whose workspace stays within max_ws_bytes; the result does not depend on the chunking.  One
+    host read (the hit count) per chunk.  stats: optional int32 [4] cuda tensor, the d_stats of the LAST chunk's calls ([0] =
+    pairs the count phase decided by exact arithmetic, [1] = 1 if the fill did not fit -- it always fits here)."""
+    nv.require_gpu()
+    assert metric in ("l2", "ip")
+    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
+    assert P.stride(1) == 1 and Q.stride(1) == 1
+    nq, dev = Q.shape[0], Q.device
+    if torch.is_tensor(radius):
+        rad = radius.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert rad.numel() == nq, "one radius per query"
+    else:
+        rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+    count = getattr(nv.lib(), f"ac_knn_{metric}_range_count")
+    fill = getattr(nv.lib(), f"ac_knn_{metric}_range_fill")
+    chunk = range_query_chunk(N, D, nq, max_ws_bytes) if nq else 1
+    ws = torch.empty(max(knn_range_workspace_bytes(N, D, min(chunk, nq)), 256), dtype=torch.uint8, device=dev)
+    parts = []
+    with torch.cuda.device(dev):
+        for s in range(0, nq, chunk):
+            q, r = Q[s:s + chunk], rad[s:s + chunk]
+            c = q.shape[0]
+            lims = torch.empty(c + 1, dtype=torch.int64, device=dev)
+            nv.check(count(nv.ptr(P), N, P.stride(0), D, nv.ptr(q), c, q.stride(0), nv.ptr(r), nv.ptr(lims), nv.ptr(ws), ws.numel(),
+                           nv.ptr(stats), nv.stream_ptr(dev)), f"ac_knn_{metric}_range_count")
+            total = int(lims[-1].item())                      # the protocol's one host read: sizes the outputs
+            outD = torch.empty(total, dtype=torch.float32, device=dev)
+            outI = torch.empty(total, dtype=torch.int64, device=dev)
+            outE = torch.empty(total, dtype=torch.float64, device=dev) if exact_out else None
+            nv.check(fill(nv.ptr(P), N, P.stride(0), D, nv.ptr(q), c, q.stride(0), row_offset, nv.ptr(lims), total,
+                          nv.ptr(outD), nv.ptr(outE), nv.ptr(outI), nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)),
+                     f"ac_knn_{metric}_range_fill")
+            parts.append((lims, outD, outI, outE))
+    if nq == 0:
+        empty = stitch_range_chunks([], dev)
+        return empty + (torch.empty(0, dtype=torch.float64, device=dev),) if exact_out else empty
+    out = stitch_range_chunks([p[:3] for p in parts], dev)
+    return out + (torch.cat([p[3] for p in parts]),) if exact_out else out
 
 
 class _HipFlatIndex:
@@ -385,6 +462,23 @@ class _HipFlatIndex:
         q = self._as_rows(x)
         D, I = self.search_device(q, int(k))
         return D.cpu().numpy(), I.cpu().numpy()
+
+    def range_search_device(self, q, radius, max_ws_bytes=256 << 20):
+        """q: [nq, d] fp32 tensor (any device), radius: float or [nq] tensor -> (lims, D, I) CUDA tensors (`knn_range_search`).
+        Searches the fp32 rows: the fp16 plane is neither needed nor prepared."""
+        self._materialize()
+        q = q.detach().to(device=self.device, dtype=torch.float32)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.stride(-1) != 1:
+            q = q.contiguous()
+        return knn_range_search(self._store, self._n, self.d, q, radius, metric=self.metric, max_ws_bytes=max_ws_bytes)
+
+    def range_search(self, x, radius):
+        """faiss signature: numpy in, (lims int64 [nq + 1], D float32, I int64) numpy out.  L2: squared distance < radius;
+        IP: inner product > radius.  Hits of a query by ascending row id."""
+        lims, D, I = self.range_search_device(self._as_rows(x), radius)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
     @property
     def exact_fallbacks(self):

@@ -463,6 +463,21 @@ class PrototypeMemory:
                 results.append((self._label_of_row(int(idx)), float(score)))
         return results
 
+    def prototypes_within(self, query_embedding: torch.Tensor, radius: float) -> List[Tuple[str, float]]:
+        """[(label, squared distance)] of every prototype (or `load_rows()` row) whose squared L2 distance to the query is
+        < radius (faiss range_search, strict), ascending by distance, ties to the lower row.  Duplicate detection before
+        `add_examples`, open-set rejection ("is any prototype closer than r?")."""
+        with self._lock:
+            if self._row_labels is None and self.updates_since_rebuild >= self.config.prototype_update_frequency:
+                self._rebuild_index()
+            if self.index.ntotal == 0:
+                return []
+            self._flush_dirty()
+            _, D, I = self.index.range_search_device(query_embedding.detach().reshape(1, -1), float(radius))
+            d, ids = D.cpu().numpy(), I.cpu().numpy()
+            order = np.lexsort((ids, d))
+            return [(self._label_of_row(int(ids[i])), float(d[i])) for i in order]
+
     def _label_of_row(self, idx):
         if self._row_labels is not None:
             return self._row_label_names[int(self._row_labels[idx].item())]

@@ -218,6 +218,66 @@ int ac_knn_ip_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D,
                          ac_stream_t stream);
 
 /*
+ * Exact RANGE search (radius queries): faiss IndexFlatL2.range_search / IndexFlatIP.range_search -- every row within a radius,
+ * as (lims, D, I).  No reference call site (memory.py only searches top-k); faiss's own GPU flat index has no range search.
+ *
+ * Exactness contract.  For query q with radius r_q (fp32, one per query):
+ *   L2: row n is a hit iff float32(d64) < r_q, d64 = the fp64 sum of (double(p_c) - double(q_c))^2 -- the value
+ *       ac_knn_l2_topk rounds and returns;
+ *   IP: row n is a hit iff float32(v64) > r_q, v64 = the fp64 sum of the exact fp32 products, as in ac_knn_ip_topk.
+ * Both comparisons are strict, as in faiss.  Membership is defined on the fp32 value the caller sees: every returned D satisfies
+ * the predicate, and a row is in the result iff a top-k search with k = N would report it with a value on that side of r_q.
+ * The hits of one query are listed by ASCENDING ROW ID -- deterministic, independent of grid size, launch order and of how the
+ * caller chunks its queries; no result depends on the order in which atomics land.
+ *   lims  int64 [nq + 1], lims[0] = 0; the hits of query q sit at [lims[q], lims[q + 1]) of D / I
+ *   I = row id + row_offset (int64), D = fp32; d_outD64 (may be NULL) receives the exact fp64 values
+ *   r_q <= 0 (L2) or r_q = +inf (IP): no hits; r_q = +inf (L2) / -inf (IP): every row with a finite fp32 value; NaN radius:
+ *   no hits; N = 0: lims all zero; nq = 0: nothing is written, AC_OK.
+ * Supported (N, D): exactly those ac_knn_l2_topk_workspace(N, D, nq, 1) accepts, with its error codes otherwise -- big stores up
+ * to the D whose 16-query tile fits in LDS, stores of <= 8192 rows any D (a plain fp64 kernel, as for top-k).
+ *
+ * Protocol: count -> read lims[nq] -> allocate -> fill (faiss's own range search counts, allocates, fills).
+ *   ac_knn_range_workspace   bytes both calls need (both metrics).  It holds the membership bitmap, nq * ceil(N / 64) * 8 bytes
+ *                            (twice that for big stores): callers with many queries call per chunk of queries.
+ *   ac_knn_*_range_count     writes d_lims and leaves membership in d_ws.  d_stats (optional int32[4], may be NULL): [0] = the
+ *                            (query, row) pairs decided by exact arithmetic in this call, the rest 0.
+ *   ac_knn_*_range_fill      the same (d_P .. ldQ) arguments, the d_lims and the d_ws of the count call, ON THE SAME STREAM with
+ *                            d_ws UNTOUCHED in between.  Writes lims[nq] entries of d_outD / d_outD64 / d_outI and never writes
+ *                            past `capacity` entries: if lims[nq] > capacity it writes nothing and sets d_stats[1] = 1
+ *                            (else 0; the other words of d_stats are left alone).
+ * Both calls are asynchronous; the only host read is the caller's read of lims[nq] to size the outputs.  Alignment / ldP / ldQ
+ * rules and AC_EWORKSPACE as ac_knn_l2_topk.
+ * Mechanism (csrc/knn_range.hip, profiles/knn_range/README.md): the fp32 MFMA sweep of ac_knn_l2_topk with a different epilogue.
+ * Its value v carries the a-priori bound |v - exact| <= E = gamma (|p| + |q|)^2 the top-k certificate uses, evaluated per row;
+ * a pair with v <= lo is a hit, with v >= hi is not, where lo / hi sit E inside / outside the radius moved one fp32 step to the
+ * safe side (so the fp32 ROUNDING of the exact value is on the proven side too); every pair in between is decided by the exact
+ * fp64 value rounded to fp32.  Membership goes to a bitmap with plain stores, each piece written by exactly one wave.
+ */
+int ac_knn_range_workspace(int64_t N, int D, int nq, size_t* bytes);
+int ac_knn_l2_range_count(const float* d_P, int64_t N, int64_t ldP, int D,
+                          const float* d_Q, int nq, int64_t ldQ,
+                          const float* d_radius, int64_t* d_lims,
+                          void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                          ac_stream_t stream);
+int ac_knn_l2_range_fill(const float* d_P, int64_t N, int64_t ldP, int D,
+                         const float* d_Q, int nq, int64_t ldQ,
+                         int64_t row_offset, const int64_t* d_lims, int64_t capacity,
+                         float* d_outD, double* d_outD64, int64_t* d_outI,
+                         void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                         ac_stream_t stream);
+int ac_knn_ip_range_count(const float* d_P, int64_t N, int64_t ldP, int D,
+                          const float* d_Q, int nq, int64_t ldQ,
+                          const float* d_radius, int64_t* d_lims,
+                          void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                          ac_stream_t stream);
+int ac_knn_ip_range_fill(const float* d_P, int64_t N, int64_t ldP, int D,
+                         const float* d_Q, int nq, int64_t ldQ,
+                         int64_t row_offset, const int64_t* d_lims, int64_t capacity,
+                         float* d_outD, double* d_outD64, int64_t* d_outI,
+                         void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                         ac_stream_t stream);
+
+/*
  * Optional profiling hook: when both events are non-NULL, every following
  * ac_knn_l2_topk / ac_knn_ip_topk call of THIS thread records `start` immediately before and
  * `stop` immediately after its sweep kernel (the HBM-bound kernel) on the

@@ -116,6 +116,16 @@ _SIGNATURES = {
                                       c_void_p, c_size_t, c_void_p, c_void_p]),
     "ac_knn_ip_range_fill": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_int64, c_void_p, c_int64,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_l2_topk_sel": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_ip_topk_sel": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_l2_topk_ids": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ac_knn_ip_topk_ids": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ac_knn_sel_pack": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "ac_knn_sel_classes": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
     "ac_knn_set_profile_events": (c_int, [c_void_p, c_void_p]),
     "ac_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ac_topk_merge_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -11,7 +11,8 @@ the lower id.  HipFlatIPIndex is the same store searched by inner product (`ac_k
 faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.
 Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `ac_knn_l2_topk_batch` /
 `ac_knn_ip_topk_batch`.  range_search() (faiss range_search: every row within a radius) is `ac_knn_*_range_count` / `_fill` over
-the fp32 rows.
+the fp32 rows.  search(x, k, sel=...) is the FILTERED search (faiss SearchParameters(sel=IDSelector...)): the k best among the
+rows a `RowSelector` names, through `ac_knn_*_topk_sel` (bitmap) or `ac_knn_*_topk_ids` (a short id list).
 """
 import ctypes
 
@@ -177,6 +178,175 @@ def knn_l2_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, p
     ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
     _, I = knn_l2_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex, prepared=prepared)
     return ex, I
+
+
+KNN_IDS_MAX = 8192       # rows the id-list route covers (include/acamd.h: ac_knn_*_topk_ids)
+
+
+def _sel_words(n):
+    return max((int(n) + 63) // 64, 1)
+
+
+def _pack_host(mask):
+    """bool [n] -> int64 words [ceil(n / 64)] (>= 1 word), bit r % 64 of word r / 64, bit 0 the least significant: numpy's
+    little-endian bit order IS the layout (faiss IDSelectorBitmap); the tail bits of the last word are zero"""
+    mask = np.ascontiguousarray(mask, dtype=bool).reshape(-1)
+    raw = np.packbits(mask, bitorder="little")
+    buf = np.zeros(_sel_words(mask.size) * 8, dtype=np.uint8)
+    buf[: raw.size] = raw
+    return buf.view("<i8").astype(np.int64, copy=False)
+
+
+class RowSelector:
+    """Which rows of a flat store a FILTERED search may return (faiss IDSelectorBitmap / IDSelectorBatch / IDSelectorRange).
+
+    words: int64 tensor, the packed bitmap (`ac_knn_*_topk_sel`'s d_sel: row r = bit r % 64 of word r / 64, bit 0 the least
+    significant); n: the rows it covers; ids: the sorted, unique int64 row ids when it was built from a host id list (else None)
+    -- a selector of <= KNN_IDS_MAX ids is searched through the id-list route.  Host inputs are packed with
+    numpy.packbits(bitorder="little") and uploaded (to `device`; without one and without a GPU they stay on the host); device
+    inputs are packed by `ac_knn_sel_pack` / `ac_knn_sel_classes` without any host synchronisation."""
+
+    def __init__(self, words, n, ids=None):
+        self.words, self.n, self.ids = words, int(n), ids
+
+    @staticmethod
+    def _upload(t, device):
+        if device is None and torch.cuda.is_available():
+            device = f"cuda:{torch.cuda.current_device()}"
+        return t if device is None else t.to(device)
+
+    @classmethod
+    def from_mask(cls, mask, device=None):
+        """mask: bool tensor / array [n]; True = selected"""
+        if isinstance(mask, torch.Tensor) and mask.is_cuda:
+            m = mask.detach().reshape(-1).to(torch.uint8).contiguous()
+            n = m.numel()
+            words = torch.empty(_sel_words(n), dtype=torch.int64, device=m.device)
+            if n == 0:
+                words.zero_()
+            with torch.cuda.device(m.device):
+                nv.check(nv.lib().ac_knn_sel_pack(nv.ptr(m), n, nv.ptr(words), nv.stream_ptr(m.device)), "ac_knn_sel_pack")
+            return cls(words, n)
+        m = mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+        m = m.reshape(-1).astype(bool)
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), m.size)
+
+    @classmethod
+    def from_ids(cls, ids, n, device=None):
+        """ids: row ids in any order, duplicates allowed; ids outside [0, n) are dropped.  A host list is sorted and
+        de-duplicated and kept next to the bitmap (the id-list route); a device tensor becomes a bitmap only (sorting it would
+        need a host read of the unique count)."""
+        n = int(n)
+        if isinstance(ids, torch.Tensor) and ids.is_cuda:
+            i = ids.detach().reshape(-1).to(torch.int64)
+            m = torch.zeros(n + 1, dtype=torch.uint8, device=i.device)
+            m[torch.where((i >= 0) & (i < n), i, torch.full_like(i, n))] = 1      # out-of-range ids land in the spare slot
+            return cls.from_mask(m[:n])
+        i = ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+        i = np.unique(i.reshape(-1).astype(np.int64))
+        i = i[(i >= 0) & (i < n)]
+        m = np.zeros(n, dtype=bool)
+        m[i] = True
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), n, cls._upload(torch.from_numpy(i), device))
+
+    @classmethod
+    def from_range(cls, lo, hi, n, device=None):
+        """rows lo <= r < hi (faiss IDSelectorRange), clipped to [0, n)"""
+        n = int(n)
+        m = np.zeros(n, dtype=bool)
+        m[max(int(lo), 0): max(min(int(hi), n), 0)] = True
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), n)
+
+    @classmethod
+    def from_classes(cls, row_class, class_ids, n_classes, device=None):
+        """rows whose class (int32 row -> class map [n]) is one of class_ids; a row class outside [0, n_classes) is unselected"""
+        n_classes = int(n_classes)
+        on = np.zeros(max(n_classes, 1), dtype=np.uint8)
+        cid = np.asarray(list(class_ids), dtype=np.int64).reshape(-1)
+        on[cid[(cid >= 0) & (cid < n_classes)]] = 1
+        if isinstance(row_class, torch.Tensor) and row_class.is_cuda:
+            rc = row_class.detach().reshape(-1).to(torch.int32).contiguous()
+            n = rc.numel()
+            words = torch.empty(_sel_words(n), dtype=torch.int64, device=rc.device)
+            if n == 0:
+                words.zero_()
+            d_on = torch.from_numpy(on).to(rc.device, non_blocking=True)
+            with torch.cuda.device(rc.device):
+                nv.check(nv.lib().ac_knn_sel_classes(nv.ptr(rc), n, nv.ptr(d_on), n_classes, nv.ptr(words), nv.stream_ptr(rc.device)),
+                         "ac_knn_sel_classes")
+            return cls(words, n)
+        rc = row_class.detach().cpu().numpy() if isinstance(row_class, torch.Tensor) else np.asarray(row_class)
+        rc = rc.reshape(-1).astype(np.int64)
+        ok = (rc >= 0) & (rc < n_classes)
+        m = np.zeros(rc.size, dtype=bool)
+        m[ok] = on[rc[ok]] != 0
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), rc.size)
+
+    def to(self, device):
+        return RowSelector(self.words.to(device), self.n, None if self.ids is None else self.ids.to(device))
+
+    def count(self):
+        """selected rows (reads the bitmap back: one host synchronisation)"""
+        if self.ids is not None:
+            return int(self.ids.numel())
+        return int(np.unpackbits(self.words.cpu().numpy().view(np.uint8), bitorder="little")[: self.n].sum())
+
+
+def knn_topk_sel(P, N, D, Q, k, sel, metric="l2", sel_bit0=0, row_offset=0, out=None, workspace=None, stats=None, exact_out=None):
+    """FILTERED top-k (`ac_knn_l2_topk_sel` / `ac_knn_ip_topk_sel`): the k best rows of P[:N] AMONG the selected ones -- what
+    `knn_l2_topk` / `knn_ip_topk` return on a store of only those rows, with the original row ids; fewer than k selected rows
+    pad with (FLT_MAX, -1) / (-FLT_MAX, -1).  sel: a RowSelector or its int64 words tensor; local row r is bit sel_bit0 + r (a
+    row shard passes sel_bit0 = its first row and the replicated global bitmap).  Other arguments, the workspace
+    (`knn_workspace_bytes`) and stats as `knn_l2_topk`; searches the fp32 rows (no prepared store).  Asynchronous."""
+    nv.require_gpu()
+    assert metric in ("l2", "ip")
+    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
+    assert P.stride(1) == 1 and Q.stride(1) == 1
+    words = sel.words if isinstance(sel, RowSelector) else sel
+    assert words.dtype == torch.int64 and words.is_cuda and words.is_contiguous()
+    if int(sel_bit0) + N > words.numel() * 64:
+        raise ValueError(f"selection of {words.numel() * 64} bits does not cover rows [{sel_bit0}, {int(sel_bit0) + N})")
+    nq, dev = Q.shape[0], Q.device
+    if out is None:
+        outD = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    else:
+        outD, outI = out
+    need = knn_workspace_bytes(N, D, nq, k)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    entry = f"ac_knn_{metric}_topk_sel"
+    with torch.cuda.device(dev):
+        rc = getattr(nv.lib(), entry)(
+            nv.ptr(P), N, P.stride(0), D, nv.ptr(Q), nq, Q.stride(0), k, row_offset, nv.ptr(words), int(sel_bit0),
+            nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(), nv.ptr(stats), nv.stream_ptr(dev))
+    nv.check(rc, entry)
+    return outD, outI
+
+
+def knn_topk_ids(P, N, D, Q, k, ids, metric="l2", row_offset=0, out=None, exact_out=None):
+    """FILTERED top-k over a short id list (`ac_knn_l2_topk_ids` / `ac_knn_ip_topk_ids`): ids = a RowSelector built by
+    `from_ids`, or a SORTED, UNIQUE int64 cuda tensor of <= KNN_IDS_MAX row ids (ids outside [0, N) are skipped).  Reads the
+    listed rows only; exact by construction, any k and D, no workspace.  Same result as `knn_topk_sel` with those rows."""
+    nv.require_gpu()
+    assert metric in ("l2", "ip")
+    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
+    assert P.stride(1) == 1 and Q.stride(1) == 1
+    ids = ids.ids if isinstance(ids, RowSelector) else ids
+    assert ids is not None and ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+    nq, dev = Q.shape[0], Q.device
+    if out is None:
+        outD = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    else:
+        outD, outI = out
+    entry = f"ac_knn_{metric}_topk_ids"
+    with torch.cuda.device(dev):
+        rc = getattr(nv.lib(), entry)(
+            nv.ptr(P), N, P.stride(0), D, nv.ptr(ids) if ids.numel() else None, ids.numel(), nv.ptr(Q), nq, Q.stride(0), k, row_offset,
+            nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.stream_ptr(dev))
+    nv.check(rc, entry)
+    return outD, outI
 
 
 def knn_range_workspace_bytes(N, D, nq):
@@ -429,8 +599,42 @@ class _HipFlatIndex:
                     self._rows_changed()                                  # never leave a plane that no longer matches the rows
                     raise
 
-    def search_device(self, q, k):
-        """q: [nq, d] fp32 tensor (any device) -> (dist, ids) CUDA tensors; no host sync."""
+    def _as_selector(self, sel):
+        """a RowSelector for the resident rows from what search() accepts: a RowSelector, a bool mask [ntotal] or row ids"""
+        if isinstance(sel, RowSelector):
+            if sel.n != self._n:
+                raise ValueError(f"selector covers {sel.n} rows, the index holds {self._n}")
+            return sel if sel.words.device == self.device else sel.to(self.device)
+        is_bool = sel.dtype == torch.bool if isinstance(sel, torch.Tensor) else np.asarray(sel).dtype == np.bool_
+        if is_bool:
+            if int(np.prod(tuple(sel.shape))) != self._n:
+                raise ValueError(f"mask has {int(np.prod(tuple(sel.shape)))} entries, the index holds {self._n} rows")
+            return RowSelector.from_mask(sel if isinstance(sel, torch.Tensor) and sel.is_cuda else (
+                sel.cpu().numpy() if isinstance(sel, torch.Tensor) else sel), device=self.device)
+        return RowSelector.from_ids(sel, self._n, device=self.device)
+
+    def _search_sel(self, q, k, sel):
+        """the FILTERED search: a selector built from <= KNN_IDS_MAX ids takes the id-list route (its length is known on the
+        host), everything else the bitmap route over the fp32 rows; the fp16 plane is neither used nor prepared"""
+        self._materialize()
+        q = q.detach().to(device=self.device, dtype=torch.float32)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.stride(-1) != 1:
+            q = q.contiguous()
+        sel = self._as_selector(sel)
+        if sel.ids is not None and sel.ids.numel() <= KNN_IDS_MAX:
+            return knn_topk_ids(self._store, self._n, self.d, q, k, sel.ids, metric=self.metric)
+        need = knn_workspace_bytes(self._n, self.d, q.shape[0], k)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+        return knn_topk_sel(self._store, self._n, self.d, q, k, sel, metric=self.metric, workspace=self._ws, stats=self._stats)
+
+    def search_device(self, q, k, sel=None):
+        """q: [nq, d] fp32 tensor (any device) -> (dist, ids) CUDA tensors; no host sync.  sel: a RowSelector, a bool mask
+        [ntotal] or row ids -- the k best AMONG those rows (`_search_sel`)."""
+        if sel is not None:
+            return self._search_sel(q, k, sel)
         self._materialize()
         q = q.detach().to(device=self.device, dtype=torch.float32)
         if q.dim() == 1:
@@ -457,10 +661,11 @@ class _HipFlatIndex:
         return search(self._store, self._n, self.d, q, k, workspace=self._ws, stats=self._stats,
                       prepared=self._prepared if batch else None)
 
-    def search(self, x, k):
-        """faiss signature: numpy in, (float32 [nq,k], int64 [nq,k]) numpy out."""
+    def search(self, x, k, sel=None):
+        """faiss signature: numpy in, (float32 [nq,k], int64 [nq,k]) numpy out.  sel (faiss: params=SearchParameters(sel=...)):
+        a RowSelector, a bool mask or row ids; fewer than k selected rows pad as faiss does."""
         q = self._as_rows(x)
-        D, I = self.search_device(q, int(k))
+        D, I = self.search_device(q, int(k)) if sel is None else self.search_device(q, int(k), sel)
         return D.cpu().numpy(), I.cpu().numpy()
 
     def range_search_device(self, q, radius, max_ws_bytes=256 << 20):

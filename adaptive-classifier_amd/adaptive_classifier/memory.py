@@ -403,6 +403,7 @@ class PrototypeMemory:
             self._dirty.clear()
             self._row_labels = None
             self._row_label_names = None
+            self._among_cache = None
             self.updates_since_rebuild = 0
 
     def _restore_from_save(self):
@@ -434,6 +435,7 @@ class PrototypeMemory:
         self._row_label_names = list(label_names)
         self._sharded = sharded
         self._row_class_cache = None
+        self._among_cache = None
         self.updates_since_rebuild = 0
         self._dirty.clear()
         if prepare and sharded is None:
@@ -443,17 +445,47 @@ class PrototypeMemory:
                 self.index._searches_since_change = 1
 
     # ------------------------------------------------------------------ search
+    def _among_selector(self, among):
+        """(RowSelector, selected rows) of the rows whose label is in `among` (unknown labels are ignored): the rows of
+        label_to_index for a one-prototype-per-class store (an id selector: the id-list route), `from_classes` over the row ->
+        class map for a load_rows() store.  Cached per label set; every rebuild / load_rows / clear drops the cache (the store
+        version the selector was built for)."""
+        from .index import RowSelector
+        key = frozenset(among)
+        cached = getattr(self, "_among_cache", None)
+        if cached is not None and cached[0] == key and cached[1].n == (
+                self.index.ntotal if self._row_labels is None else int(self._row_labels.numel())):
+            return cached[1], cached[2]
+        if self._row_labels is not None:
+            cls = [i for i, nm in enumerate(self._row_label_names) if nm in key]
+            sel = RowSelector.from_classes(self._row_labels, cls, len(self._row_label_names))
+            count = sel.count() if cls else 0               # (one host read per label set, then cached)
+        else:
+            ids = sorted(self.label_to_index[l] for l in key if l in self.label_to_index)
+            sel = RowSelector.from_ids(np.asarray(ids, dtype=np.int64), self.index.ntotal, device=self.index.device)
+            count = len(ids)
+        self._among_cache = (key, sel, count)
+        return sel, count
+
     def get_nearest_prototypes(self, query_embedding: torch.Tensor, k: int = 5,
-                               min_similarity: Optional[float] = None) -> List[Tuple[str, float]]:
-        """[(label, score)] ascending in distance; scores = softmax(exp(-d^2)) (memory.py:85-136)."""
+                               min_similarity: Optional[float] = None, among=None) -> List[Tuple[str, float]]:
+        """[(label, score)] ascending in distance; scores = softmax(exp(-d^2)) (memory.py:85-136).
+        among: an iterable of labels -- only their rows are searched (FILTERED search); unknown labels are ignored, an empty
+        set gives []; k is clamped to the number of selected rows, as the reference clamps it to ntotal."""
         with self._lock:
             if self._row_labels is None and self.updates_since_rebuild >= self.config.prototype_update_frequency:
                 self._rebuild_index()
             if self.index.ntotal == 0:
                 return []
             self._flush_dirty()
-            k = min(k, self.index.ntotal)
-            D, I = self.index.search_device(query_embedding.detach().reshape(1, -1), k)
+            if among is not None:
+                sel, count = self._among_selector(among)
+                if count == 0:
+                    return []
+                D, I = self.index.search_device(query_embedding.detach().reshape(1, -1), min(k, count), sel)
+            else:
+                k = min(k, self.index.ntotal)
+                D, I = self.index.search_device(query_embedding.detach().reshape(1, -1), k)
             S = proto_scores(D, I)
             ids = I[0].cpu().numpy()
             scores = S[0].cpu().numpy()
@@ -483,28 +515,34 @@ class PrototypeMemory:
             return self._row_label_names[int(self._row_labels[idx].item())]
         return self.index_to_label[idx]
 
-    def search_batch(self, queries: torch.Tensor, k: int):
+    def search_batch(self, queries: torch.Tensor, k: int, among=None):
         """Device-resident batch search: (scores [b,k], row ids [b,k], dist [b,k]) CUDA tensors.
 
-        Same arithmetic as get_nearest_prototypes per row; no host synchronisation."""
+        Same arithmetic as get_nearest_prototypes per row; no host synchronisation.  among: as get_nearest_prototypes, but the
+        shape stays [b, k]: rows beyond the selected ones are padding (id -1, score 0)."""
         with self._lock:
             if self._row_labels is None and self.updates_since_rebuild >= self.config.prototype_update_frequency:
                 self._rebuild_index()
             self._flush_dirty()
-            D, I = self._search_locked(queries, k)
+            D, I = self._search_locked(queries, k, among)
             return proto_scores(D, I), I, D
 
-    def search_raw(self, queries: torch.Tensor, k: int):
+    def search_raw(self, queries: torch.Tensor, k: int, among=None):
         """search_batch without the score kernel: (dist [b,k] f32, row ids [b,k] i64) on the device -- the inputs of
-        ac_predict_post, which derives the scores itself."""
+        ac_predict_post, which derives the scores itself.  among: as search_batch."""
         with self._lock:
             if self._row_labels is None and self.updates_since_rebuild >= self.config.prototype_update_frequency:
                 self._rebuild_index()
             self._flush_dirty()
-            return self._search_locked(queries, k)
+            return self._search_locked(queries, k, among)
 
-    def _search_locked(self, queries, k):
+    def _search_locked(self, queries, k, among=None):
         sharded = getattr(self, "_sharded", None)
+        if among is not None:
+            sel = self._among_selector(among)[0]
+            if sharded is not None and (sharded.world > 1 or sharded.force_collectives):
+                return sharded.search_block(queries, k, sel=sel)
+            return self.index.search_device(queries, min(k, max(self.index.ntotal, 1)), sel)
         if sharded is not None and (sharded.world > 1 or sharded.force_collectives):
             return sharded.search_block(queries, k)           # this rank's queries against every rank's row shard
         k = min(k, max(self.index.ntotal, 1))
@@ -563,6 +601,7 @@ class PrototypeMemory:
             self.index_to_label.clear()
             self._row_labels = None
             self._row_label_names = None
+            self._among_cache = None
             self.updates_since_rebuild = 0
 
     def drop_label(self, label):

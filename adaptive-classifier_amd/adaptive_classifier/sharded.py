@@ -180,10 +180,22 @@ class ShardedSearch:
             return g.reshape(-1, q_local.shape[-1])
         return torch.cat([g[r, :sizes[r]] for r in range(self.world)])
 
-    def search(self, queries, k):
+    def _local(self, Q, k, sel):
+        """this rank's shard searched for Q: (exact fp64 values, global ids).  sel: None, or the GLOBAL RowSelector (replicated
+        on every rank) -- the shard reads its slice of the bitmap in place (sel_bit0 = row_offset), over the fp32 rows."""
+        if sel is None:
+            return self._search(self.rows, self.n_local, self.dim, Q, k, self.row_offset)
+        from . import index as ix
+        ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
+        _, I = ix.knn_topk_sel(self.rows, self.n_local, self.dim, Q, k, sel, metric=self.metric, sel_bit0=self.row_offset,
+                               row_offset=self.row_offset, exact_out=ex)
+        return ex, I
+
+    def search(self, queries, k, sel=None):
         """queries [b, D] (identical on all ranks) -> global (dist fp32 [b,k], ids [b,k]) on EVERY rank.
-        The local search returns EXACT fp64 distances; they are what travels and what the merge orders by."""
-        D_loc, I_loc = self._search(self.rows, self.n_local, self.dim, queries, k, self.row_offset)
+        The local search returns EXACT fp64 distances; they are what travels and what the merge orders by.
+        sel: the global RowSelector (FILTERED search, `_local`)."""
+        D_loc, I_loc = self._local(queries, k, sel)
         if not self._collective:
             return D_loc.to(torch.float32), I_loc
         both = self._all_gather(_pack(D_loc, I_loc))            # ONE message per peer: fp64 bits and ids side by side
@@ -268,18 +280,21 @@ class ShardedSearch:
             cur = ahead
         yield self._search_block_fixed(None, k, gathered=cur)
 
-    def search_block(self, q_local, k, block_sizes=None, gathered=None):
+    def search_block(self, q_local, k, block_sizes=None, gathered=None, sel=None):
         """The data-parallel step: this rank's query block [m, D] -> the global (dist fp32 [m, k], ids [m, k]) of THOSE
         queries.  all_gather(queries) -> local search of all of them -> all_to_all of the candidate lists -> this rank
         merges only its own block.  With `block_rows` (constructor) this is the fixed-batch path: blocks padded to block_rows,
         pre-allocated messages, nothing read back to the host; `gathered` = a handle of prefetch_queries() for this block.
         Otherwise -- block_sizes: every rank's m when the caller knows them (validated against this rank's
         block; a wrong list raises here instead of hanging in the collective); None = the ranks exchange their sizes first
-        (one extra 8-byte all_gather).  Sizes may differ and may be 0."""
+        (one extra 8-byte all_gather).  Sizes may differ and may be 0.
+        sel: the global RowSelector (FILTERED search, `_local`); not available on the fixed-batch path."""
+        if sel is not None and self.block_rows is not None:
+            raise ValueError("the fixed-batch path (block_rows) has no filtered search: construct without block_rows to pass sel")
         if self.block_rows is not None and block_sizes is None:
             return self._search_block_fixed(q_local, k, gathered)     # fixed shapes: no size exchange, no host read-back
         if not self._collective:
-            D_loc, I_loc = self._search(self.rows, self.n_local, self.dim, q_local, k, self.row_offset)
+            D_loc, I_loc = self._local(q_local, k, sel)
             return D_loc.to(torch.float32), I_loc
         G, m = self.world, q_local.shape[0]
         sizes = self._check_sizes(self.block_sizes(m) if block_sizes is None else block_sizes, m)
@@ -288,7 +303,7 @@ class ShardedSearch:
         if total == 0:
             return torch.empty((0, k), dtype=torch.float32, device=dev), torch.empty((0, k), dtype=torch.int64, device=dev)
         q_all = self.gather_queries(q_local, sizes)
-        D_loc, I_loc = self._search(self.rows, self.n_local, self.dim, q_all, k, self.row_offset)
+        D_loc, I_loc = self._local(q_all, k, sel)
         both = _pack(D_loc, I_loc)                                 # [total, 2k] int64: one message per peer
         if all(x == m for x in sizes):
             both = self._all_to_all(both.reshape(G, m, both.shape[1]))   # -> [shard, own query, 2k]

@@ -334,6 +334,15 @@ struct MergeParams {
     // four radix rounds, and the bound is tighter than tau - |q|^2 + E (no error term: both sides are sweep values).
     int thr_only = 0;
 };
+// FILTERED search (acamd.h): the selection, a SECOND kernel argument of the *_sel / *_ids kernels.  (Not fields of MergeParams:
+// the plain kernels take scalars behind the struct, whose kernarg offsets -- and the loads that read them -- would move.)
+struct SelArgs {
+    const uint64_t* sel = nullptr;   // bitmap: local row r is a candidate iff bit (sel_bit0 + r) is set
+    int64_t sel_bit0 = 0;
+    const int64_t* ids = nullptr;    // id-list route (knn_small_exact_ids): n_ids sorted, unique row ids; ids outside [0, N) are skipped
+    int64_t n_ids = 0;
+    int by_ids = 0;                  // host side: 1 = the id-list kernel
+};
 constexpr int kKnnSmallN = 8192;                    // rows the small-store search covers
 struct WsTake {                                      // running-offset workspace allocator (256-byte granules)
     size_t off = 0;
@@ -349,10 +358,11 @@ MergeParams knn_merge_params(const float* P, int64_t N, int64_t ldP, const float
                              int64_t row_offset, float* outD, double* outD64, int64_t* outI, int32_t* stats, char* ws,
                              const ExactPlan& ep);
 // ip: the inner-product instantiations.  attr_lds: dynamic-LDS opt-in to set first (0 = the caller's earlier launch did)
-int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream);
+int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream, const SelArgs* sel = nullptr);
 // merge / re-rank, then (N > 0) exact fallback + fallback merge; merge_lds = this launch's share of ep.merge_lds
-int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream);
-int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream);
+// sel != NULL (both below): the FILTERED forms of the kernels
+int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream, const SelArgs* sel = nullptr);
+int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream, const SelArgs* sel = nullptr);
 
 // Per-call options (ac_bert_config.gemm_arith_opt / ln_fusion_opt / one_launch_opt): for the duration of ONE native call on the
 // calling thread they take precedence over the process-wide switches (ac_gemm_set_arith, ac_gemm_set_ln_fusion,

@@ -21,6 +21,7 @@
 namespace {
 
 using ac::MergeParams;
+using ac::SelArgs;
 using ac::fkey;
 using ac::fkey_inv;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -50,6 +51,13 @@ __device__ __forceinline__ void emit_hit(const MergeParams& prm, size_t at, bool
     prm.outD[at] = real ? (float)v : (IP ? -FLT_MAX : FLT_MAX);
     if (prm.outD64) prm.outD64[at] = real ? v : (IP ? -(double)INFINITY : (double)INFINITY);
     prm.outI[at] = real ? id + prm.row_offset : -1;
+}
+
+// FILTERED search (acamd.h): SEL = true instantiations of the bodies below are the kernels *_sel; the plain kernels
+// instantiate SEL = false, which compiles every selection statement away.
+__device__ __forceinline__ bool row_selected(const SelArgs& sa, int64_t row) {
+    const int64_t b = sa.sel_bit0 + row;
+    return (sa.sel[b >> 6] >> (b & 63)) & 1ull;
 }
 
 constexpr int kMergeThreads = 256;
@@ -104,7 +112,7 @@ __device__ __forceinline__ uint32_t block_radix_select(int n, int want, KeyFn ke
 
 // (Each kernel below is a thin `template <bool IP> __global__` wrapper around a force-inlined body that takes the parameters by
 //  reference: written straight into the kernel, hipcc schedules the same code differently.)
-template <bool IP>
+template <bool IP, bool SEL = false>
 __device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, char* smem) {
     const int q = blockIdx.x;
     const int tid = threadIdx.x;
@@ -340,6 +348,10 @@ __device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, ch
                 ok = (ns >= kout) && (kth < a_last - E + qn2) && !overflow;
             }
             if (prm.cand_cnt && nreal < kp) ok = 0;      // fewer than k' candidates kept: the "unseen rows >= a_last" premise is gone
+            // FILTERED search over the per-block lists: a block that ever pruned keeps exactly k' entries, so fewer than k' real
+            // entries IN TOTAL mean that no block pruned -- every list still holds every selected row of its block (tau stayed
+            // +inf), all of them were re-ranked above, and the result is complete however few they are (padding included).
+            if constexpr (SEL) { if (!prm.cand_cnt && nreal < kp && !overflow) ok = 1; }
         }
         int flag = 0;
         if (!ok) {
@@ -354,6 +366,11 @@ template <bool IP>
 __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank(MergeParams prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     knn_merge_rerank_body<IP>(prm, smem);
+}
+template <bool IP>
+__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank_sel(MergeParams prm) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_merge_rerank_body<IP, true>(prm, smem);
 }
 
 // --------------------------------------------------------------------------------------
@@ -372,8 +389,8 @@ constexpr int kFbRound = 32;          // rows per wave between barriers
 //  no query flagged -- every call of an ordinary batch -- dispatching fb_S x nq = 16 384 empty 512-thread blocks cost 8.5 us;
 //  fb_S x 8 cost 2.  A device holds <= ~1000 of these blocks at once, so flagged batches lose nothing.)
 constexpr int kFbQueryGroups = 8, kFbMergeGroups = 32;
-template <bool IP>
-__device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm, const int q, const int slab, char* smem) {
+template <bool IP, bool SEL = false>
+__device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm, const int q, const int slab, char* smem, const SelArgs* sa = nullptr) {
     const int flag = prm.flags[q];
     if (flag == 0 || (flag < 0 && slab != 0)) return;
     const bool direct = flag < 0;
@@ -428,6 +445,7 @@ __device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm,
         for (int m = 0; m < kFbRound; ++m) {
             const int64_t row = base + (int64_t)m * kFbWaves + wave;
             if (row >= row_hi) break;
+            if constexpr (SEL) { if (!row_selected(*sa, row)) continue; }      // (wave-uniform: a wave scans one row)
             const f32x4* prow = reinterpret_cast<const f32x4*>(prm.P + (size_t)row * prm.ldP);
             double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
             for (int c4 = lane; c4 < nc4; c4 += 64) {
@@ -468,6 +486,14 @@ __global__ __launch_bounds__(kFbThreads) void knn_exact_fallback(MergeParams prm
     for (int q = blockIdx.y; q < nq; q += gridDim.y) {
         knn_exact_fallback_query<IP>(prm, q, blockIdx.x, smem);
         __syncthreads();                                            // (the next query reuses the lists)
+    }
+}
+template <bool IP>
+__global__ __launch_bounds__(kFbThreads) void knn_exact_fallback_sel(MergeParams prm, int nq, SelArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    for (int q = blockIdx.y; q < nq; q += gridDim.y) {
+        knn_exact_fallback_query<IP, true>(prm, q, blockIdx.x, smem, &sa);
+        __syncthreads();
     }
 }
 
@@ -590,16 +616,26 @@ __global__ __launch_bounds__(256) void rows_to_class_kernel(const int64_t* I, in
 // --------------------------------------------------------------------------------------
 constexpr int kSmallThreads = 256;
 
-template <bool IP>
-__device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int npow2, char* smem) {
+// MODE 0: every row of the store.  FILTERED search -- MODE 1: the rows whose selection bit is set; MODE 2 (id-list route,
+// ac_knn_*_topk_ids): entry r of the sort is row ids[r] of the store (n_ids sorted, unique ids; an id outside [0, N) is skipped)
+// and ids[r] is what is emitted.  A skipped entry is padding: (+inf, 0x7fffffff) sorts last.
+template <bool IP, int MODE = 0>
+__device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int npow2, char* smem, const SelArgs* sa = nullptr) {
     double* ds = reinterpret_cast<double*>(smem);                // [npow2]
     int32_t* is = reinterpret_cast<int32_t*>(ds + npow2);        // [npow2]
     const int q = blockIdx.x, tid = threadIdx.x;
     const float* qv = prm.Q + (size_t)q * prm.ldQ;
     for (int r = tid; r < npow2; r += kSmallThreads) {
         double a = INFINITY;
-        if (r < prm.N) {
-            const float* p = prm.P + (size_t)r * prm.ldP;
+        int64_t row = r;
+        bool have = r < prm.N;
+        if constexpr (MODE == 1) have = have && row_selected(*sa, r);
+        if constexpr (MODE == 2) {
+            have = r < sa->n_ids;
+            if (have) { row = sa->ids[r]; have = row >= 0 && row < prm.N; }
+        }
+        if (MODE == 0 ? r < prm.N : have) {
+            const float* p = prm.P + (size_t)(MODE == 2 ? row : (int64_t)r) * prm.ldP;
             double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
             int c = 0;
             for (; c + 3 < prm.D; c += 4) {
@@ -611,7 +647,8 @@ __device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int
             if (IP) a = -a;                                      // (inner product: the key -(p.q))
         }
         ds[r] = a;
-        is[r] = r < prm.N ? r : 0x7fffffff;
+        if constexpr (MODE == 0) is[r] = r < prm.N ? r : 0x7fffffff;
+        else is[r] = have ? (int32_t)row : 0x7fffffff;
     }
     __syncthreads();
     for (int size = 2; size <= npow2; size <<= 1)
@@ -628,7 +665,8 @@ __device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int
             __syncthreads();
         }
     for (int t = tid; t < prm.k; t += kSmallThreads) {
-        const bool real = t < prm.N;                             // (k may exceed npow2: the lists are read for real hits only)
+        bool real = t < prm.N;                                   // (k may exceed npow2: the lists are read for real hits only)
+        if constexpr (MODE != 0) real = t < npow2 && is[t < npow2 ? t : 0] != 0x7fffffff;
         emit_hit<IP>(prm, (size_t)q * prm.k + t, real, real ? ds[t] : 0.0, real ? (int64_t)is[t] : -1);
     }
 }
@@ -636,6 +674,16 @@ template <bool IP>
 __global__ __launch_bounds__(kSmallThreads) void knn_small_exact(MergeParams prm, int npow2) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     knn_small_exact_body<IP>(prm, npow2, smem);
+}
+template <bool IP>
+__global__ __launch_bounds__(kSmallThreads) void knn_small_exact_sel(MergeParams prm, int npow2, SelArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_small_exact_body<IP, 1>(prm, npow2, smem, &sa);
+}
+template <bool IP>
+__global__ __launch_bounds__(kSmallThreads) void knn_small_exact_ids(MergeParams prm, int npow2, SelArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_small_exact_body<IP, 2>(prm, npow2, smem, &sa);
 }
 
 }  // namespace
@@ -674,20 +722,28 @@ MergeParams knn_merge_params(const float* P, int64_t N, int64_t ldP, const float
 }
 
 // (function attributes are set per call: they are per device, and a cached flag is not)
-int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream) {
+int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream, const SelArgs* sel) {
     void (*fn)(MergeParams) = ip ? knn_merge_rerank<true> : knn_merge_rerank<false>;
+    if (sel) fn = ip ? knn_merge_rerank_sel<true> : knn_merge_rerank_sel<false>;         // FILTERED search: one more certificate rule
     if (attr_lds) AC_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds));
     hipLaunchKernelGGL(fn, dim3(nq), dim3(kMergeThreads), lds, stream, mp);
     AC_LAUNCH_CHECK();
     return AC_OK;
 }
 
-int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream) {
-    const int rc = knn_merge_launch(ip, mp, nq, ep.merge_lds, merge_lds, stream);
+int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream, const SelArgs* sel) {
+    const int rc = knn_merge_launch(ip, mp, nq, ep.merge_lds, merge_lds, stream, sel);
     if (rc != AC_OK || mp.N == 0) return rc;          // (an empty store: everything is padding, nothing can be flagged)
+    const dim3 fb_grid(ep.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups);
+    if (sel) {                                        // FILTERED search: the fallback scans the selected rows only
+        void (*fbs_fn)(MergeParams, int, SelArgs) = ip ? knn_exact_fallback_sel<true> : knn_exact_fallback_sel<false>;
+        (void)hipFuncSetAttribute((const void*)fbs_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ep.fb_lds);
+        hipLaunchKernelGGL(fbs_fn, fb_grid, dim3(kFbThreads), ep.fb_lds, stream, mp, nq, *sel);
+    } else {
     void (*fb_fn)(MergeParams, int) = ip ? knn_exact_fallback<true> : knn_exact_fallback<false>;
     (void)hipFuncSetAttribute((const void*)fb_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ep.fb_lds);
-    hipLaunchKernelGGL(fb_fn, dim3(ep.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups), dim3(kFbThreads), ep.fb_lds, stream, mp, nq);
+    hipLaunchKernelGGL(fb_fn, fb_grid, dim3(kFbThreads), ep.fb_lds, stream, mp, nq);
+    }
     AC_LAUNCH_CHECK();
     const int np2 = next_pow2(ep.fb_S * mp.k > 2 ? ep.fb_S * mp.k : 2);
     void (*fbm_fn)(MergeParams, int, int) = ip ? knn_exact_fb_merge<true> : knn_exact_fb_merge<false>;
@@ -697,8 +753,17 @@ int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, 
     return AC_OK;
 }
 
-int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream) {
+int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream, const SelArgs* sel) {
     const size_t lds = (size_t)npow2 * 12;
+    if (sel) {                                        // FILTERED search: the id-list kernel or the bitmap kernel
+        void (*sfn)(MergeParams, int, SelArgs);
+        if (sel->by_ids) sfn = ip ? knn_small_exact_ids<true> : knn_small_exact_ids<false>;
+        else sfn = ip ? knn_small_exact_sel<true> : knn_small_exact_sel<false>;
+        (void)hipFuncSetAttribute((const void*)sfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(sfn, dim3(nq), dim3(kSmallThreads), lds, stream, mp, npow2, *sel);
+        AC_LAUNCH_CHECK();
+        return AC_OK;
+    }
     void (*fn)(MergeParams, int) = ip ? knn_small_exact<true> : knn_small_exact<false>;
     (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(fn, dim3(nq), dim3(kSmallThreads), lds, stream, mp, npow2);

@@ -89,6 +89,38 @@ struct SweepParams {
     int32_t* clear_ctr;   // [64] the merge / fallback kernels' slot counter and ...
     int32_t* clear_stats; // [4] the caller's d_stats (or NULL): zeroed by workgroup 0 here instead of by two memset launches
 };
+// FILTERED search (the SEL instantiations take this struct; the plain ones keep SweepParams, so that their kernarg segment -- the
+// hidden arguments behind it included -- stays where it was): row r is a candidate iff bit (sel_bit0 + r) of the bitmap is set
+// (acamd.h "FILTERED search")
+struct SweepParamsSel : SweepParams {
+    const uint64_t* sel;
+    int64_t sel_bit0;
+};
+template <bool SEL> struct sweep_params { typedef SweepParams type; };
+template <> struct sweep_params<true> { typedef SweepParamsSel type; };
+
+// The 16 selection bits of a wave's tile (rows row_base .. row_base + 15, bit i = row row_base + i): they sit in at most two
+// 64-bit words, fetched wave-uniformly through the SCALAR unit (constant address space, as knn_plane_sweep's norms: off the
+// vmcnt queue the prefetched rows / the DMA ring sit in).  Bits of rows >= N are never read as rows: the second word is touched
+// only if one of its rows exists, a tile past N reads nothing, and the callers test row < N besides.
+__device__ __forceinline__ uint32_t sweep_sel_bits(const uint64_t* sel, int64_t sel_bit0, int64_t N, int64_t row_base) {
+    if (row_base >= N) return 0u;
+    typedef const uint64_t __attribute__((address_space(4)))* cup;
+    const uint32_t rem = __builtin_amdgcn_readfirstlane((uint32_t)((sel_bit0 & 63) + row_base));     // (N < 2^31)
+    const cup w = (cup)(uintptr_t)(sel + (sel_bit0 >> 6) + (rem >> 6));
+    const int s = (int)(rem & 63u);
+    uint64_t bits = w[0] >> s;
+    if (s > 48 && row_base + (64 - s) < N) bits |= w[1] << (64 - s);
+    return (uint32_t)bits & 0xffffu;
+}
+// an unselected row's sweep value becomes +inf BEFORE the `acc < tau` test: it is never pushed, so lists, pruning and tau see
+// exactly the selected rows
+template <int NACC>
+__device__ __forceinline__ void sweep_sel_apply(f32x4& acc, uint32_t bits, int lane) {
+#pragma unroll
+    for (int r = 0; r < NACC; ++r)
+        if (!((bits >> Shape::acc_row(r, lane)) & 1u)) acc[r] = INFINITY;
+}
 
 // XCD-aware block id remap (cdna guide T1, bijective form): hardware places block b on XCD
 // b % 8; give each XCD a contiguous range of virtual ids so that the nqt query-tile blocks
@@ -181,8 +213,11 @@ __device__ __forceinline__ void prune_dispatch(float* ld, int32_t* li, int* cnt_
 // by -2 either way, so "smaller is better" still holds and the lists, prune_list and tau are untouched: they order by `<` on
 // floats and by fkey, which is monotone over negative values too, and the padding sentinel +inf stays the largest key.  Only the
 // |p|^2 fold of the epilogue goes; the running sum of squares stays, because the certificate needs the largest row norm.
-template <int J, bool IP = false>
-__global__ __launch_bounds__(kThreads, 2) void knn_sweep(SweepParams prm) {
+// SEL = true is the FILTERED form (ac_knn_*_topk_sel): rows whose selection bit is clear are taken out in the epilogue.
+// (Its 16-query form is held to 128 VGPRs -- 4 waves per SIMD, two blocks per CU, the residency the planner sizes the grid for from
+// knn_sweep<1>: left at the bound 2 the L2 instantiation took 129.)
+template <int J, bool IP = false, bool SEL = false>
+__global__ __launch_bounds__(kThreads, (SEL && J == 1) ? 4 : 2) void knn_sweep(typename sweep_params<SEL>::type prm) {
     typedef Shape S;
     typedef S::acc_t acc_t;
     static_assert(J == 1 || J == 2, "query tile = 1 or 2 sub-tiles of 16 (LDS budget; tau[] reload below)");
@@ -296,6 +331,11 @@ __global__ __launch_bounds__(kThreads, 2) void knn_sweep(SweepParams prm) {
         wave_maxnorm = fmaxf(wave_maxnorm, rn);
 
         const int64_t row_base = (cur_tile * prm.G + g) * (int64_t)(kWaves * S::ROWS) + wave * S::ROWS;
+        if constexpr (SEL) {
+            const uint32_t sbits = sweep_sel_bits(prm.sel, prm.sel_bit0, prm.N, row_base);
+#pragma unroll
+            for (int jj = 0; jj < J; ++jj) sweep_sel_apply<S::NACC>(acc[jj], sbits, lane);
+        }
         bool maybe = false;
 #pragma unroll
         for (int jj = 0; jj < J; ++jj)
@@ -436,8 +476,10 @@ constexpr int ring_qs_bytes(int maxch) { return (maxch - ring_reg_chunks(maxch))
 
 template <int N> __device__ __forceinline__ void sweep_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <int RINGC, int MAXCH, bool IP = false>
-__global__ __launch_bounds__(kThreads, 2) void knn_sweep_ring(SweepParams prm) {
+// SEL = true: the FILTERED form, as knn_sweep's (the selection word comes through the scalar unit, so the counted vmcnt waits
+// of the DMA ring are untouched).
+template <int RINGC, int MAXCH, bool IP = false, bool SEL = false>
+__global__ __launch_bounds__(kThreads, 2) void knn_sweep_ring(typename sweep_params<SEL>::type prm) {
     constexpr int kRingMaxChunks = MAXCH, kRingRegChunks = ring_reg_chunks(MAXCH), kRingQsBytes = ring_qs_bytes(MAXCH);
     typedef Shape S;
     typedef S::acc_t acc_t;
@@ -535,6 +577,7 @@ __global__ __launch_bounds__(kThreads, 2) void knn_sweep_ring(SweepParams prm) {
         wave_maxnorm = fmaxf(wave_maxnorm, rn);
 
         const int64_t row_base = (cur_tile * prm.G + g) * (int64_t)(kWaves * S::ROWS) + wave * S::ROWS;
+        if constexpr (SEL) sweep_sel_apply<S::NACC>(acc[0], sweep_sel_bits(prm.sel, prm.sel_bit0, prm.N, row_base), lane);
         bool maybe = false;
 #pragma unroll
         for (int r = 0; r < S::NACC; ++r) maybe |= (acc[0][r] < tau[0]);
@@ -1027,9 +1070,12 @@ extern "C" int ac_knn_l2_topk(const float* d_P, int64_t N, int64_t ldP, int D, c
 
 // the fp32-sweep search of both metrics: ip = false squared L2 (ac_knn_l2_topk_x), true inner product (ac_knn_ip_topk_x).  One
 // plan, one workspace layout and one launch sequence; the metric only picks the instantiation of each kernel.
+// d_sel != NULL: the FILTERED search (ac_knn_*_topk_sel) -- the same plan, workspace and launch sequence with the SEL
+// instantiation of the sweep and of the exact stages.
 static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
                     int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64,
-                    int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+                    int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_,
+                    const uint64_t* d_sel = nullptr, int64_t sel_bit0 = 0) {
     hipStream_t stream = (hipStream_t)stream_;
     Plan pl;
     int rc = make_plan(N, D, nq, k, &pl);
@@ -1046,12 +1092,14 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
         AC_REQUIRE((((uintptr_t)d_P) & 15) == 0, AC_EINVAL, "knn: d_P must be 16-byte aligned");
     }
     char* ws = (char*)d_ws;
+    ac::SelArgs sa;
+    sa.sel = d_sel; sa.sel_bit0 = sel_bit0;
     if (d_stats && (pl.small || N == 0)) AC_HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(int32_t), stream));
     if (pl.small) {
         MergeParams sp;
         sp.P = d_P; sp.N = N; sp.ldP = ldP; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.k = k; sp.row_offset = row_offset;
         sp.outD = d_outD; sp.outD64 = d_outD64; sp.outI = d_outI;
-        return ac::knn_small_exact_launch(ip, sp, nq, pl.small_pow2, stream);
+        return ac::knn_small_exact_launch(ip, sp, nq, pl.small_pow2, stream, d_sel ? &sa : nullptr);
     }
 
     MergeParams mp = ac::knn_merge_params(d_P, N, ldP, d_Q, ldQ, D, pl.Dp, k, pl.kp, row_offset, d_outD, d_outD64, d_outI, d_stats, ws, pl.ex);
@@ -1067,7 +1115,7 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
         AC_HIP_CHECK(hipMemsetAsync(ws + pl.off_part_i, 0xff, (size_t)pl.nqt * pl.TQ * pl.G * pl.kp * 4, stream));
         AC_HIP_CHECK(hipMemsetAsync(ws + pl.off_maxnorm, 0, (size_t)pl.G * pl.nqt * 4, stream));
     } else {
-        SweepParams sp{};
+        SweepParamsSel sp{};                          // (the plain kernels take its SweepParams base)
         sp.P = d_P; sp.N = N; sp.ldP = ldP; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.Dp = pl.Dp;
         sp.ng = pl.ng; sp.nq = nq; sp.kp = pl.kp; sp.cap = pl.cap; sp.G = pl.G; sp.nqt = pl.nqt;
         sp.ntiles = pl.ntiles;
@@ -1077,23 +1125,36 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
         sp.zeros = zeros_device();                    // a zero-initialised __device__ array: no memset launch per call
         sp.clear_ctr = (int32_t*)(ws + pl.ex.off_fb_ctr);
         sp.clear_stats = d_stats;
+        sp.sel = d_sel; sp.sel_bit0 = sel_bit0;
         const int nblk = pl.G * pl.nqt;
         if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
-        void (*sweep_fn)(SweepParams);
+        void (*sweep_fn)(SweepParams) = nullptr;
+        void (*sweep_sel_fn)(SweepParamsSel) = nullptr;      // FILTERED search: the SEL instantiation of the same sweep
         if (pl.ring) {
-            if (D <= 768) sweep_fn = ip ? knn_sweep_ring<4, 24, true> : knn_sweep_ring<4, 24, false>;
+            if (d_sel) {
+                if (D <= 768) sweep_sel_fn = ip ? knn_sweep_ring<4, 24, true, true> : knn_sweep_ring<4, 24, false, true>;
+                else sweep_sel_fn = ip ? knn_sweep_ring<4, 32, true, true> : knn_sweep_ring<4, 32, false, true>;
+            } else if (D <= 768) sweep_fn = ip ? knn_sweep_ring<4, 24, true> : knn_sweep_ring<4, 24, false>;
             else sweep_fn = ip ? knn_sweep_ring<4, 32, true> : knn_sweep_ring<4, 32, false>;
-            AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
+            AC_HIP_CHECK(hipFuncSetAttribute(d_sel ? (const void*)sweep_sel_fn : (const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
         } else {
-            if (pl.TQ == 32) sweep_fn = ip ? knn_sweep<2, true> : knn_sweep<2, false>;
+            if (d_sel) {
+                if (pl.TQ == 32) sweep_sel_fn = ip ? knn_sweep<2, true, true> : knn_sweep<2, false, true>;
+                else sweep_sel_fn = ip ? knn_sweep<1, true, true> : knn_sweep<1, false, true>;
+            } else if (pl.TQ == 32) sweep_fn = ip ? knn_sweep<2, true> : knn_sweep<2, false>;
             else sweep_fn = ip ? knn_sweep<1, true> : knn_sweep<1, false>;
-            (void)hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds);
+            (void)hipFuncSetAttribute(d_sel ? (const void*)sweep_sel_fn : (const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds);
         }
-        hipLaunchKernelGGL(sweep_fn, dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
+        if (d_sel) {
+            hipLaunchKernelGGL(sweep_sel_fn, dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, sp);
+        } else {
+            const SweepParams base = sp;
+            hipLaunchKernelGGL(sweep_fn, dim3(nblk), dim3(kThreads), pl.sweep_lds, stream, base);
+        }
         AC_LAUNCH_CHECK();
         if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
     }
-    return ac::knn_exact_tail(ip, mp, pl.ex, nq, pl.ex.merge_lds, stream);
+    return ac::knn_exact_tail(ip, mp, pl.ex, nq, pl.ex.merge_lds, stream, d_sel && N > 0 ? &sa : nullptr);
 }
 
 extern "C" int ac_knn_l2_topk_x(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q,
@@ -1120,6 +1181,65 @@ extern "C" int ac_knn_ip_topk_x(const float* d_P, int64_t N, int64_t ldP, int D,
                                 int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
                                 ac_stream_t stream_) {
     return knn_topk(true, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes, d_stats, stream_);
+}
+
+// FILTERED search (acamd.h "FILTERED search"): the k best rows AMONG the selected ones.  The argument checks return before any
+// HIP call; the search itself is knn_topk with the selection (same plan, same workspace as ac_knn_l2_topk_workspace).
+static int knn_topk_sel(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ, int k,
+                        int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0, float* d_outD, double* d_outD64,
+                        int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+    AC_REQUIRE(sel_bit0 >= 0, AC_EINVAL, "knn sel: sel_bit0=%lld must be >= 0", (long long)sel_bit0);
+    AC_REQUIRE(d_sel != nullptr || N <= 0, AC_EINVAL, "knn sel: d_sel is NULL");
+    AC_REQUIRE((((uintptr_t)d_sel) & 7) == 0, AC_EINVAL, "knn sel: d_sel must be 8-byte aligned");
+    return knn_topk(ip, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes, d_stats, stream_,
+                    N > 0 ? d_sel : nullptr, sel_bit0);
+}
+
+extern "C" int ac_knn_l2_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ, int k,
+                                  int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0, float* d_outD, double* d_outD64,
+                                  int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+    return knn_topk_sel(false, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_sel, sel_bit0, d_outD, d_outD64, d_outI, d_ws, ws_bytes,
+                        d_stats, stream_);
+}
+
+extern "C" int ac_knn_ip_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ, int k,
+                                  int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0, float* d_outD, double* d_outD64,
+                                  int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+    return knn_topk_sel(true, d_P, N, ldP, D, d_Q, nq, ldQ, k, row_offset, d_sel, sel_bit0, d_outD, d_outD64, d_outI, d_ws, ws_bytes,
+                        d_stats, stream_);
+}
+
+// Id-list route: the k best among M listed rows (sorted, unique ids), for sparse selections -- the small-store sort with one
+// indirection, exact by construction, no workspace.
+static int knn_topk_ids(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q,
+                        int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64, int64_t* d_outI,
+                        ac_stream_t stream_) {
+    AC_REQUIRE(M >= 0 && M <= ac::kKnnSmallN, AC_EINVAL, "knn ids: M=%lld outside [0, %d]", (long long)M, ac::kKnnSmallN);
+    AC_REQUIRE(d_ids != nullptr || M == 0, AC_EINVAL, "knn ids: d_ids is NULL");
+    AC_REQUIRE(N >= 0 && N < 2147483647LL, AC_EINVAL, "knn ids: N=%lld out of range", (long long)N);
+    AC_REQUIRE(D >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "knn ids: bad D=%d nq=%d k=%d", D, nq, k);
+    if (nq == 0) return AC_OK;
+    AC_REQUIRE(d_Q && d_outD && d_outI, AC_EINVAL, "knn ids: null pointer");
+    AC_REQUIRE(ldQ >= D && ldP >= D, AC_EINVAL, "knn ids: ldQ=%lld / ldP=%lld < D=%d", (long long)ldQ, (long long)ldP, D);
+    AC_REQUIRE(d_P != nullptr || N == 0 || M == 0, AC_EINVAL, "knn ids: d_P is NULL");
+    MergeParams sp;
+    sp.P = d_P; sp.N = N; sp.ldP = ldP; sp.Q = d_Q; sp.ldQ = ldQ; sp.D = D; sp.k = k; sp.row_offset = row_offset;
+    sp.outD = d_outD; sp.outD64 = d_outD64; sp.outI = d_outI;
+    ac::SelArgs sa;
+    sa.ids = d_ids; sa.n_ids = M; sa.by_ids = 1;
+    return ac::knn_small_exact_launch(ip, sp, nq, next_pow2((int)(M > 2 ? M : 2)), (hipStream_t)stream_, &sa);
+}
+
+extern "C" int ac_knn_l2_topk_ids(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q,
+                                  int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64, int64_t* d_outI,
+                                  ac_stream_t stream_) {
+    return knn_topk_ids(false, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, stream_);
+}
+
+extern "C" int ac_knn_ip_topk_ids(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q,
+                                  int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64, int64_t* d_outI,
+                                  ac_stream_t stream_) {
+    return knn_topk_ids(true, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, stream_);
 }
 
 // ---------------------------------------------------------------------------------------------------------

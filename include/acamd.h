@@ -278,6 +278,67 @@ int ac_knn_ip_range_fill(const float* d_P, int64_t N, int64_t ldP, int D,
                          ac_stream_t stream);
 
 /*
+ * FILTERED search (row selectors): "the k best rows AMONG these rows" -- faiss IndexFlat.search(x, k,
+ * params=SearchParameters(sel=IDSelectorBitmap / IDSelectorBatch / IDSelectorRange)).  No reference call site.
+ *
+ * A SELECTION is a device bitmap of 64-bit words, (d_sel, sel_bit0): local row r (0 <= r < N) is selected iff bit
+ * (sel_bit0 + r) % 64 of word (sel_bit0 + r) / 64 is set, bit 0 the least significant -- on this little-endian target byte for
+ * byte faiss's IDSelectorBitmap layout.  d_sel is 8-byte aligned and holds at least ceil((sel_bit0 + N) / 64) words; bits outside
+ * [sel_bit0, sel_bit0 + N) are never read as rows.  sel_bit0 lets the row shard at row_offset use its slice of a replicated
+ * global bitmap as it is (sel_bit0 = row_offset): nothing is re-packed.
+ *
+ * Result contract: exactly what ac_knn_*_topk_x returns on a store that holds only the selected rows, with the ORIGINAL row ids
+ * -- the k best selected rows by the exact fp64 value rounded once to fp32, ascending (L2) / descending (IP), ties to the lower
+ * row id, fewer than k selected rows padded with (FLT_MAX, -1) / (-FLT_MAX, -1) (d_outD64: +inf / -inf); d_outD64 and
+ * row_offset as in ac_knn_l2_topk_x.  An all-ones selection returns the bits of the unfiltered call.
+ *
+ *   ac_knn_l2_topk_sel / ac_knn_ip_topk_sel   the arguments of ac_knn_*_topk_x plus (d_sel, sel_bit0) after row_offset.  The
+ *       workspace is the one ac_knn_l2_topk_workspace(N, D, nq, k) returns -- the SAME plan drives both -- and d_stats has the same
+ *       meaning ([0] = queries that took the exact fp64 fallback, which scans the selected rows only).  Mechanism: the fp32 sweeps
+ *       with a selection flag (an unselected row's sweep value becomes +inf before it is compared with the running threshold), the
+ *       same merge / fp64 re-rank, and one more certificate rule: fewer than k' = k + 8 real candidates IN TOTAL means that no
+ *       sweep block ever pruned its list (a pruned list keeps exactly k'), so every selected row was re-ranked and the result is
+ *       complete -- a selection of fewer than k rows is certified, not sent to the fallback (profiles/knn_select/README.md).
+ *   ac_knn_l2_topk_ids / ac_knn_ip_topk_ids   the id-list route for SPARSE selections: d_ids = M sorted, unique int64 row ids,
+ *       M <= 8192; ids outside [0, N) are skipped on the device.  fp64 values of the listed rows only, sorted by (value, id): exact
+ *       by construction, any k and any D, no workspace, M * D * 4 bytes read per query instead of a sweep of the store.
+ *   ac_knn_sel_pack      d_sel bit r = (d_mask[r] != 0), r < n                                   (uint8 / bool mask -> bitmap)
+ *   ac_knn_sel_classes   d_sel bit r = d_class_on[d_row_class[r]] != 0; a class outside [0, n_classes) gives 0
+ *       Both write the ceil(n / 64) words of d_sel (8-byte aligned), every word by exactly one wave (ballot + one ordinary store,
+ *       no atomics), the tail bits past n as 0 and nothing past the last word.  Asynchronous, no host synchronisation.
+ * AC_EINVAL, before any device work, names the argument: d_sel NULL with N > 0, d_sel not 8-byte aligned, sel_bit0 < 0,
+ * M < 0 or M > 8192.  Everything else (ldP / ldQ / alignment of d_P, AC_EWORKSPACE, supported (N, D, k)) as ac_knn_l2_topk_x.
+ * Not covered: filtered search over the prepared fp16 plane (ac_knn_*_topk_batch) and filtered range search.
+ */
+int ac_knn_l2_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                       const float* d_Q, int nq, int64_t ldQ, int k,
+                       int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0,
+                       float* d_outD, double* d_outD64, int64_t* d_outI,
+                       void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                       ac_stream_t stream);
+int ac_knn_ip_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                       const float* d_Q, int nq, int64_t ldQ, int k,
+                       int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0,
+                       float* d_outD, double* d_outD64, int64_t* d_outI,
+                       void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                       ac_stream_t stream);
+int ac_knn_l2_topk_ids(const float* d_P, int64_t N, int64_t ldP, int D,
+                       const int64_t* d_ids, int64_t M,
+                       const float* d_Q, int nq, int64_t ldQ, int k,
+                       int64_t row_offset,
+                       float* d_outD, double* d_outD64, int64_t* d_outI,
+                       ac_stream_t stream);
+int ac_knn_ip_topk_ids(const float* d_P, int64_t N, int64_t ldP, int D,
+                       const int64_t* d_ids, int64_t M,
+                       const float* d_Q, int nq, int64_t ldQ, int k,
+                       int64_t row_offset,
+                       float* d_outD, double* d_outD64, int64_t* d_outI,
+                       ac_stream_t stream);
+int ac_knn_sel_pack(const uint8_t* d_mask, int64_t n, uint64_t* d_sel, ac_stream_t stream);
+int ac_knn_sel_classes(const int32_t* d_row_class, int64_t n, const uint8_t* d_class_on, int n_classes,
+                       uint64_t* d_sel, ac_stream_t stream);
+
+/*
  * Optional profiling hook: when both events are non-NULL, every following
  * ac_knn_l2_topk / ac_knn_ip_topk call of THIS thread records `start` immediately before and
  * `stop` immediately after its sweep kernel (the HBM-bound kernel) on the

@@ -14,9 +14,10 @@ import numpy as np
 import pytest
 import torch
 
+from strategic_ref import BOUND      # 2e-5: |utility - fp64 utility|, fp32 GEMM sums at D = 768 (csrc/strategic.hip for the cost term)
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-BOUND = 2e-5          # |utility - fp64 utility|: fp32 GEMM sums at D = 768 (see csrc/strategic.hip for the cost term)
 
 
 def _head(D, H1, H2, C, dev, seed):
@@ -80,6 +81,9 @@ def test_best_response_kernel_matches_fp64(cuda_dev, dims, C, b):
             want = u64.argmax(1)                                  # (first maximum)
             ch = r["choice"].long()
             sure = (top2[:, 0] - top2[:, 1]) > 2 * BOUND
+            # what this test decides: with this head scale the softmax maximum is about 1/C for every candidate, so beyond a few
+            # classes most rows are near-tied and leave the next assertion (tests/test_strategic_reference_gpu.py uses sharp heads)
+            print(f"\n[sure rows] dims {dims} C {C} b {b} mode {mode} cost {ct}: {int(sure.sum())}/{b}", end="")
             assert torch.equal(ch[sure], want[sure])
             assert ((u64.max(1).values - u64.gather(1, ch[:, None])[:, 0]).abs() <= 2 * BOUND).all()
             assert torch.equal(r["Y"], Y[torch.arange(b), ch])

@@ -12,7 +12,8 @@ faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never
 Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `ac_knn_l2_topk_batch` /
 `ac_knn_ip_topk_batch`.  range_search() (faiss range_search: every row within a radius) is `ac_knn_*_range_count` / `_fill` over
 the fp32 rows.  search(x, k, sel=...) is the FILTERED search (faiss SearchParameters(sel=IDSelector...)): the k best among the
-rows a `RowSelector` names, through `ac_knn_*_topk_sel` (bitmap) or `ac_knn_*_topk_ids` (a short id list).
+rows a `RowSelector` names, through `ac_knn_*_topk_ids` (a short id list), `ac_knn_*_topk_batch_sel` (bitmap over the prepared
+store: a selection known to hold >= 1 / SEL_BATCH_MAX_SPARSITY of the rows) or `ac_knn_*_topk_sel` (bitmap over the fp32 rows).
 """
 import ctypes
 
@@ -181,6 +182,21 @@ def knn_l2_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, p
 
 
 KNN_IDS_MAX = 8192       # rows the id-list route covers (include/acamd.h: ac_knn_*_topk_ids)
+# The filtered search takes the prepared store only for a selection KNOWN to hold at least 1 / 32 of the rows: the thresholds of
+# the prepared-store sweeps come from selected rows only -- stage A samples >= 128 k' rows, a two-phase round sees 256 tiles of 256
+# rows -- and at density 1 / 32 both still see >= 4 k' selected rows, the planner's own margin.  Sparser, the thresholds may stay
+# +inf; a store with more selected rows than the candidate buffer holds then overflows it and every query is redone in fp64 (exact,
+# but slower than the fp32 route).  Measured at 256 x 1M x 768 (profiles/knn_select/README.md): no query takes the fallback at
+# 1/32 -- nor at 1 %, where the 10 159 selected rows still fit the buffer; the fraction stays at the planner's margin.
+SEL_BATCH_MAX_SPARSITY = 32
+
+
+def sel_batch_applies(N, nq, k, count, total=None):
+    """the routing rule of the filtered search: the prepared-store route for a selection whose size is known on the host and
+    dense enough (count * SEL_BATCH_MAX_SPARSITY >= total rows; total defaults to N -- a row shard passes the global figures)
+    where `batch_applies(N, nq, k, auto=True)` holds"""
+    total = N if total is None else total
+    return count is not None and int(count) * SEL_BATCH_MAX_SPARSITY >= int(total) and batch_applies(N, nq, k, auto=True)
 
 
 def _sel_words(n):
@@ -202,12 +218,15 @@ class RowSelector:
 
     words: int64 tensor, the packed bitmap (`ac_knn_*_topk_sel`'s d_sel: row r = bit r % 64 of word r / 64, bit 0 the least
     significant); n: the rows it covers; ids: the sorted, unique int64 row ids when it was built from a host id list (else None)
-    -- a selector of <= KNN_IDS_MAX ids is searched through the id-list route.  Host inputs are packed with
+    -- a selector of <= KNN_IDS_MAX ids is searched through the id-list route; known_count: the number of selected rows when the
+    host knows it -- for free when the selector is built from host data, else after `count()` -- or None (the index then keeps a
+    bitmap search on the fp32 rows: it never reads a bitmap back to pick a route).  Host inputs are packed with
     numpy.packbits(bitorder="little") and uploaded (to `device`; without one and without a GPU they stay on the host); device
     inputs are packed by `ac_knn_sel_pack` / `ac_knn_sel_classes` without any host synchronisation."""
 
-    def __init__(self, words, n, ids=None):
+    def __init__(self, words, n, ids=None, count=None):
         self.words, self.n, self.ids = words, int(n), ids
+        self.known_count = None if count is None else int(count)
 
     @staticmethod
     def _upload(t, device):
@@ -229,7 +248,7 @@ class RowSelector:
             return cls(words, n)
         m = mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
         m = m.reshape(-1).astype(bool)
-        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), m.size)
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), m.size, count=int(m.sum()))
 
     @classmethod
     def from_ids(cls, ids, n, device=None):
@@ -247,7 +266,7 @@ class RowSelector:
         i = i[(i >= 0) & (i < n)]
         m = np.zeros(n, dtype=bool)
         m[i] = True
-        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), n, cls._upload(torch.from_numpy(i), device))
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), n, cls._upload(torch.from_numpy(i), device), count=i.size)
 
     @classmethod
     def from_range(cls, lo, hi, n, device=None):
@@ -255,7 +274,7 @@ class RowSelector:
         n = int(n)
         m = np.zeros(n, dtype=bool)
         m[max(int(lo), 0): max(min(int(hi), n), 0)] = True
-        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), n)
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), n, count=int(m.sum()))
 
     @classmethod
     def from_classes(cls, row_class, class_ids, n_classes, device=None):
@@ -280,24 +299,29 @@ class RowSelector:
         ok = (rc >= 0) & (rc < n_classes)
         m = np.zeros(rc.size, dtype=bool)
         m[ok] = on[rc[ok]] != 0
-        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), rc.size)
+        return cls(cls._upload(torch.from_numpy(_pack_host(m)), device), rc.size, count=int(m.sum()))
 
     def to(self, device):
-        return RowSelector(self.words.to(device), self.n, None if self.ids is None else self.ids.to(device))
+        return RowSelector(self.words.to(device), self.n, None if self.ids is None else self.ids.to(device), count=self.known_count)
 
     def count(self):
-        """selected rows (reads the bitmap back: one host synchronisation)"""
-        if self.ids is not None:
-            return int(self.ids.numel())
-        return int(np.unpackbits(self.words.cpu().numpy().view(np.uint8), bitorder="little")[: self.n].sum())
+        """selected rows: known_count where it is known, else read from the bitmap (one host synchronisation) and kept"""
+        if self.known_count is None:
+            self.known_count = (int(self.ids.numel()) if self.ids is not None else
+                                int(np.unpackbits(self.words.cpu().numpy().view(np.uint8), bitorder="little")[: self.n].sum()))
+        return self.known_count
 
 
-def knn_topk_sel(P, N, D, Q, k, sel, metric="l2", sel_bit0=0, row_offset=0, out=None, workspace=None, stats=None, exact_out=None):
+def knn_topk_sel(P, N, D, Q, k, sel, metric="l2", sel_bit0=0, row_offset=0, out=None, workspace=None, stats=None, exact_out=None,
+                 prepared=None):
     """FILTERED top-k (`ac_knn_l2_topk_sel` / `ac_knn_ip_topk_sel`): the k best rows of P[:N] AMONG the selected ones -- what
     `knn_l2_topk` / `knn_ip_topk` return on a store of only those rows, with the original row ids; fewer than k selected rows
     pad with (FLT_MAX, -1) / (-FLT_MAX, -1).  sel: a RowSelector or its int64 words tensor; local row r is bit sel_bit0 + r (a
     row shard passes sel_bit0 = its first row and the replicated global bitmap).  Other arguments, the workspace
-    (`knn_workspace_bytes`) and stats as `knn_l2_topk`; searches the fp32 rows (no prepared store).  Asynchronous."""
+    (`knn_workspace_bytes`) and stats as `knn_l2_topk`.  prepared: optional (planes, norms) from `prepare_store`: where
+    `batch_applies(N, nq, k)` holds the search proposes from the store's fp16 plane (`ac_knn_*_topk_batch_sel`, workspace
+    `knn_batch_workspace_bytes`) -- the same exact result at any density of the selection, but only worth it for a dense one
+    (`sel_batch_applies`); else, and without it, the fp32 rows are searched.  Asynchronous."""
     nv.require_gpu()
     assert metric in ("l2", "ip")
     assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
@@ -312,13 +336,15 @@ def knn_topk_sel(P, N, D, Q, k, sel, metric="l2", sel_bit0=0, row_offset=0, out=
         outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
     else:
         outD, outI = out
-    need = knn_workspace_bytes(N, D, nq, k)
+    batch = prepared is not None and batch_applies(N, nq, k)
+    need = knn_batch_workspace_bytes(N, D, nq, k) if batch else knn_workspace_bytes(N, D, nq, k)
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    entry = f"ac_knn_{metric}_topk_sel"
+    entry = f"ac_knn_{metric}_topk_batch_sel" if batch else f"ac_knn_{metric}_topk_sel"
+    store = (nv.ptr(prepared[0]), nv.ptr(prepared[1])) if batch else ()
     with torch.cuda.device(dev):
         rc = getattr(nv.lib(), entry)(
-            nv.ptr(P), N, P.stride(0), D, nv.ptr(Q), nq, Q.stride(0), k, row_offset, nv.ptr(words), int(sel_bit0),
+            nv.ptr(P), N, P.stride(0), D, *store, nv.ptr(Q), nq, Q.stride(0), k, row_offset, nv.ptr(words), int(sel_bit0),
             nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(), nv.ptr(stats), nv.stream_ptr(dev))
     nv.check(rc, entry)
     return outD, outI
@@ -615,7 +641,9 @@ class _HipFlatIndex:
 
     def _search_sel(self, q, k, sel):
         """the FILTERED search: a selector built from <= KNN_IDS_MAX ids takes the id-list route (its length is known on the
-        host), everything else the bitmap route over the fp32 rows; the fp16 plane is neither used nor prepared"""
+        host); a selection KNOWN to be dense (`sel_batch_applies`: known_count * 32 >= ntotal, where the unfiltered search
+        would take the prepared store) takes the prepared store -- the plane is prepared at once for >= BATCH_MIN_QUERIES
+        queries, fewer only use a plane that exists; everything else, an unknown count included, searches the fp32 rows"""
         self._materialize()
         q = q.detach().to(device=self.device, dtype=torch.float32)
         if q.dim() == 1:
@@ -625,10 +653,17 @@ class _HipFlatIndex:
         sel = self._as_selector(sel)
         if sel.ids is not None and sel.ids.numel() <= KNN_IDS_MAX:
             return knn_topk_ids(self._store, self._n, self.d, q, k, sel.ids, metric=self.metric)
-        need = knn_workspace_bytes(self._n, self.d, q.shape[0], k)
+        batch = sel_batch_applies(self._n, q.shape[0], k, sel.known_count)
+        if batch and self._prepared is None:
+            if q.shape[0] >= BATCH_MIN_QUERIES:
+                self._prepared = prepare_store(self._store, self._n, self.d, capacity=self._store.shape[0])
+            else:
+                batch = False
+        need = knn_batch_workspace_bytes(self._n, self.d, q.shape[0], k) if batch else knn_workspace_bytes(self._n, self.d, q.shape[0], k)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return knn_topk_sel(self._store, self._n, self.d, q, k, sel, metric=self.metric, workspace=self._ws, stats=self._stats)
+        return knn_topk_sel(self._store, self._n, self.d, q, k, sel, metric=self.metric, workspace=self._ws, stats=self._stats,
+                            prepared=self._prepared if batch else None)
 
     def search_device(self, q, k, sel=None):
         """q: [nq, d] fp32 tensor (any device) -> (dist, ids) CUDA tensors; no host sync.  sel: a RowSelector, a bool mask

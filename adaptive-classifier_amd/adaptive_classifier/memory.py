@@ -464,6 +464,7 @@ class PrototypeMemory:
             ids = sorted(self.label_to_index[l] for l in key if l in self.label_to_index)
             sel = RowSelector.from_ids(np.asarray(ids, dtype=np.int64), self.index.ntotal, device=self.index.device)
             count = len(ids)
+        sel.known_count = count                             # (the index routes a dense selection to the prepared store by it)
         self._among_cache = (key, sel, count)
         return sel, count
 

@@ -182,13 +182,22 @@ class ShardedSearch:
 
     def _local(self, Q, k, sel):
         """this rank's shard searched for Q: (exact fp64 values, global ids).  sel: None, or the GLOBAL RowSelector (replicated
-        on every rank) -- the shard reads its slice of the bitmap in place (sel_bit0 = row_offset), over the fp32 rows."""
+        on every rank) -- the shard reads its slice of the bitmap in place (sel_bit0 = row_offset).  The index's routing rule
+        with the GLOBAL figures (`index.sel_batch_applies`: the selector's known count over the rows it covers): a dense
+        selection searches the shard's prepared plane -- prepared at once for >= BATCH_MIN_QUERIES queries, fewer only use a
+        plane that exists -- anything else, an unknown count included, the fp32 rows."""
         if sel is None:
             return self._search(self.rows, self.n_local, self.dim, Q, k, self.row_offset)
         from . import index as ix
+        batch = ix.sel_batch_applies(self.n_local, Q.shape[0], k, getattr(sel, "known_count", None), total=getattr(sel, "n", None))
+        if batch and self._prepared is None:
+            if Q.shape[0] >= ix.BATCH_MIN_QUERIES:
+                self._prepared = ix.prepare_store(self.rows, self.n_local, self.dim)
+            else:
+                batch = False
         ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
         _, I = ix.knn_topk_sel(self.rows, self.n_local, self.dim, Q, k, sel, metric=self.metric, sel_bit0=self.row_offset,
-                               row_offset=self.row_offset, exact_out=ex)
+                               row_offset=self.row_offset, exact_out=ex, prepared=self._prepared if batch else None)
         return ex, I
 
     def search(self, queries, k, sel=None):

@@ -279,10 +279,12 @@ int knn_prepare_queries(const double* sampleD, int kp, const float* Q, int64_t l
                         double gamma, uint16_t* qplane, float* thr, float* qfac, hipStream_t stream, int32_t* zero_ints = nullptr,
                         int64_t zero_count = 0);             // zero_ints: device ints the same launch clears (the candidate counters)
 int64_t knn_sample_rows(int64_t N, int64_t stride);
+struct SelArgs;
 int knn_batch_launch(bool ip, const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
                      const float* qfac, float* cand_d, int32_t* cand_i, int32_t* cand_cnt, int cap, int segs, int64_t row_stride,
                      int best_only, hipStream_t stream, int32_t* clear_ctr = nullptr, int32_t* clear_stats = nullptr,
-                     int two_phase_kp = 0, unsigned* wgmin = nullptr, void* ctl = nullptr);
+                     int two_phase_kp = 0, unsigned* wgmin = nullptr, void* ctl = nullptr,
+                     const SelArgs* sel = nullptr);           // sel: the FILTERED sweep (bitmap + first bit; knn_batch.hip SEL)
 bool ln_fusion_enabled();        // gemm_pipe.hip: false = this call / process runs no in-launch exchange between workgroups
 bool knn_batch_two_phase_applies(int64_t N, int nq, int kp, int segs);
 size_t knn_batch_two_phase_bytes();
@@ -358,10 +360,13 @@ MergeParams knn_merge_params(const float* P, int64_t N, int64_t ldP, const float
                              int64_t row_offset, float* outD, double* outD64, int64_t* outI, int32_t* stats, char* ws,
                              const ExactPlan& ep);
 // ip: the inner-product instantiations.  attr_lds: dynamic-LDS opt-in to set first (0 = the caller's earlier launch did)
-int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream, const SelArgs* sel = nullptr);
+// sel_thr (FILTERED search in candidate-buffer mode): the per-query thresholds the main sweep used (one more certificate rule)
+int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream, const SelArgs* sel = nullptr,
+                     const float* sel_thr = nullptr);
 // merge / re-rank, then (N > 0) exact fallback + fallback merge; merge_lds = this launch's share of ep.merge_lds
 // sel != NULL (both below): the FILTERED forms of the kernels
-int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream, const SelArgs* sel = nullptr);
+int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream, const SelArgs* sel = nullptr,
+                   const float* sel_thr = nullptr);
 int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream, const SelArgs* sel = nullptr);
 
 // Per-call options (ac_bert_config.gemm_arith_opt / ln_fusion_opt / one_launch_opt): for the duration of ONE native call on the

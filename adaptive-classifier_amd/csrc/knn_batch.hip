@@ -163,7 +163,52 @@ struct BatchParams {
     acp::GridCtl* ctl;                       // zeroed before the launch
 };
 
-typedef const BatchParams __attribute__((address_space(4)))* KArgs;
+// FILTERED search over the prepared store (ac_knn_*_topk_batch_sel; acamd.h "FILTERED search"): the SEL instantiations take this
+// struct, the plain ones keep BatchParams and with it their kernarg segment.  STORE row r is a candidate iff bit (sel_bit0 + r)
+// of the bitmap is set.
+struct BatchParamsSel : BatchParams {
+    const uint64_t* sel;
+    int64_t sel_bit0;
+};
+template <bool SEL> struct batch_params { typedef BatchParams type; };
+template <> struct batch_params<true> { typedef BatchParamsSel type; };
+
+// The selection bits of 32 logical rows l0 .. l0 + 31 (bit i = logical row l0 + i; l0 is a multiple of 32 and wave-uniform),
+// fetched through the SCALAR unit like the sweeps of knn_l2.hip (constant address space: nothing enters the vmcnt queue the DMA
+// ring is counted on).  Logical row i is store row (i >> 3) * rs8 + (i & 7): a run of 8 logical rows is 8 consecutive store rows,
+// whose 8 bits start at ANY bit of the bitmap -- two 32-bit words at most.  Runs at or past `nr` read nothing (their rows never
+// qualify anyway: +inf norms / the IP bound check); the second word of a run is read only if one of its rows exists, so nothing
+// behind word (sel_bit0 + N - 1) / 64 is touched.  Fetched where it is used (a few scalar loads per 32 x 128 accumulator tile)
+// rather than kept: nothing of it is live across the filter's passes.
+template <bool BURST>
+__device__ __forceinline__ uint32_t batch_sel_bits(const uint64_t* sel, int64_t sel_bit0, int l0, int rs8, int nr) {
+    typedef const uint32_t __attribute__((address_space(4)))* cwp;
+    typedef const uint64_t __attribute__((address_space(4)))* cup;
+    if (l0 >= nr) return 0u;
+    if constexpr (!BURST) {                                        // the whole store: 32 consecutive bits, two 64-bit words at most
+        const uint32_t rem = __builtin_amdgcn_readfirstlane((uint32_t)(sel_bit0 & 63) + (uint32_t)l0);
+        const cup w = (cup)(uintptr_t)(sel + (sel_bit0 >> 6) + (rem >> 6));
+        const int s = (int)(rem & 63u);
+        uint64_t bits = w[0] >> s;
+        if (s > 32 && l0 + (64 - s) < nr) bits |= w[1] << (64 - s);
+        return (uint32_t)bits;
+    } else {
+        const cwp base = (cwp)(uintptr_t)(reinterpret_cast<const uint32_t*>(sel) + ((sel_bit0 >> 6) << 1));
+        const uint32_t b0 = (uint32_t)(sel_bit0 & 63);
+        uint32_t bits = 0u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (l0 + 8 * u < nr) {                                 // (wave-uniform)
+                const uint32_t b = __builtin_amdgcn_readfirstlane(b0 + (uint32_t)(((l0 >> 3) + u) * rs8));      // (N < 2^31: no wrap)
+                const int s = (int)(b & 31u);
+                uint32_t x = base[b >> 5] >> s;
+                if (s > 24 && l0 + 8 * u + (32 - s) < nr) x |= base[(b >> 5) + 1] << (32 - s);
+                bits |= (x & 0xffu) << (8 * u);
+            }
+        }
+        return bits;
+    }
+}
 
 template <int N> __device__ __forceinline__ void bwait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -183,8 +228,15 @@ template <int N> __device__ __forceinline__ void bwait_vm() { asm volatile("s_wa
 // the norms' +inf padding did for L2 -- rows past the end never qualify and are never published as a minimum -- is a bound check
 // of the LOGICAL row against BatchParams::N here (a zero plane row, or the clamped DMA's copy of the last row, gives a v that
 // would beat every real row when all products are negative).
-template <int BNS, int NWV, bool BURST, bool TWO_PHASE = false, bool IP = false>        // ring depth, waves; TWO_PHASE: BatchParams::two_phase (its own instantiation)
-__global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams prm) {
+// SEL (the LAST parameter: every other form keeps its name up to the defaulted argument): the FILTERED sweep.  An unselected row is
+// treated as the IP form treats a row past the end -- its sweep value is +inf before anything looks at it: the main filter's
+// comparison with thr, the best_only offer of stage A, the two-phase minima.  Thresholds therefore come from selected rows only; a
+// two-phase round in which fewer than k' workgroups saw a selected row leaves thr at +inf (the k'-th smallest published minimum is
+// +inf then), a sample stage that kept fewer than k' rows leaves it where it was (knn_merge_rerank).  A sample stage tests the bit
+// of the STORE row (batch_sel_bits).
+template <int BNS, int NWV, bool BURST, bool TWO_PHASE = false, bool IP = false, bool SEL = false>        // ring depth, waves; TWO_PHASE: BatchParams::two_phase (its own instantiation)
+__global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(typename batch_params<SEL>::type prm) {
+    typedef const typename batch_params<SEL>::type __attribute__((address_space(4)))* KArgs;
     constexpr int WMW = NWV / 2, TM = BBM / (32 * WMW), TN = 4;    // wave grid WMW x 2, wave tile (32 TM) x 128
     constexpr int GPW = BGA / NWV;                                  // store / query groups each wave stages
     constexpr int PPW = 4 * GPW;                                    // DMA pieces per wave and stage
@@ -318,9 +370,14 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
         // (logical rows come in runs of 8 = one group of BatchParams::row_stride; a group past the end never qualifies --
         //  with row_stride == 1 the array is also padded with +inf to whole tiles)
         const int rs8 = 8 * (int)ka->row_stride, nr = (int)ka->N;
+        // (SEL) the selection bits of this lane's 16 rows of tile mi: bit (r & 3) + 8 (r >> 2)
+        auto sel_lane = [&](int mi) -> uint32_t {
+            if constexpr (SEL) return batch_sel_bits<BURST>(ka->sel, ka->sel_bit0, row0 + mi * 32, rs8, nr) >> (4 * kg);
+            else return 0u;
+        };
         auto load_pn = [&](int mi, float (&pn)[16]) {
             const int l0 = row0 + mi * 32;                          // multiple of 32
-            if constexpr (IP) {                                     // no norm term: nothing to load (sweep_val never reads pn)
+            if constexpr (IP) {                                     // no norm term: nothing to load (the plain sweep_val never reads pn)
                 (void)l0; (void)pn;
             } else if constexpr (!BURST) {                          // the whole store: contiguous, padded with +inf -- nothing to check
 #pragma unroll
@@ -337,6 +394,12 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
                     pn[4 * r4] = in ? t.x : INFINITY; pn[4 * r4 + 1] = in ? t.y : INFINITY;
                     pn[4 * r4 + 2] = in ? t.z : INFINITY; pn[4 * r4 + 3] = in ? t.w : INFINITY;
                 }
+            }
+            if constexpr (SEL && !IP) {                             // an unselected row gets the norm of a row past the end
+                const uint32_t m = sel_lane(mi);
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (!((m >> ((r & 3) + 8 * (r >> 2))) & 1u)) pn[r] = INFINITY;
             }
         };
         float thr[4], qf[4];
@@ -370,6 +433,29 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void knn_batch_sweep(BatchParams
 #pragma unroll
                             for (int ni = 0; ni < 4; ++ni) acc[mi][ni][r] = INFINITY;
                         }
+                }
+            }
+            // (SEL) unselected rows likewise, in place and once per tile -- only where a bit of the 32-row tile is clear (the
+            // bits are wave-uniform scalars: a fully selected tile costs their fetch and one scalar compare)
+            if constexpr (SEL) {
+#pragma unroll
+                for (int mi = 0; mi < TM; ++mi) {
+                    const uint32_t sb = batch_sel_bits<BURST>(ka->sel, ka->sel_bit0, row0 + mi * 32, rs8, nr);
+                    if (sb != 0xffffffffu) {
+                        // (the lane half from the hardware lane count: taken from kg, the thread id stays live across the k-loop
+                        //  of the two-phase form and costs it a spill slot.  The value is lane >> 5 either way; only hipcc's
+                        //  register allocation hangs on the form, and tests/test_kernel_resources_cpu.py -- <= 16 bytes of
+                        //  scratch, none inside the k-loop -- is what guards it against a later compiler.)
+                        unsigned ln;                                 // (volatile: computed here, not hoisted in front of the k-loop)
+                        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+                        const uint32_t m = sb >> ((ln >> 5) << 2);
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            if (!((m >> ((r & 3) + 8 * (r >> 2))) & 1u)) {
+#pragma unroll
+                                for (int ni = 0; ni < 4; ++ni) acc[mi][ni][r] = INFINITY;
+                            }
+                    }
                 }
             }
         }
@@ -656,21 +742,22 @@ bool knn_batch_two_phase_applies(int64_t N, int nq, int kp, int segs) {
 }
 size_t knn_batch_two_phase_bytes() { return (size_t)64 * 8 * 256 * sizeof(unsigned); }       // wgmin for the largest grid
 
-template <bool IP>
+template <bool IP, bool SEL>
 static int knn_batch_launch_t(const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
                      const float* qfac, float* cand_d, int32_t* cand_i, int32_t* cand_cnt, int cap, int segs, int64_t row_stride,
                      int best_only, hipStream_t stream, int32_t* clear_ctr, int32_t* clear_stats, int two_phase_kp, unsigned* wgmin,
-                     void* ctl) {
+                     void* ctl, const SelArgs* sel) {
     // (measured and dropped, profiles/r03/knn_batch_probe*.txt: a ring of 5 slots -- no change, the DMA depth is not the limit;
     //  2 x 2 waves of 128 x 128 with the 512-register budget, one wave per SIMD -- 120 vs 80 ms at 4096 x 10M: hipcc shuffles
     //  ~200 accumulator registers per iteration and a lone wave per SIMD hides nothing)
     constexpr int ns = 4, nwv = 8;
     const size_t lds = (size_t)ns * BSLOT * 16;
     // (per call, like the launch sites of knn_l2.hip and knn_exact.hip: function attributes are per device, and a cached flag is neither)
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, false, IP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, false, false, IP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, true, IP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    BatchParams p{};
+    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, false, IP, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, false, false, IP, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    AC_HIP_CHECK(hipFuncSetAttribute((const void*)knn_batch_sweep<ns, nwv, true, true, IP, SEL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    typename batch_params<SEL>::type p{};
+    if constexpr (SEL) { p.sel = sel->sel; p.sel_bit0 = sel->sel_bit0; }
     p.Pp = Pp; p.p_rows = (N + 255) / 256 * 256; p.pnorm = pnorm;
     p.q_rows = ((int64_t)nq + 255) / 256 * 256;
     p.row_stride = row_stride < 1 ? 1 : row_stride;
@@ -707,23 +794,24 @@ static int knn_batch_launch_t(const uint16_t* Pp, const float* pnorm, int64_t N,
         p.cand_d = cand_d + qoff * cap; p.cand_i = cand_i + qoff * cap; p.cand_cnt = cand_cnt + qoff * segs;
         p.clear_ctr = t0 == 0 ? clear_ctr : nullptr; p.clear_stats = t0 == 0 ? clear_stats : nullptr;
         const dim3 grid((unsigned)nblk), block(64 * nwv);
-        if (p.two_phase) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, true, IP>), grid, block, lds, stream, p);
-        else if (segs > 1 || p.row_stride > 1 || best_only) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, false, IP>), grid, block, lds, stream, p);
-        else hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, false, false, IP>), grid, block, lds, stream, p);
+        if (p.two_phase) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, true, IP, SEL>), grid, block, lds, stream, p);
+        else if (segs > 1 || p.row_stride > 1 || best_only) hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, true, false, IP, SEL>), grid, block, lds, stream, p);
+        else hipLaunchKernelGGL((knn_batch_sweep<ns, nwv, false, false, IP, SEL>), grid, block, lds, stream, p);
         AC_LAUNCH_CHECK();
     }
     return AC_OK;
 }
 
-// ip: the inner-product instantiations (pnorm is not read then)
+// ip: the inner-product instantiations (pnorm is not read then); sel != NULL: the FILTERED instantiations (sel->sel, sel->sel_bit0)
 int knn_batch_launch(bool ip, const uint16_t* Pp, const float* pnorm, int64_t N, int D, const uint16_t* Qp, int nq, const float* thr,
                      const float* qfac, float* cand_d, int32_t* cand_i, int32_t* cand_cnt, int cap, int segs, int64_t row_stride,
                      int best_only, hipStream_t stream, int32_t* clear_ctr, int32_t* clear_stats, int two_phase_kp, unsigned* wgmin,
-                     void* ctl) {
-    return ip ? knn_batch_launch_t<true>(Pp, pnorm, N, D, Qp, nq, thr, qfac, cand_d, cand_i, cand_cnt, cap, segs, row_stride, best_only, stream,
-                                         clear_ctr, clear_stats, two_phase_kp, wgmin, ctl)
-              : knn_batch_launch_t<false>(Pp, pnorm, N, D, Qp, nq, thr, qfac, cand_d, cand_i, cand_cnt, cap, segs, row_stride, best_only, stream,
-                                          clear_ctr, clear_stats, two_phase_kp, wgmin, ctl);
+                     void* ctl, const SelArgs* sel) {
+#define AC_KNN_BATCH_ARGS Pp, pnorm, N, D, Qp, nq, thr, qfac, cand_d, cand_i, cand_cnt, cap, segs, row_stride, best_only, stream, \
+                          clear_ctr, clear_stats, two_phase_kp, wgmin, ctl, sel
+    if (sel) return ip ? knn_batch_launch_t<true, true>(AC_KNN_BATCH_ARGS) : knn_batch_launch_t<false, true>(AC_KNN_BATCH_ARGS);
+    return ip ? knn_batch_launch_t<true, false>(AC_KNN_BATCH_ARGS) : knn_batch_launch_t<false, false>(AC_KNN_BATCH_ARGS);
+#undef AC_KNN_BATCH_ARGS
 }
 
 }  // namespace ac

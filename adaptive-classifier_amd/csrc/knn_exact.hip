@@ -113,7 +113,7 @@ __device__ __forceinline__ uint32_t block_radix_select(int n, int want, KeyFn ke
 // (Each kernel below is a thin `template <bool IP> __global__` wrapper around a force-inlined body that takes the parameters by
 //  reference: written straight into the kernel, hipcc schedules the same code differently.)
 template <bool IP, bool SEL = false>
-__device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, char* smem) {
+__device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, char* smem, const float* sel_thr = nullptr) {
     const int q = blockIdx.x;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -352,6 +352,13 @@ __device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, ch
             // entries IN TOTAL mean that no block pruned -- every list still holds every selected row of its block (tau stayed
             // +inf), all of them were re-ranked above, and the result is complete however few they are (padding included).
             if constexpr (SEL) { if (!prm.cand_cnt && nreal < kp && !overflow) ok = 1; }
+            // FILTERED search in candidate-buffer mode (knn_merge_rerank_selc; sel_thr = the thresholds the main sweep used): a
+            // sweep that ran with thr = +inf kept every selected row (v < +inf for every finite v; unselected rows carry +inf and
+            // are never kept), so a list that did not overflow holds ALL of them, and with nreal <= k' all of them were re-ranked
+            // above: complete, padding included.  A finite threshold or nreal > k' leaves the unfiltered rule as it is.
+            // (Premise, shared with the per-block rule above: a selected row has a finite sweep value -- a row whose |p|^2
+            //  overflows fp32 is kept by no sweep, filtered or not.)
+            if constexpr (SEL) { if (sel_thr && prm.cand_cnt && nreal <= kp && !overflow && sel_thr[q] == INFINITY) ok = 1; }
         }
         int flag = 0;
         if (!ok) {
@@ -371,6 +378,11 @@ template <bool IP>
 __global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank_sel(MergeParams prm) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     knn_merge_rerank_body<IP, true>(prm, smem);
+}
+template <bool IP>
+__global__ __launch_bounds__(kMergeThreads) void knn_merge_rerank_selc(MergeParams prm, const float* sel_thr) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    knn_merge_rerank_body<IP, true>(prm, smem, sel_thr);
 }
 
 // --------------------------------------------------------------------------------------
@@ -722,7 +734,15 @@ MergeParams knn_merge_params(const float* P, int64_t N, int64_t ldP, const float
 }
 
 // (function attributes are set per call: they are per device, and a cached flag is not)
-int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream, const SelArgs* sel) {
+int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, size_t lds, hipStream_t stream, const SelArgs* sel,
+                     const float* sel_thr) {
+    if (sel && sel_thr) {                             // FILTERED search over a candidate buffer: the rule that reads the thresholds
+        void (*cfn)(MergeParams, const float*) = ip ? knn_merge_rerank_selc<true> : knn_merge_rerank_selc<false>;
+        if (attr_lds) AC_HIP_CHECK(hipFuncSetAttribute((const void*)cfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds));
+        hipLaunchKernelGGL(cfn, dim3(nq), dim3(kMergeThreads), lds, stream, mp, sel_thr);
+        AC_LAUNCH_CHECK();
+        return AC_OK;
+    }
     void (*fn)(MergeParams) = ip ? knn_merge_rerank<true> : knn_merge_rerank<false>;
     if (sel) fn = ip ? knn_merge_rerank_sel<true> : knn_merge_rerank_sel<false>;         // FILTERED search: one more certificate rule
     if (attr_lds) AC_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds));
@@ -731,8 +751,9 @@ int knn_merge_launch(bool ip, const MergeParams& mp, int nq, size_t attr_lds, si
     return AC_OK;
 }
 
-int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream, const SelArgs* sel) {
-    const int rc = knn_merge_launch(ip, mp, nq, ep.merge_lds, merge_lds, stream, sel);
+int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, size_t merge_lds, hipStream_t stream, const SelArgs* sel,
+                   const float* sel_thr) {
+    const int rc = knn_merge_launch(ip, mp, nq, ep.merge_lds, merge_lds, stream, sel, sel_thr);
     if (rc != AC_OK || mp.N == 0) return rc;          // (an empty store: everything is padding, nothing can be flagged)
     const dim3 fb_grid(ep.fb_S, nq < kFbQueryGroups ? nq : kFbQueryGroups);
     if (sel) {                                        // FILTERED search: the fallback scans the selected rows only

@@ -734,6 +734,28 @@ struct PlaneSweepParams {
     int32_t* clear_stats;
 };
 
+// FILTERED search over the plane (ac_knn_*_topk_batch_sel, <= 64 queries): the SEL instantiations take this struct, the plain ones
+// keep PlaneSweepParams and their kernarg segment (as SweepParamsSel above)
+struct PlaneSweepParamsSel : PlaneSweepParams {
+    const uint64_t* sel;
+    int64_t sel_bit0;
+};
+template <bool SEL> struct plane_sweep_params { typedef PlaneSweepParams type; };
+template <> struct plane_sweep_params<true> { typedef PlaneSweepParamsSel type; };
+
+// The 32 selection bits of a wave's rows row_base .. row_base + 31 (bit i = row row_base + i): sweep_sel_bits for the plane sweep's
+// wave tile -- two 64-bit words at most, through the scalar unit, the second one only if one of its rows exists.
+__device__ __forceinline__ uint32_t plane_sel_bits(const uint64_t* sel, int64_t sel_bit0, int64_t N, int row_base) {
+    if (row_base >= N) return 0u;
+    typedef const uint64_t __attribute__((address_space(4)))* cup;
+    const uint32_t rem = __builtin_amdgcn_readfirstlane((uint32_t)(sel_bit0 & 63) + (uint32_t)row_base);     // (N < 2^31)
+    const cup w = (cup)(uintptr_t)(sel + (sel_bit0 >> 6) + (rem >> 6));
+    const int s = (int)(rem & 63u);
+    uint64_t bits = w[0] >> s;
+    if (s > 32 && row_base + (64 - s) < N) bits |= w[1] << (64 - s);
+    return (uint32_t)bits;
+}
+
 typedef _Float16 kf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t ku32x4 __attribute__((ext_vector_type(4)));
 // C/D layout of v_mfma_f32_32x32x16_f16: lane owns column (lane & 31) and these 16 rows
@@ -742,8 +764,10 @@ __device__ __forceinline__ int plane_acc_row(int r, int lane) { return (r & 3) +
 // IP (the last parameter): the inner-product proposal v = f_q acc ~ -2 p.q.  No norm is loaded; the rows past N, which the L2
 // form keeps out through the +inf padding of the norms, are bound-checked here (a zero plane row gives v = 0: the best value
 // of all when every product is negative).
-template <int TQ, bool IP = false>
-__global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams prm) {
+// SEL (after IP): the FILTERED form.  An unselected row's value becomes +inf -- through the norm term, like a row past N -- before it
+// meets tau or a list, so the per-workgroup lists, pruning and tau see exactly the selected rows (knn_sweep's rule).
+template <int TQ, bool IP = false, bool SEL = false>
+__global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(typename plane_sweep_params<SEL>::type prm) {
     constexpr int NJ = TQ / 32;                       // 32-column sub-tiles of the query tile
     constexpr int NB = 4, GK = 4;                     // register buffers x k-steps per buffer (16 loads in flight)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -813,6 +837,8 @@ __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams 
         const cfp pn = (cfp)(uintptr_t)(prm.pnorm + __builtin_amdgcn_readfirstlane(row0));
         bool maybe = false;
         const int left = (int)prm.N - row0 - 4 * kg;                           // (IP) rows (r & 3) + 8 (r >> 2) below it exist
+        uint32_t sbits = 0u;                                                   // (SEL) this lane's rows: bit (r & 3) + 8 (r >> 2)
+        if constexpr (SEL) sbits = plane_sel_bits(prm.sel, prm.sel_bit0, prm.N, row0) >> (4 * kg);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             float pnr;
@@ -822,6 +848,7 @@ __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(PlaneSweepParams 
                 const float lo = pn[(r & 3) + 8 * (r >> 2)], hi = pn[(r & 3) + 8 * (r >> 2) + 4];
                 pnr = kg ? hi : lo;
             }
+            if constexpr (SEL) { if (!((sbits >> ((r & 3) + 8 * (r >> 2))) & 1u)) pnr = INFINITY; }
 #pragma unroll
             for (int jj = 0; jj < NJ; ++jj) {
                 acc[jj][r] = fmaf(acc[jj][r], qf[jj], pnr);                    // the sweep value, in place
@@ -1386,7 +1413,7 @@ bool make_plane_plan(int64_t N, int D, int nq, int k, PlanePlan* pp) {
 
 int plane_search(bool ip, const PlanePlan& pp, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
                  const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset, float* d_outD, double* d_outD64, int64_t* d_outI,
-                 char* ws, int32_t* d_stats, hipStream_t stream) {
+                 char* ws, int32_t* d_stats, hipStream_t stream, const ac::SelArgs* sel = nullptr) {
     const int64_t np = (N + 255) / 256 * 256;
     const uint32_t* d_maxnorm = reinterpret_cast<const uint32_t*>(d_norms + np);
     const double gamma = ac::knn_batch_gamma(D);
@@ -1396,7 +1423,8 @@ int plane_search(bool ip, const PlanePlan& pp, const float* d_P, int64_t N, int6
                                      (float*)(ws + pp.off_thr), (float*)(ws + pp.off_qfac), stream);
     if (rc != AC_OK) return rc;
     // 2. one pass over the plane per query tile
-    PlaneSweepParams sp{};
+    PlaneSweepParamsSel sp{};                         // (the plain kernels take its PlaneSweepParams base)
+    if (sel) { sp.sel = sel->sel; sp.sel_bit0 = sel->sel_bit0; }
     sp.Pp = d_planes; sp.pnorm = d_norms; sp.Qp = (const uint16_t*)(ws + pp.off_qp); sp.q_rows = pp.q_rows;
     sp.qfac = (const float*)(ws + pp.off_qfac); sp.N = N; sp.ntiles = pp.ntiles; sp.Kp = pp.Kp;
     sp.kp = pp.kp; sp.cap = pp.cap; sp.G = pp.G;
@@ -1406,11 +1434,20 @@ int plane_search(bool ip, const PlanePlan& pp, const float* d_P, int64_t N, int6
         sp.q0 = qt * pp.TQ; sp.nq = nq - sp.q0 < pp.TQ ? nq - sp.q0 : pp.TQ;
         sp.clear_ctr = qt == 0 ? (int32_t*)(ws + pp.ex.off_fb_ctr) : nullptr;
         sp.clear_stats = qt == 0 ? d_stats : nullptr;
-        void (*sweep_fn)(PlaneSweepParams);
-        if (pp.TQ == 64) sweep_fn = ip ? knn_plane_sweep<64, true> : knn_plane_sweep<64, false>;
-        else sweep_fn = ip ? knn_plane_sweep<32, true> : knn_plane_sweep<32, false>;
-        AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
-        hipLaunchKernelGGL(sweep_fn, dim3(pp.G), dim3(kThreads), pp.sweep_lds, stream, sp);
+        if (sel) {                                    // FILTERED search: the SEL instantiation of the same sweep
+            void (*sweep_sel_fn)(PlaneSweepParamsSel);
+            if (pp.TQ == 64) sweep_sel_fn = ip ? knn_plane_sweep<64, true, true> : knn_plane_sweep<64, false, true>;
+            else sweep_sel_fn = ip ? knn_plane_sweep<32, true, true> : knn_plane_sweep<32, false, true>;
+            AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_sel_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
+            hipLaunchKernelGGL(sweep_sel_fn, dim3(pp.G), dim3(kThreads), pp.sweep_lds, stream, sp);
+        } else {
+            void (*sweep_fn)(PlaneSweepParams);
+            if (pp.TQ == 64) sweep_fn = ip ? knn_plane_sweep<64, true> : knn_plane_sweep<64, false>;
+            else sweep_fn = ip ? knn_plane_sweep<32, true> : knn_plane_sweep<32, false>;
+            AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pp.sweep_lds));
+            const PlaneSweepParams base = sp;
+            hipLaunchKernelGGL(sweep_fn, dim3(pp.G), dim3(kThreads), pp.sweep_lds, stream, base);
+        }
         AC_LAUNCH_CHECK();
     }
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
@@ -1419,7 +1456,9 @@ int plane_search(bool ip, const PlanePlan& pp, const float* d_P, int64_t N, int6
     mp.G = pp.G; mp.nblk = 1; mp.gamma = gamma;
     mp.part_d = (const float*)(ws + pp.off_part_d); mp.part_i = (const int32_t*)(ws + pp.off_part_i);
     mp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    return ac::knn_exact_tail(ip, mp, pp.ex, nq, pp.ex.merge_lds, stream);
+    // (FILTERED: knn_merge_rerank_sel's per-block rule -- fewer than k' = k + 24 real entries in total => complete -- and the
+    //  fallback over the selected rows)
+    return ac::knn_exact_tail(ip, mp, pp.ex, nq, pp.ex.merge_lds, stream, sel);
 }
 
 }  // namespace
@@ -1477,11 +1516,16 @@ static int batch_segs(const BatchPlan& bp, int64_t rows, int nq) {
 static int knn_topk_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
                           const float* d_norms, const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset,
                           float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
-                          int32_t* d_stats, ac_stream_t stream_) {
+                          int32_t* d_stats, ac_stream_t stream_, const uint64_t* d_sel = nullptr, int64_t sel_bit0 = 0) {
     hipStream_t stream = (hipStream_t)stream_;
     BatchPlan bp;
     int rc = make_batch_plan(N, D, nq, k, &bp);
     if (rc != AC_OK) return rc;
+    // d_sel != NULL: the FILTERED search (ac_knn_*_topk_batch_sel) -- the same plan, workspace and launch sequence with the SEL
+    // instantiations of the sweeps and of the exact stages
+    ac::SelArgs sa;
+    sa.sel = d_sel; sa.sel_bit0 = sel_bit0;
+    const ac::SelArgs* const sel = d_sel ? &sa : nullptr;
     AC_REQUIRE(d_P && d_planes && d_norms && d_Q && d_outD && d_outI, AC_EINVAL, "knn batch: null pointer");
     AC_REQUIRE(ldQ >= D && ldP >= bp.Dp && (ldP % 4) == 0 && (((uintptr_t)d_P) & 15) == 0, AC_EINVAL, "knn batch: bad leading dimension / alignment");
     AC_REQUIRE(d_ws && ws_bytes >= bp.total, AC_EWORKSPACE, "knn batch: workspace %zu < required %zu", ws_bytes, bp.total);
@@ -1491,7 +1535,7 @@ static int knn_topk_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int
         if (make_plane_plan(N, D, nq, k, &pp)) {
             AC_REQUIRE(ws_bytes >= pp.total, AC_EWORKSPACE, "knn batch: workspace %zu < required %zu", ws_bytes, pp.total);
             return plane_search(ip, pp, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, ws,
-                                d_stats, stream);
+                                d_stats, stream, sel);
         }
     }
     const int64_t np = (N + 255) / 256 * 256;
@@ -1533,7 +1577,7 @@ static int knn_topk_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int
         sp.cand_segs = segs;
         rc = ac::knn_batch_launch(ip, d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
                                   (const float*)(ws + bp.off_qfac), (float*)(ws + bp.off_cd), (int32_t*)(ws + bp.off_ci),
-                                  (int32_t*)(ws + bp.off_cnt), bp.cap, segs, sst, st == 0 ? 1 : 0, stream);
+                                  (int32_t*)(ws + bp.off_cnt), bp.cap, segs, sst, st == 0 ? 1 : 0, stream, nullptr, nullptr, 0, nullptr, nullptr, sel);
         if (rc != AC_OK) return rc;
         sp.N = ac::knn_sample_rows(N, sst); sp.run_stride = sst > 1 ? 8 * sst : 0;   // sample row i = store row (i >> 3) * 8 sst + (i & 7)
         rc = ac::knn_merge_launch(ip, sp, nq, st == 0 ? bp.ex.merge_lds : 0, mlds, stream);      // (the opt-in covers the later stages)
@@ -1556,7 +1600,7 @@ static int knn_topk_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_start, stream));
     rc = ac::knn_batch_launch(ip, d_planes, d_norms, N, D, (const uint16_t*)(ws + bp.off_qp), nq, (const float*)(ws + bp.off_thr),
                               (const float*)(ws + bp.off_qfac), (float*)(ws + bp.off_cd), (int32_t*)(ws + bp.off_ci), (int32_t*)(ws + bp.off_cnt), bp.cap, msegs, 1, 0, stream,
-                              (int32_t*)(ws + bp.ex.off_fb_ctr), d_stats, two_phase ? bp.kp : 0, (unsigned*)(ws + bp.off_wgmin), ws + bp.off_ctl);
+                              (int32_t*)(ws + bp.ex.off_fb_ctr), d_stats, two_phase ? bp.kp : 0, (unsigned*)(ws + bp.off_wgmin), ws + bp.off_ctl, sel);
     if (rc != AC_OK) return rc;
     if (g_prof_start && g_prof_stop) AC_HIP_CHECK(hipEventRecord(g_prof_stop, stream));
     // 4. merge + exact re-rank + certificate, then the exact fallback for uncertified queries
@@ -1565,7 +1609,8 @@ static int knn_topk_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int
     mp.cand_cnt = (const int32_t*)(ws + bp.off_cnt); mp.cand_cap = bp.cap; mp.cand_segs = msegs;
     mp.part_d = (const float*)(ws + bp.off_cd); mp.part_i = (const int32_t*)(ws + bp.off_ci);
     mp.part_maxnorm = reinterpret_cast<const float*>(d_maxnorm);
-    return ac::knn_exact_tail(ip, mp, bp.ex, nq, mlds, stream);
+    // (FILTERED: the merge also reads the thresholds the main sweep used -- the candidate-buffer rule of knn_merge_rerank_selc)
+    return ac::knn_exact_tail(ip, mp, bp.ex, nq, mlds, stream, sel, sel ? (const float*)(ws + bp.off_thr) : nullptr);
 }
 
 extern "C" int ac_knn_l2_topk_batch(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
@@ -1587,4 +1632,33 @@ extern "C" int ac_knn_ip_topk_batch(const float* d_P, int64_t N, int64_t ldP, in
                                     int32_t* d_stats, ac_stream_t stream_) {
     return knn_topk_batch(true, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes,
                           d_stats, stream_);
+}
+
+// FILTERED search over the prepared store (acamd.h "FILTERED search"): the selection checks of ac_knn_*_topk_sel, then the limits
+// of ac_knn_l2_topk_batch -- all before any HIP call; the search is knn_topk_batch with the selection.
+static int knn_topk_batch_sel(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+                              const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0,
+                              float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                              ac_stream_t stream_) {
+    AC_REQUIRE(sel_bit0 >= 0, AC_EINVAL, "knn batch sel: sel_bit0=%lld must be >= 0", (long long)sel_bit0);
+    AC_REQUIRE(d_sel != nullptr, AC_EINVAL, "knn batch sel: d_sel is NULL");
+    AC_REQUIRE((((uintptr_t)d_sel) & 7) == 0, AC_EINVAL, "knn batch sel: d_sel must be 8-byte aligned");
+    return knn_topk_batch(ip, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_outD, d_outD64, d_outI, d_ws, ws_bytes,
+                          d_stats, stream_, d_sel, sel_bit0);
+}
+
+extern "C" int ac_knn_l2_topk_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+                                        const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset, const uint64_t* d_sel,
+                                        int64_t sel_bit0, float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
+                                        int32_t* d_stats, ac_stream_t stream_) {
+    return knn_topk_batch_sel(false, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_sel, sel_bit0, d_outD, d_outD64,
+                              d_outI, d_ws, ws_bytes, d_stats, stream_);
+}
+
+extern "C" int ac_knn_ip_topk_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+                                        const float* d_Q, int nq, int64_t ldQ, int k, int64_t row_offset, const uint64_t* d_sel,
+                                        int64_t sel_bit0, float* d_outD, double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes,
+                                        int32_t* d_stats, ac_stream_t stream_) {
+    return knn_topk_batch_sel(true, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, k, row_offset, d_sel, sel_bit0, d_outD, d_outD64,
+                              d_outI, d_ws, ws_bytes, d_stats, stream_);
 }

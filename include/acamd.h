@@ -308,7 +308,23 @@ int ac_knn_ip_range_fill(const float* d_P, int64_t N, int64_t ldP, int D,
  *       no atomics), the tail bits past n as 0 and nothing past the last word.  Asynchronous, no host synchronisation.
  * AC_EINVAL, before any device work, names the argument: d_sel NULL with N > 0, d_sel not 8-byte aligned, sel_bit0 < 0,
  * M < 0 or M > 8192.  Everything else (ldP / ldQ / alignment of d_P, AC_EWORKSPACE, supported (N, D, k)) as ac_knn_l2_topk_x.
- * Not covered: filtered search over the prepared fp16 plane (ac_knn_*_topk_batch) and filtered range search.
+ *   ac_knn_l2_topk_batch_sel / ac_knn_ip_topk_batch_sel   the filtered search over a PREPARED store: the arguments of
+ *       ac_knn_*_topk_batch plus (d_sel, sel_bit0) after row_offset, the limits of ac_knn_l2_topk_batch (N >= 65536, k <= 100, else
+ *       AC_EUNSUPPORTED) and the workspace ac_knn_l2_topk_batch_workspace(N, D, nq, k) returns.  The result is that of
+ *       ac_knn_*_topk_sel bit for bit; an all-ones selection returns the bits of ac_knn_*_topk_batch, d_stats included
+ *       ([0] = queries answered by the fp64 fallback over the selected rows, [1] = 2 when the plane sweep ran).  The prepared store is
+ *       neither changed nor re-prepared: one plane serves every selection.  Mechanism: the two proposal sweeps of the prepared
+ *       store with a selection flag -- an unselected row's value is +inf before a list, a threshold or a published minimum sees it,
+ *       so thresholds come from selected rows only; a stage that sees fewer than k' = k + 24 of them leaves the threshold where it
+ *       was, +inf at first.  <= 64 queries: the per-workgroup lists and the rule above with k' = k + 24.  More: the candidate buffer
+ *       and one more rule -- a main sweep that ran with threshold +inf filtered nothing, so a buffer that did not overflow holds
+ *       every selected row, and with <= k' of them all were re-ranked: complete, padding included.  The library is exact at any
+ *       density; for a sparse one the thresholds stay +inf, a big store overflows the buffer and the queries are answered by the
+ *       fallback -- the caller routes sparse selections to ac_knn_*_topk_sel / _ids.  Where "sparse" begins: the planner's margins
+ *       say about 1/32 of the rows; measured at 256 x 1M x 768, no query takes the fallback at 1/32 (nor at 1 %, whose 10 159
+ *       selected rows still fit the candidate buffer) (profiles/knn_select/README.md).
+ * AC_EINVAL for the batch forms: d_sel NULL, d_sel not 8-byte aligned, sel_bit0 < 0 -- checked first, before any device work.
+ * Not covered: filtered range search.
  */
 int ac_knn_l2_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D,
                        const float* d_Q, int nq, int64_t ldQ, int k,
@@ -322,6 +338,20 @@ int ac_knn_ip_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D,
                        float* d_outD, double* d_outD64, int64_t* d_outI,
                        void* d_ws, size_t ws_bytes, int32_t* d_stats,
                        ac_stream_t stream);
+int ac_knn_l2_topk_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                             const uint16_t* d_planes, const float* d_norms,
+                             const float* d_Q, int nq, int64_t ldQ, int k,
+                             int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0,
+                             float* d_outD, double* d_outD64, int64_t* d_outI,
+                             void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                             ac_stream_t stream);
+int ac_knn_ip_topk_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                             const uint16_t* d_planes, const float* d_norms,
+                             const float* d_Q, int nq, int64_t ldQ, int k,
+                             int64_t row_offset, const uint64_t* d_sel, int64_t sel_bit0,
+                             float* d_outD, double* d_outD64, int64_t* d_outI,
+                             void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                             ac_stream_t stream);
 int ac_knn_l2_topk_ids(const float* d_P, int64_t N, int64_t ldP, int D,
                        const int64_t* d_ids, int64_t M,
                        const float* d_Q, int nq, int64_t ldQ, int k,

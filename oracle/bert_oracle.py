@@ -125,10 +125,11 @@ def encode_cls_roberta(model, ids, mask):
 
 
 def make_modernbert(hidden=768, layers=22, heads=12, intermediate=1152, vocab=50368, max_pos=8192, local_attention=128,
-                    global_every=3, seed=0, init_scale=1.0):
+                    global_every=3, seed=0, init_scale=1.0, norm_jitter=0.0):
     """transformers ModernBertModel (modeling_modernbert.py), fp32 / eval / eager attention, random init.
     init_scale > 1 widens the Linear weights so the attention logits are not all ~0 (a uniform softmax would
-    hide RoPE / window mistakes)."""
+    hide RoPE / window mistakes).  norm_jitter > 0 draws every LayerNorm gain from U(1 - j, 1 + j) (the init is all ones:
+    a norm applied twice, or left out after another norm, would then change nothing)."""
     from transformers import ModernBertConfig, ModernBertModel
     cfg = ModernBertConfig(vocab_size=vocab, hidden_size=hidden, intermediate_size=intermediate,
                            num_hidden_layers=layers, num_attention_heads=heads, max_position_embeddings=max_pos,
@@ -145,6 +146,12 @@ def make_modernbert(hidden=768, layers=22, heads=12, intermediate=1152, vocab=50
             for name, p in model.named_parameters():
                 if name.endswith("Wqkv.weight") or name.endswith("Wi.weight") or name.endswith("Wo.weight"):
                     p.mul_(init_scale)
+    if norm_jitter:
+        g = torch.Generator().manual_seed(seed + 29)
+        with torch.no_grad():
+            for name, p in model.named_parameters():
+                if name.endswith("norm.weight"):
+                    p.copy_(1.0 + norm_jitter * (2.0 * torch.rand(p.shape, generator=g) - 1.0))
     return model
 
 
@@ -152,3 +159,36 @@ def make_modernbert(hidden=768, layers=22, heads=12, intermediate=1152, vocab=50
 def encode_cls_modernbert(model, ids, mask):
     out = model(input_ids=ids, attention_mask=mask)
     return F.normalize(out.last_hidden_state[:, 0, :], p=2, dim=1)
+
+
+def make_distilbert(hidden=768, layers=3, heads=12, intermediate=3072, vocab=2000, max_pos=512, seed=0, qk_scale=1.0,
+                    ln_outlier=1.0):
+    """transformers DistilBertModel (the BERT block without token types; q_lin ... names), fp32 / eval / eager, random init."""
+    from transformers import DistilBertConfig, DistilBertModel
+    cfg = DistilBertConfig(vocab_size=vocab, dim=hidden, n_layers=layers, n_heads=heads, hidden_dim=intermediate,
+                           max_position_embeddings=max_pos)
+    try:
+        cfg._attn_implementation = "eager"
+    except Exception:
+        pass
+    torch.manual_seed(seed)
+    model = DistilBertModel(cfg).eval()
+    if qk_scale != 1.0 or ln_outlier != 1.0:
+        sharpen_attention(model, qk_scale, ln_outlier, seed=seed + 17)
+    return model
+
+
+def make_electra(hidden=128, layers=2, heads=2, intermediate=512, vocab=2000, max_pos=64, seed=0, qk_scale=1.0, ln_outlier=1.0):
+    """transformers ElectraModel with embedding_size == hidden_size (the BERT block under BERT's names), fp32 / eval / eager."""
+    from transformers import ElectraConfig, ElectraModel
+    cfg = ElectraConfig(vocab_size=vocab, embedding_size=hidden, hidden_size=hidden, num_hidden_layers=layers,
+                        num_attention_heads=heads, intermediate_size=intermediate, max_position_embeddings=max_pos)
+    try:
+        cfg._attn_implementation = "eager"
+    except Exception:
+        pass
+    torch.manual_seed(seed)
+    model = ElectraModel(cfg).eval()
+    if qk_scale != 1.0 or ln_outlier != 1.0:
+        sharpen_attention(model, qk_scale, ln_outlier, seed=seed + 17)
+    return model

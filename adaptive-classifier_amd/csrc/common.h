@@ -369,6 +369,26 @@ int knn_exact_tail(bool ip, const MergeParams& mp, const ExactPlan& ep, int nq, 
                    const float* sel_thr = nullptr);
 int knn_small_exact_launch(bool ip, const MergeParams& mp, int nq, int npow2, hipStream_t stream, const SelArgs* sel = nullptr);
 
+// knn_l2.hip: the planner rule and host helpers of the fp32 row-stream sweeps (knn_stream.h), shared by the top-k search
+// (knn_l2.hip) and the range search (knn_range.hip)
+struct KnnSweepShape {
+    int Dp = 0;           // round_up(D, 4)
+    int ng = 0;           // k-groups per 16-row tile
+    int kp = 0, cap = 0;  // candidates kept per list (k + pad); list capacity, a power of two >= 2 kp
+    bool small = false;   // (k, D) is outside the sweep -- a 16-query tile + its lists exceed the LDS limit, or k > AC_KNN_MAX_K --
+                          // and the store is small enough (N <= kKnnSmallN) for the small-store path
+};
+// validates (N, D, nq, k) and decides sweep / small store / refused (AC_EUNSUPPORTED), with the error text set
+int knn_sweep_shape(int64_t N, int D, int nq, int k, KnnSweepShape* s);
+size_t knn_query_tile_bytes(int TQ, int ng);         // LDS of a staged tile of TQ queries
+double knn_sweep_gamma0(int ng);                     // |sweep value - exact| <= gamma0 (|p| + |q|)^2 for the k-loop of knn_stream.h
+// row groups of a sweep grid sized to ONE residency round: blocks co-resident on a CU (occupancy of `kernel` at kThreads and `lds`
+// bytes, clamped to 1 .. 2; kernel = NULL: one) x CUs, shared among nqt query tiles; >= 1, then at most ntiles (0 for an empty store)
+int64_t knn_residency_groups(const void* kernel, size_t lds, int nqt, int64_t ntiles);
+const float* knn_zeros_device();                     // >= 16 B of zeros on the current device: the sweeps' tail-group loads read it
+// d_P / ldP / alignment of a non-empty store; `who` prefixes the error text ("knn", "knn range")
+int knn_check_store(const char* who, const float* d_P, int64_t ldP, int Dp);
+
 // Per-call options (ac_bert_config.gemm_arith_opt / ln_fusion_opt / one_launch_opt): for the duration of ONE native call on the
 // calling thread they take precedence over the process-wide switches (ac_gemm_set_arith, ac_gemm_set_ln_fusion,
 // ac_set_persistent_kernels), which remain as test / A-B hooks and as the default of calls that do not say.  Thread-local and

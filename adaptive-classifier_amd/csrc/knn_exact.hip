@@ -14,6 +14,7 @@
 // workspace plan of stages 1 - 2 (knn_exact_plan) and ONE driver that launches them (knn_exact_tail), used by the fp32, plane and
 // batch routes alike; the shard merges and score utilities (ac_topk_merge*, ac_rows_to_class, ac_proto_scores) close the file.
 #include "common.h"
+#include "knn_stream.h"
 
 #include <float.h>
 #include <math.h>
@@ -24,7 +25,12 @@ using ac::MergeParams;
 using ac::SelArgs;
 using ac::fkey;
 using ac::fkey_inv;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using acknn::f32x4;
+// the exact fp64 value of a (row, query) pair, defined once for every search (knn_stream.h)
+using acknn::exact_term;
+using acknn::exact_wave;
+using acknn::exact_wave_sum;
+using acknn::exact_lane;
 
 // --------------------------------------------------------------------------------------
 // merge + exact re-rank + certificate.  One block (256 threads) per query.
@@ -33,17 +39,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // ascending, ties to the lower id -- the order the L2 stages already implement on their distances.  Negation is exact in fp32
 // and fp64, so the key order is the descending order of p.q; none of the stages assumes a non-negative key (they compare
 // doubles with `<` / `==`, and their padding, +inf with id 0x7fffffff, stays last).  The key is negated back once, where a
-// result is written.  exact_term = one fp64 accumulation step of the exact value: (p - q)^2, or p q (an fp32 product is exact in
-// fp64, so fma(p, q, acc) is the fp64 sum of the exact products).
-template <bool IP>
-__device__ __forceinline__ double exact_term(float p, float q, double acc) {
-    if constexpr (IP) {
-        return fma((double)p, (double)q, acc);
-    } else {
-        const double e = (double)p - (double)q;
-        return fma(e, e, acc);
-    }
-}
+// result is written.
 // one output slot: a hit (its exact key, local row id) or faiss-style padding -- (FLT_MAX, -1) for L2, (-FLT_MAX, -1) for IP
 template <bool IP>
 __device__ __forceinline__ void emit_hit(const MergeParams& prm, size_t at, bool real, double key, int64_t id) {
@@ -265,9 +261,7 @@ __device__ __forceinline__ void knn_merge_rerank_body(const MergeParams& prm, ch
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
-            double a = (acc[u][0] + acc[u][1]) + (acc[u][2] + acc[u][3]);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
+            const double a = exact_wave_sum(acc[u][0], acc[u][1], acc[u][2], acc[u][3]);
             if (lane == 0 && s0 + u < ns) exact[s0 + u] = IP ? -a : a;          // (inner product: the key -(p.q))
         }
     }
@@ -458,17 +452,8 @@ __device__ __forceinline__ void knn_exact_fallback_query(const MergeParams& prm,
             const int64_t row = base + (int64_t)m * kFbWaves + wave;
             if (row >= row_hi) break;
             if constexpr (SEL) { if (!row_selected(*sa, row)) continue; }      // (wave-uniform: a wave scans one row)
-            const f32x4* prow = reinterpret_cast<const f32x4*>(prm.P + (size_t)row * prm.ldP);
-            double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            for (int c4 = lane; c4 < nc4; c4 += 64) {
-                const f32x4 p = prow[c4];
-                const f32x4 qq = *reinterpret_cast<const f32x4*>(qrow + 4 * c4);
-                a0 = exact_term<IP>(p.x, qq.x, a0); a1 = exact_term<IP>(p.y, qq.y, a1);
-                a2 = exact_term<IP>(p.z, qq.z, a2); a3 = exact_term<IP>(p.w, qq.w, a3);
-            }
-            double a = (a0 + a1) + (a2 + a3);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
+            double a = exact_wave<IP>(prm.P + (size_t)row * prm.ldP, nc4, lane,
+                                      [&](int c4) { return *reinterpret_cast<const f32x4*>(qrow + 4 * c4); });      // (the query sits in LDS, zero padded)
             if (IP) a = -a;                 // (inner product: the key -(p.q); the same bits knn_merge_rerank computes for this row)
             if (lane == 0 && (a < td || (a == td && (int32_t)row < ti))) {
                 const int s = atomicAdd(&misc[0], 1);
@@ -648,14 +633,7 @@ __device__ __forceinline__ void knn_small_exact_body(const MergeParams& prm, int
         }
         if (MODE == 0 ? r < prm.N : have) {
             const float* p = prm.P + (size_t)(MODE == 2 ? row : (int64_t)r) * prm.ldP;
-            double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-            int c = 0;
-            for (; c + 3 < prm.D; c += 4) {
-                a0 = exact_term<IP>(p[c], qv[c], a0); a1 = exact_term<IP>(p[c + 1], qv[c + 1], a1);
-                a2 = exact_term<IP>(p[c + 2], qv[c + 2], a2); a3 = exact_term<IP>(p[c + 3], qv[c + 3], a3);
-            }
-            for (; c < prm.D; ++c) a0 = exact_term<IP>(p[c], qv[c], a0);
-            a = (a0 + a1) + (a2 + a3);
+            a = exact_lane<IP>(p, qv, prm.D);
             if (IP) a = -a;                                      // (inner product: the key -(p.q))
         }
         ds[r] = a;

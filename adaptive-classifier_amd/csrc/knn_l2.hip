@@ -5,14 +5,16 @@
 //
 // This file: the three sweeps that build the candidate lists, their planners and the search entry points.  Every route ends in
 // the exact stages of knn_exact.hip (merge + fp64 re-rank + certificate, exact fallback), all on one stream, no host
-// synchronisation:
+// synchronisation.  The planner rule and the host helpers the range search shares (ac::knn_sweep_shape and what follows it in
+// common.h) are defined here too:
 //
 //  knn_sweep<TQ>      the HBM sweep.  Every prototype row is read from HBM exactly once per
-//                     query tile of TQ queries.  The query tile lives in LDS, pre-scaled by -2
-//                     and pre-arranged in MFMA B-fragment order; prototype rows stream
-//                     HBM -> VGPR (float4 per lane, no LDS round trip: nothing is shared between
-//                     waves) and go straight into v_mfma_f32_32x32x2_f32 / _16x16x4_f32 as the
-//                     A operand.  acc[row][query] = |p|^2 - 2 q.p  (|p|^2 is folded in by one
+//                     query tile of TQ queries.  Load path and k-loop are the fp32 row-stream core of knn_stream.h
+//                     (stage_queries + stream_tiles), which the range search's knn_range_sweep (knn_range.hip) runs on too:
+//                     the query tile lives in LDS, pre-scaled by -2 and pre-arranged in MFMA B-fragment order; prototype
+//                     rows stream HBM -> VGPR (float4 per lane, no LDS round trip: nothing is shared between
+//                     waves) and go straight into v_mfma_f32_16x16x4_f32 as the A operand.  What is written here is the
+//                     epilogue: acc[row][query] = |p|^2 - 2 q.p  (|p|^2 is folded in by one
 //                     extra MFMA whose A operand is the lane's running sum of squares).
 //                     Each lane owns ONE query column, so the running threshold tau_q is one
 //                     register; a candidate is pushed to the block's per-query LDS list only if
@@ -28,6 +30,7 @@
 // Roofline: algorithmic bytes per sweep = N*D*4; MFMA time at TQ=32 is
 // 16 B/clk/CU (> the 10.3 B/clk/CU HBM feed), so the sweep is HBM-bound for nq <= 32.
 #include "common.h"
+#include "knn_stream.h"
 
 #include <float.h>
 #include <math.h>
@@ -35,35 +38,17 @@
 
 namespace {
 
+using namespace acknn;       // the shared streaming core: f32x4, kWaves / kThreads / kGroup / kLdsLimit, Shape, xcd_remap, stream_tiles
 using ac::ExactPlan;
 using ac::MergeParams;
 using ac::fkey;
 using ac::fkey_inv;
 using ac::next_pow2;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kWaves = 8;               // waves per sweep block (2 per SIMD)
-constexpr int kThreads = kWaves * 64;
-constexpr int kGroup = 8;               // float4 loads in flight per lane per buffer
 constexpr int kPad = 8;                 // extra candidates kept beyond k
 constexpr int kMergeMaxCand = 32768;    // G * k' limit (merge kernel keeps 32-bit keys in LDS)
-constexpr int kLdsLimit = 160 * 1024;
-
-// One MFMA shape for every query-tile width: v_mfma_f32_16x16x4_f32.  A lane (row i = lane & 15,
-// k-slice h = lane >> 4) loads float4 P[row0 + i][16*kb + 4*h ..]: 16 rows x 64 contiguous bytes per
-// wave load (two instructions per 128-B line; the 32x32x2 shape would touch 32 rows x 32 B).  A query
-// tile is J sub-tiles of 16 queries; the A fragment is reused for the J B-fragments.
-struct Shape {
-    static constexpr int ROWS = 16, KSPLIT = 4, NACC = 4, KCOLS = 16;
-    typedef f32x4 acc_t;
-    static __device__ __forceinline__ acc_t mfma(float a, float b, acc_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-    }
-    // C/D layout: col = lane & 15, row = 4 * (lane >> 4) + r
-    static __device__ __forceinline__ int acc_row(int r, int lane) { return 4 * (lane >> 4) + r; }
-};
 
 __device__ __attribute__((aligned(16))) float g_knn_zeros[64];     // zero-initialised; tail-group loads of the sweep read it
 
@@ -122,15 +107,6 @@ __device__ __forceinline__ void sweep_sel_apply(f32x4& acc, uint32_t bits, int l
         if (!((bits >> Shape::acc_row(r, lane)) & 1u)) acc[r] = INFINITY;
 }
 
-// XCD-aware block id remap (cdna guide T1, bijective form): hardware places block b on XCD
-// b % 8; give each XCD a contiguous range of virtual ids so that the nqt query-tile blocks
-// of one row group (consecutive virtual ids) share one L2.
-__device__ __forceinline__ int xcd_remap(int b, int nblk) {
-    const int x = b & 7, s = b >> 3;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + s;
-}
 
 // Wave-level prune of one candidate list: keep the kp smallest by (d, id), compacted to the front (in no particular order --
 // nothing downstream reads the lists as sorted: the merge radix-selects over all of them); update cnt and tau.  n <= cap <= 512.
@@ -245,80 +221,21 @@ __global__ __launch_bounds__(kThreads, (SEL && J == 1) ? 4 : 2) void knn_sweep(t
     float* tau_s = reinterpret_cast<float*>(cnt + TQ);
     float* wmax_s = tau_s + TQ;                       // [kWaves]
 
-    // ---- stage the query tile: slot (jj, kb, ksub, j) = -2 * Q[qt*TQ + 16*jj + j][16*kb + 4*ksub ..+3] ----
-    {
-        const int c4_per_q = prm.ng * kGroup * S::KSPLIT;   // float4 columns per query (padded)
-        const int total = TQ * c4_per_q;
-        for (int t = tid; t < total; t += kThreads) {
-            const int j = t / c4_per_q;
-            const int c4 = t - j * c4_per_q;
-            const int kb = c4 / S::KSPLIT, ksub = c4 - kb * S::KSPLIT;
-            const int qrow = qt * TQ + j;
-            const int col = 4 * c4;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (qrow < prm.nq && col < prm.D) {
-                const float* src = prm.Q + (size_t)qrow * prm.ldQ + col;
-                val.x = -2.f * src[0];
-                if (col + 1 < prm.D) val.y = -2.f * src[1];
-                if (col + 2 < prm.D) val.z = -2.f * src[2];
-                if (col + 3 < prm.D) val.w = -2.f * src[3];
-            }
-            Qs[((j >> 4) * (prm.ng * kGroup) + kb) * 64 + ksub * 16 + (j & 15)] = val;
-        }
-        for (int t = tid; t < TQ; t += kThreads) {
-            cnt[t] = 0;
-            tau_s[t] = (qt * TQ + t < prm.nq) ? INFINITY : -INFINITY;
-        }
+    stage_queries<J>(Qs, prm.Q, prm.ldQ, prm.D, prm.nq, prm.ng, qt, tid);
+    for (int t = tid; t < TQ; t += kThreads) {
+        cnt[t] = 0;
+        tau_s[t] = (qt * TQ + t < prm.nq) ? INFINITY : -INFINITY;
     }
     __syncthreads();
 
     const int j = lane & 15;            // query column (within each sub-tile) this lane owns in C/D
-    const int ksub = lane / S::ROWS;    // k sub-slice this lane feeds in the A/B layout
-    const int arow = lane % S::ROWS;    // tile row this lane feeds in the A layout
     float tau[J];
 #pragma unroll
     for (int jj = 0; jj < J; ++jj) tau[jj] = tau_s[16 * jj + j];
     float wave_maxnorm = 0.f;
 
-    // tiles of this block: T = it * G + g
-    const int64_t my_tiles = (prm.ntiles > g) ? (prm.ntiles - 1 - g) / prm.G + 1 : 0;
-    const int ng = prm.ng;
-    const int64_t total = my_tiles * ng;
-
-    f32x4 buf[2][kGroup];
-    // prefetch state (flattened group counter -> tile, group)
-    int64_t pf_tile = 0;
-    int pf_grp = 0;
-    const float* pf_ptr;
-    auto tile_rowptr = [&](int64_t it) -> const float* {
-        int64_t row = (it * prm.G + g) * (int64_t)(kWaves * S::ROWS) + wave * S::ROWS + arow;
-        if (row > prm.N - 1) row = prm.N - 1;
-        return prm.P + (size_t)row * prm.ldP;
-    };
-    pf_ptr = tile_rowptr(0);
-
-#define AC_PREFETCH(B)                                                                   \
-    do {                                                                                 \
-        const int kb0 = pf_grp * kGroup;                                                 \
-        if ((kb0 + kGroup) * S::KCOLS <= prm.Dp) { /* wave-uniform: whole group in bounds */ \
-            _Pragma("unroll") for (int u = 0; u < kGroup; ++u)                           \
-                buf[B][u] = *reinterpret_cast<const f32x4*>(pf_ptr + 4 * ksub + (kb0 + u) * S::KCOLS); \
-        } else { /* tail group: out-of-range float4s are fetched from a zero block instead */ \
-            _Pragma("unroll") for (int u = 0; u < kGroup; ++u) {                         \
-                const int col = (kb0 + u) * S::KCOLS + 4 * ksub;                         \
-                const float* src = col < prm.Dp ? pf_ptr + col : prm.zeros;              \
-                buf[B][u] = *reinterpret_cast<const f32x4*>(src);                        \
-            }                                                                            \
-        }                                                                                \
-        if (++pf_grp == ng) { pf_grp = 0; ++pf_tile; pf_ptr = tile_rowptr(pf_tile); }    \
-    } while (0)
-
-    acc_t acc[J];
-    float nsq = 0.f;
-    int64_t cur_tile = 0;
-    int cur_grp = 0;
-
-    auto epilogue = [&]() {
+    // per 16-row tile of this wave: fold, selection, list push / prune
+    auto epilogue = [&](acc_t (&acc)[J], float nsq, int64_t row_base) {
         // fold |p|^2 in: A = this lane's partial sum of squares, B = 1  (inner product: v = -2 p.q, nothing to fold)
         if constexpr (!IP) {
 #pragma unroll
@@ -330,7 +247,6 @@ __global__ __launch_bounds__(kThreads, (SEL && J == 1) ? 4 : 2) void knn_sweep(t
         rn += __shfl_xor(rn, 32);
         wave_maxnorm = fmaxf(wave_maxnorm, rn);
 
-        const int64_t row_base = (cur_tile * prm.G + g) * (int64_t)(kWaves * S::ROWS) + wave * S::ROWS;
         if constexpr (SEL) {
             const uint32_t sbits = sweep_sel_bits(prm.sel, prm.sel_bit0, prm.N, row_base);
 #pragma unroll
@@ -382,51 +298,8 @@ __global__ __launch_bounds__(kThreads, (SEL && J == 1) ? 4 : 2) void knn_sweep(t
             if (J > 1) tau[J - 1] = tau_s[16 * (J - 1) + j];     // J is 1 or 2
             pend = true;   // re-test un-pushed entries against the tightened tau
         }
-        nsq = 0.f;
     };
-
-#define AC_COMPUTE(B)                                                                    \
-    do {                                                                                 \
-        if (cur_grp == 0) {                                                              \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj)                             \
-                _Pragma("unroll") for (int r = 0; r < S::NACC; ++r) acc[jj][r] = 0.f;    \
-        }                                                                                \
-        const f32x4* qsrc = Qs + (size_t)cur_grp * kGroup * 64 + lane;                   \
-        const size_t jstride = (size_t)ng * kGroup * 64;                                 \
-        f32x4 bq[J];                                                                     \
-        _Pragma("unroll") for (int jj = 0; jj < J; ++jj) bq[jj] = qsrc[jj * jstride];    \
-        _Pragma("unroll") for (int u = 0; u < kGroup; ++u) {                             \
-            const f32x4 a = buf[B][u];                                                   \
-            f32x4 b[J];                                                                  \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) b[jj] = bq[jj];             \
-            if (u + 1 < kGroup) { /* LDS reads one step ahead */                         \
-                _Pragma("unroll") for (int jj = 0; jj < J; ++jj) bq[jj] = qsrc[jj * jstride + (u + 1) * 64]; \
-            }                                                                            \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = S::mfma(a.x, b[jj].x, acc[jj]); \
-            nsq = fmaf(a.x, a.x, nsq); nsq = fmaf(a.y, a.y, nsq);                        \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = S::mfma(a.y, b[jj].y, acc[jj]); \
-            nsq = fmaf(a.z, a.z, nsq); nsq = fmaf(a.w, a.w, nsq);                        \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = S::mfma(a.z, b[jj].z, acc[jj]); \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = S::mfma(a.w, b[jj].w, acc[jj]); \
-            __builtin_amdgcn_sched_barrier(0); /* keep the per-load consume order */     \
-        }                                                                                \
-        if (++cur_grp == ng) { epilogue(); cur_grp = 0; ++cur_tile; }                    \
-    } while (0)
-
-    // Loads are issued unconditionally (past the end they re-read the last row, clamped in
-    // tile_rowptr) so that every path has the same number of loads in flight: a load inside a
-    // branch makes hipcc's s_waitcnt accounting wait on the buffer it has just issued.
-    if (total > 0) {
-        AC_PREFETCH(0);
-        for (int64_t gg = 0; gg < total; gg += 2) {
-            AC_PREFETCH(1);
-            AC_COMPUTE(0);
-            AC_PREFETCH(0);
-            if (gg + 1 < total) AC_COMPUTE(1);
-        }
-    }
-#undef AC_PREFETCH
-#undef AC_COMPUTE
+    stream_tiles<J>(prm.P, prm.N, prm.ldP, prm.Dp, prm.ng, prm.G, g, prm.ntiles, prm.zeros, Qs, lane, wave, epilogue);
 
     // ---- final: sort + cut every list to kp, write the block's partial result ----
     __syncthreads();
@@ -965,15 +838,6 @@ __global__ __launch_bounds__(kThreads, 2) void knn_plane_sweep(typename plane_sw
     }
 }
 
-const float* zeros_device() {                 // (the symbol has one address per device)
-    static const float* cache[64] = {nullptr};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) dev = 0;
-    if (!cache[dev]) { void* q = nullptr; (void)hipGetSymbolAddress(&q, HIP_SYMBOL(g_knn_zeros)); cache[dev] = (const float*)q; }
-    return cache[dev];
-}
-
 // ---- host-side planning ----
 struct Plan {
     bool small;          // knn_small_exact instead of the fused sweep
@@ -989,22 +853,16 @@ struct Plan {
 // AC_KNN_G (tuning experiments): the sweep grid's row groups; each planner applies its own clamp.  0 = not set
 static int64_t env_knn_g() { const char* e = getenv("AC_KNN_G"); const int64_t v = e ? atoll(e) : 0; return v >= 1 ? v : 0; }
 
+// LDS behind the query tile of knn_sweep / knn_sweep_ring: the lists (value + id), cnt[], tau[], the waves' row-norm maxima
+static size_t sweep_list_bytes(int TQ, int cap) { return (size_t)TQ * cap * 8 + TQ * 8 + kWaves * 4 + 64; }
+
 static int make_plan(int64_t N, int D, int nq, int k, Plan* pl) {
-    AC_REQUIRE(N >= 0 && N < 2147483647LL, AC_EINVAL, "knn: N=%lld out of range", (long long)N);
-    AC_REQUIRE(D >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "knn: bad D=%d nq=%d k=%d", D, nq, k);
     *pl = Plan{};
-    pl->Dp = (D + 3) / 4 * 4;
-    pl->kp = k + kPad;
-    pl->cap = next_pow2(2 * pl->kp);
-    if (pl->cap < 64) pl->cap = 64;
-    pl->ng = (pl->Dp + 16 * kGroup - 1) / (16 * kGroup);
-    // does the fused sweep cover (D, k)?  LDS: one 16-query tile + its candidate lists
-    const size_t lds16 = (size_t)pl->ng * kGroup * 64 * 16 + (size_t)16 * pl->cap * 8 + 16 * 8 + kWaves * 4 + 64;
-    if (k > AC_KNN_MAX_K || lds16 > (size_t)kLdsLimit) {
-        AC_REQUIRE(N <= ac::kKnnSmallN, AC_EUNSUPPORTED,
-                   "knn: k=%d, D=%d is outside the fused sweep (k <= %d, query tile + lists <= %d B of LDS) and "
-                   "N=%lld exceeds the small-store path (N <= %d)", k, D, AC_KNN_MAX_K, kLdsLimit, (long long)N,
-                   ac::kKnnSmallN);
+    ac::KnnSweepShape sh;
+    const int rc = ac::knn_sweep_shape(N, D, nq, k, &sh);
+    if (rc != AC_OK) return rc;
+    pl->Dp = sh.Dp; pl->ng = sh.ng; pl->kp = sh.kp; pl->cap = sh.cap;
+    if (sh.small) {
         pl->small = true;
         pl->small_pow2 = next_pow2((int)(N > 2 ? N : 2));
         pl->TQ = 16; pl->G = 1; pl->nqt = 1;
@@ -1013,8 +871,7 @@ static int make_plan(int64_t N, int D, int nq, int k, Plan* pl) {
     }
     int TQ = nq > 16 ? 32 : 16;
     for (;;) {
-        pl->sweep_lds = (size_t)(TQ / 16) * pl->ng * kGroup * 64 * 16 + (size_t)TQ * pl->cap * 8 + TQ * 8 +
-                        kWaves * 4 + 64;
+        pl->sweep_lds = ac::knn_query_tile_bytes(TQ, pl->ng) + sweep_list_bytes(TQ, pl->cap);
         if (pl->sweep_lds <= (size_t)kLdsLimit) break;
         AC_REQUIRE(TQ == 32, AC_EUNSUPPORTED,
                    "knn: D=%d with k=%d needs %zu B of LDS (> %d); unsupported", D, k, pl->sweep_lds, kLdsLimit);
@@ -1025,27 +882,19 @@ static int make_plan(int64_t N, int D, int nq, int k, Plan* pl) {
     const int rows_per_tile = kWaves * 16;
     pl->ntiles = (N + rows_per_tile - 1) / rows_per_tile;
     const ac::DevInfo& di = ac::dev_info();
-    // blocks that are actually co-resident on a CU (VGPR/LDS limited); the grid is sized to exactly
-    // one residency round so that no CU idles in a second, partial round
     // <= 16 queries, D a multiple of 32 up to 768: the LDS-ring form (rows by non-temporal DMA, queries in registers)
     static const int ring_env = getenv("AC_KNN_RING") ? atoi(getenv("AC_KNN_RING")) : -1;      // 0 = never (A/B)
     if (TQ == 16 && pl->nqt == 1 && (D % 32) == 0 && D <= 1024 && ring_env != 0) {
-        const size_t lists = ring_qs_bytes(D <= 768 ? 24 : 32) + (size_t)TQ * pl->cap * 8 + TQ * 8 + kWaves * 4 + 64 + 64;
+        const size_t lists = ring_qs_bytes(D <= 768 ? 24 : 32) + sweep_list_bytes(TQ, pl->cap) + 64;
         // (tools/sweep_ring_bench.hip: 4 chunks per wave stream as fast as 8)
         pl->ring = (size_t)kWaves * 4 * 2048 + lists <= (size_t)kLdsLimit ? 4 : 0;
         if (pl->ring) pl->sweep_lds = (size_t)kWaves * pl->ring * 2048 + lists;
     }
-    int per_cu = 0;
-    hipError_t oe = pl->ring ? hipSuccess : (TQ == 32)
-        ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, knn_sweep<2>, kThreads, pl->sweep_lds)
-        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, knn_sweep<1>, kThreads, pl->sweep_lds);
-    if (pl->ring) per_cu = 1;                        // (8 waves at the 256-register budget fill a CU)
-    if (oe != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu > 2) per_cu = 2;
-    int64_t G = ((int64_t)di.cus * per_cu) / pl->nqt;
-    if (G < 1) G = 1;
-    if (G > pl->ntiles) G = pl->ntiles;
+    // One block per CU for the ring form (8 waves at the 256-register budget fill a CU) and for the 32-query tile: this plan also
+    // launches the FILTERED knn_sweep<2, *, true>, which needs more than 128 VGPRs, i.e. one block per CU whatever the plain form
+    // takes.  Only the 16-query tile, whose every instantiation is held to 128 VGPRs, asks the occupancy query.
+    const bool one_per_cu = pl->ring || TQ == 32;
+    int64_t G = ac::knn_residency_groups(one_per_cu ? nullptr : (const void*)knn_sweep<1>, pl->sweep_lds, pl->nqt, pl->ntiles);
     if (G > kMergeMaxCand / pl->kp) {
         G = kMergeMaxCand / pl->kp;
         if (pl->nqt == 1 && G > di.cus) G = G / di.cus * di.cus;
@@ -1071,6 +920,66 @@ static int make_plan(int64_t N, int D, int nq, int k, Plan* pl) {
 thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
 
 }  // namespace
+
+// ---- the planner rule and host helpers every fp32 row-stream sweep shares (common.h) ----
+namespace ac {
+
+int knn_sweep_shape(int64_t N, int D, int nq, int k, KnnSweepShape* s) {
+    AC_REQUIRE(N >= 0 && N < 2147483647LL, AC_EINVAL, "knn: N=%lld out of range", (long long)N);
+    AC_REQUIRE(D >= 1 && nq >= 0 && k >= 1, AC_EINVAL, "knn: bad D=%d nq=%d k=%d", D, nq, k);
+    *s = KnnSweepShape{};
+    s->Dp = (D + 3) / 4 * 4;
+    s->kp = k + kPad;
+    s->cap = next_pow2(2 * s->kp);
+    if (s->cap < 64) s->cap = 64;
+    s->ng = (s->Dp + Shape::KCOLS * kGroup - 1) / (Shape::KCOLS * kGroup);
+    // does the fused sweep cover (D, k)?  LDS: one 16-query tile + its candidate lists
+    const size_t lds16 = knn_query_tile_bytes(16, s->ng) + sweep_list_bytes(16, s->cap);
+    if (k > AC_KNN_MAX_K || lds16 > (size_t)kLdsLimit) {
+        AC_REQUIRE(N <= kKnnSmallN, AC_EUNSUPPORTED,
+                   "knn: k=%d, D=%d is outside the fused sweep (k <= %d, query tile + lists <= %d B of LDS) and "
+                   "N=%lld exceeds the small-store path (N <= %d)", k, D, AC_KNN_MAX_K, kLdsLimit, (long long)N,
+                   kKnnSmallN);
+        s->small = true;
+    }
+    return AC_OK;
+}
+
+size_t knn_query_tile_bytes(int TQ, int ng) { return (size_t)(TQ / 16) * ng * kGroup * 64 * 16; }
+
+// 1.01 n 2^-24, n = 128 ng + 16 roundings per term of stream_tiles' fp32 fma chain (acamd.h "exactness contract")
+double knn_sweep_gamma0(int ng) { return 1.01 * (double)(ng * kGroup * 16 + 16) * 5.9604644775390625e-08; }
+
+// blocks that are actually co-resident on a CU (VGPR/LDS limited); the grid is sized to exactly
+// one residency round so that no CU idles in a second, partial round
+int64_t knn_residency_groups(const void* kernel, size_t lds, int nqt, int64_t ntiles) {
+    int per_cu = 1;
+    if (kernel && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kThreads, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu > 2) per_cu = 2;
+    int64_t G = ((int64_t)dev_info().cus * per_cu) / nqt;
+    if (G < 1) G = 1;
+    if (G > ntiles) G = ntiles;       // (an empty store: 0; its callers launch nothing, or clamp to 1 for the workspace layout)
+    return G;
+}
+
+const float* knn_zeros_device() {             // a zero-initialised __device__ array: no memset launch per call (the symbol has one address per device)
+    static const float* cache[64] = {nullptr};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64) dev = 0;
+    if (!cache[dev]) { void* q = nullptr; (void)hipGetSymbolAddress(&q, HIP_SYMBOL(g_knn_zeros)); cache[dev] = (const float*)q; }
+    return cache[dev];
+}
+
+int knn_check_store(const char* who, const float* d_P, int64_t ldP, int Dp) {
+    AC_REQUIRE(d_P != nullptr, AC_EINVAL, "%s: d_P is NULL", who);
+    AC_REQUIRE(ldP >= Dp && (ldP % 4) == 0, AC_EINVAL, "%s: ldP=%lld must be a multiple of 4 and >= round_up(D,4)=%d", who, (long long)ldP, Dp);
+    AC_REQUIRE((((uintptr_t)d_P) & 15) == 0, AC_EINVAL, "%s: d_P must be 16-byte aligned", who);
+    return AC_OK;
+}
+
+}  // namespace ac
 
 extern "C" int ac_knn_set_profile_events(void* start_event, void* stop_event) {
     g_prof_start = (hipEvent_t)start_event;
@@ -1112,12 +1021,7 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
     AC_REQUIRE(ldQ >= D, AC_EINVAL, "knn: ldQ=%lld < D=%d", (long long)ldQ, D);
     AC_REQUIRE(ws_bytes >= pl.total && (d_ws || pl.total == 0), AC_EWORKSPACE,
                "knn: workspace %zu < required %zu", ws_bytes, pl.total);
-    if (N > 0) {
-        AC_REQUIRE(d_P != nullptr, AC_EINVAL, "knn: d_P is NULL");
-        AC_REQUIRE(ldP >= pl.Dp && (ldP % 4) == 0, AC_EINVAL,
-                   "knn: ldP=%lld must be a multiple of 4 and >= round_up(D,4)=%d", (long long)ldP, pl.Dp);
-        AC_REQUIRE((((uintptr_t)d_P) & 15) == 0, AC_EINVAL, "knn: d_P must be 16-byte aligned");
-    }
+    if (N > 0 && (rc = ac::knn_check_store("knn", d_P, ldP, pl.Dp)) != AC_OK) return rc;
     char* ws = (char*)d_ws;
     ac::SelArgs sa;
     sa.sel = d_sel; sa.sel_bit0 = sel_bit0;
@@ -1131,7 +1035,7 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
 
     MergeParams mp = ac::knn_merge_params(d_P, N, ldP, d_Q, ldQ, D, pl.Dp, k, pl.kp, row_offset, d_outD, d_outD64, d_outI, d_stats, ws, pl.ex);
     mp.G = pl.G; mp.nblk = pl.G * pl.nqt;
-    mp.gamma = 1.01 * (double)(pl.ng * kGroup * 16 + 16) * 5.9604644775390625e-08;    // n * 2^-24, n roundings per term
+    mp.gamma = ac::knn_sweep_gamma0(pl.ng);
     mp.part_d = (const float*)(ws + pl.off_part_d);
     mp.part_i = (const int32_t*)(ws + pl.off_part_i);
     mp.part_maxnorm = (const float*)(ws + pl.off_maxnorm);
@@ -1149,7 +1053,7 @@ static int knn_topk(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
         sp.part_d = (float*)(ws + pl.off_part_d);
         sp.part_i = (int32_t*)(ws + pl.off_part_i);
         sp.part_maxnorm = (float*)(ws + pl.off_maxnorm);
-        sp.zeros = zeros_device();                    // a zero-initialised __device__ array: no memset launch per call
+        sp.zeros = ac::knn_zeros_device();
         sp.clear_ctr = (int32_t*)(ws + pl.ex.off_fb_ctr);
         sp.clear_stats = d_stats;
         sp.sel = d_sel; sp.sel_bit0 = sel_bit0;

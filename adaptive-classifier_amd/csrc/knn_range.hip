@@ -6,26 +6,25 @@
 // by exactly one wave with plain vector stores; the only atomic is an integer sum into d_stats[0].
 //
 // Count phase, big stores (the (N, D) the fused top-k sweep covers):
-//   knn_range_sweep<J, IP>   knn_sweep's load path and k-loop (knn_l2.hip: float4 rows HBM -> VGPR, v_mfma_f32_16x16x4_f32, the
-//                            query tile in LDS pre-scaled by -2, |p|^2 folded in by one extra MFMA), restated here because the
-//                            listings of knn_l2.hip must not change.  The epilogue is new: no lists, no pruning, no barrier.  Each
-//                            lane owns one query column and classifies its 4 rows x J queries against two thresholds in
-//                            sweep-value space (see "The bound" below): certain-in, certain-out, or ambiguous.
+//   knn_range_sweep<J, IP>   the fp32 row-stream core knn_sweep runs on (knn_stream.h: stage_queries + stream_tiles -- float4 rows
+//                            HBM -> VGPR, v_mfma_f32_16x16x4_f32, the query tile in LDS pre-scaled by -2) with an epilogue of its
+//                            own: |p|^2 folded in by one extra MFMA, then no lists, no pruning, no barrier.  Each lane owns one
+//                            query column and classifies its 4 rows x J queries against two thresholds in sweep-value space (see
+//                            "The bound" below): certain-in, certain-out, or ambiguous.
 //                            Two bitmaps [nq][W] of 64-bit words (W = ceil(N / 64)): `in` and `amb`.  A wave's tile is 16 rows, so
 //                            it owns the 16-BIT PIECE (query, row / 16) of each bitmap -- a quarter of a word, written with one
-//                            plain 2-byte store by lanes 0..15.  (The issue's recommended shape has one wave write a whole word;
-//                            that needs 64 consecutive rows per wave, i.e. a different row -> wave mapping than knn_sweep's
-//                            interleaved 128-row tiles, or a trip through LDS and a barrier.  A 2-byte store touches no
-//                            neighbouring piece, so "exactly one writer, no atomic" holds at piece granularity.)  Both bitmaps
-//                            are zeroed by a memset before the sweep and only NON-ZERO pieces are stored: for a selective radius
-//                            the sweep writes next to nothing.
+//                            plain 2-byte store by lanes 0..15.  (A whole word per wave would need 64 consecutive rows per wave,
+//                            i.e. a different row -> wave mapping than the core's interleaved 128-row tiles, or a trip through LDS
+//                            and a barrier.  A 2-byte store touches no neighbouring piece, so "exactly one writer, no atomic"
+//                            holds at piece granularity.)  Both bitmaps are zeroed by a memset before the sweep and only NON-ZERO
+//                            pieces are stored: for a selective radius the sweep writes next to nothing.
 //   knn_range_resolve<IP>    one wave per (query, strip of 64 words = 4096 rows): every ambiguous pair is decided by the exact
-//                            fp64 value rounded to fp32 and compared with r_q (the wave-order reduction of knn_merge_rerank: same
-//                            bits as the top-k result), the decided bits are merged into `in` by the lane that owns the word,
+//                            fp64 value rounded to fp32 and compared with r_q (knn_stream.h's wave-order value, the one
+//                            knn_merge_rerank computes: same bits as the top-k result), the decided bits are merged into `in` by the lane that owns the word,
 //                            the strip's popcount is written.  d_stats[0] += pairs decided.
 // Count phase, small stores (N <= kKnnSmallN and a D the sweep does not cover):
 //   knn_range_small<IP>      one wave per (query, word): lane b computes the fp64 value of row 64 w + b in knn_small_exact's
-//                            order, decides, the ballot IS the word.  A strip is one word here.
+//                            (lane) order, decides, the ballot IS the word.  A strip is one word here.
 // Both:
 //   knn_range_scan           exclusive scan of the strip popcounts per query (offsets relative to the query's first hit) and of
 //                            the per-query totals across queries -> lims.  One workgroup.
@@ -35,8 +34,8 @@
 //
 // The bound (certain-in implies the fp32-ROUNDED exact value is on the right side of r):
 //   Let s be the real value the sweep approximates (L2: |p|^2 - 2 p.q, IP: -2 p.q) and v its fp32 MFMA-chain value.  knn_topk's
-//   certificate uses |v - s| <= gamma0 (|p| + |q|)^2, gamma0 = 1.01 n 2^-24, n = the chain's roundings per term; the k-loop here
-//   is the same chain, so the same bound holds.  x64 (d64 or v64, in ANY summation order) differs from the real value x by at most
+//   certificate uses |v - s| <= gamma0 (|p| + |q|)^2, gamma0 = 1.01 n 2^-24, n = the chain's roundings per term (knn_sweep_gamma0); both
+//   sweeps run the one k-loop of stream_tiles, so the same bound holds by construction.  x64 (d64 or v64, in ANY summation order) differs from the real value x by at most
 //   (D + 3) 2^-53 (|p| + |q|)^2 (L2: x <= (|p| + |q|)^2, all terms non-negative; IP: sum |p_i q_i| <= |p||q|).  The thresholds
 //   below use E = gamma (sqrt~(|p|^2~) + |q|~)^2 + 1e-30 with gamma = 1.02 gamma0: the extra 1 % covers the relative error of the
 //   fp32 row norm (<= n 2^-24 <~ 2e-4 for every D the sweep takes), of its hardware square root (1 ulp), of the fp64 |q| and the
@@ -49,80 +48,35 @@
 //   Anything else -- NaN or infinite v or E included, every comparison with them is false -- is ambiguous and decided exactly.
 //   Queries that can have no hit (NaN radius; L2 r <= 0; IP r = +inf) are switched off in the sweep: no bit, no exact decision.
 #include "common.h"
+#include "knn_stream.h"
 
 #include <float.h>
 #include <math.h>
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace acknn;       // the shared streaming core and the exact fp64 value (knn_stream.h)
 
-constexpr int kWaves = 8;               // waves per sweep block (2 per SIMD), as knn_sweep
-constexpr int kThreads = kWaves * 64;
-constexpr int kGroup = 8;               // float4 loads in flight per lane per buffer
-constexpr int kLdsLimit = 160 * 1024;
 constexpr int kStripWords = 64;         // words per strip of the big-store form (one lane per word)
 constexpr int kPostWaves = 4;           // waves per block of resolve / small / fill
 
-__device__ __attribute__((aligned(16))) float g_range_zeros[64];     // zero-initialised; tail-group loads of the sweep read it
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// XCD-aware block id remap, as knn_sweep: the nqt query-tile blocks of one row group share one L2
-__device__ __forceinline__ int xcd_remap(int b, int nblk) {
-    const int x = b & 7, s = b >> 3;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int base = (x < r) ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-    return base + s;
-}
-
-// one fp64 accumulation step of the exact value, as knn_exact.hip: (p - q)^2, or p q (an fp32 product is exact in fp64)
-template <bool IP>
-__device__ __forceinline__ double exact_term(float p, float q, double acc) {
-    if constexpr (IP) {
-        return fma((double)p, (double)q, acc);
-    } else {
-        const double e = (double)p - (double)q;
-        return fma(e, e, acc);
-    }
-}
 // the predicate of the contract, on the fp32 value the user sees; false for a NaN radius or value
 template <bool IP>
 __device__ __forceinline__ bool is_hit(double x64, float r) { return IP ? (float)x64 > r : (float)x64 < r; }
 
-// Exact value of one (row, query) pair by a whole wave, in knn_merge_rerank's order (four accumulators over c4 = lane, lane + 64,
-// ..., the (a0 + a1) + (a2 + a3) fold, the xor-shuffle tree): the bits a top-k search returns for the pair.  Columns D..Dp-1 of the
-// row are zero (the store's contract), the query is read element-wise with zeros past D.
+// Exact value of one (row, query) pair by a whole wave, in the wave order of knn_stream.h: the bits a top-k search returns for the
+// pair.  Columns D..Dp-1 of the row are zero (the store's contract), the query is read element-wise with zeros past D.
 template <bool IP>
-__device__ __forceinline__ double exact_wave(const float* prow, const float* qrow, int D, int nc4, int lane) {
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    for (int c4 = lane; c4 < nc4; c4 += 64) {
-        const f32x4 p = *reinterpret_cast<const f32x4*>(prow + 4 * c4);
+__device__ __forceinline__ double exact_wave_global(const float* prow, const float* qrow, int D, int nc4, int lane) {
+    return exact_wave<IP>(prow, nc4, lane, [&](int c4) {
         const int c = 4 * c4;
         f32x4 qq;
         qq.x = qrow[c];                                   // (c < D: c4 < nc4 = ceil(D / 4))
         qq.y = c + 1 < D ? qrow[c + 1] : 0.f;
         qq.z = c + 2 < D ? qrow[c + 2] : 0.f;
         qq.w = c + 3 < D ? qrow[c + 3] : 0.f;
-        a0 = exact_term<IP>(p.x, qq.x, a0); a1 = exact_term<IP>(p.y, qq.y, a1);
-        a2 = exact_term<IP>(p.z, qq.z, a2); a3 = exact_term<IP>(p.w, qq.w, a3);
-    }
-    double a = (a0 + a1) + (a2 + a3);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
-    return a;
-}
-// ... by one lane, in knn_small_exact's order
-template <bool IP>
-__device__ __forceinline__ double exact_lane(const float* p, const float* qv, int D) {
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    int c = 0;
-    for (; c + 3 < D; c += 4) {
-        a0 = exact_term<IP>(p[c], qv[c], a0); a1 = exact_term<IP>(p[c + 1], qv[c + 1], a1);
-        a2 = exact_term<IP>(p[c + 2], qv[c + 2], a2); a3 = exact_term<IP>(p[c + 3], qv[c + 3], a3);
-    }
-    for (; c < D; ++c) a0 = exact_term<IP>(p[c], qv[c], a0);
-    return (a0 + a1) + (a2 + a3);
+        return qq;
+    });
 }
 
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
@@ -184,57 +138,36 @@ __global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(RangeParams prm) 
     double* qn_s = cout_s + TQ;
     int* live_s = reinterpret_cast<int*>(qn_s + TQ);
 
-    // ---- stage the query tile: slot (jj, kb, ksub, j) = -2 * Q[qt*TQ + 16*jj + j][16*kb + 4*ksub ..+3] ----
-    {
-        const int c4_per_q = prm.ng * kGroup * 4;     // float4 columns per query (padded)
-        const int total = TQ * c4_per_q;
-        for (int t = tid; t < total; t += kThreads) {
-            const int j = t / c4_per_q;
-            const int c4 = t - j * c4_per_q;
-            const int kb = c4 / 4, ksub = c4 - kb * 4;
-            const int qrow = qt * TQ + j;
-            const int col = 4 * c4;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (qrow < prm.nq && col < prm.D) {
-                const float* src = prm.Q + (size_t)qrow * prm.ldQ + col;
-                val.x = -2.f * src[0];
-                if (col + 1 < prm.D) val.y = -2.f * src[1];
-                if (col + 2 < prm.D) val.z = -2.f * src[2];
-                if (col + 3 < prm.D) val.w = -2.f * src[3];
-            }
-            Qs[((j >> 4) * (prm.ng * kGroup) + kb) * 64 + ksub * 16 + (j & 15)] = val;
+    stage_queries<J>(Qs, prm.Q, prm.ldQ, prm.D, prm.nq, prm.ng, qt, tid);
+    // per-query constants of the thresholds, in fp64 (a wave per query)
+    for (int t = wave; t < TQ; t += kWaves) {
+        const int qrow = qt * TQ + t;
+        double a = 0;
+        float r = NAN;
+        if (qrow < prm.nq) {
+            const float* src = prm.Q + (size_t)qrow * prm.ldQ;
+            for (int c = lane; c < prm.D; c += 64) a = fma((double)src[c], (double)src[c], a);
+            r = prm.radius[qrow];
         }
-        // per-query constants of the thresholds, in fp64 (a wave per query)
-        for (int t = wave; t < TQ; t += kWaves) {
-            const int qrow = qt * TQ + t;
-            double a = 0;
-            float r = NAN;
-            if (qrow < prm.nq) {
-                const float* src = prm.Q + (size_t)qrow * prm.ldQ;
-                for (int c = lane; c < prm.D; c += 64) a = fma((double)src[c], (double)src[c], a);
-                r = prm.radius[qrow];
-            }
 #pragma unroll
-            for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
-            if (lane == 0) {
-                const bool live = IP ? (r < INFINITY) : (r > 0.f);            // false for NaN
-                if (IP) {
-                    cin_s[t] = -2.0 * (double)nextafterf(r, INFINITY);
-                    cout_s[t] = -2.0 * (double)r;
-                } else {
-                    cin_s[t] = (double)nextafterf(r, -INFINITY) - a;
-                    cout_s[t] = (double)r - a;
-                }
-                qn_s[t] = sqrt(a);
-                live_s[t] = live ? 1 : 0;
+        for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
+        if (lane == 0) {
+            const bool live = IP ? (r < INFINITY) : (r > 0.f);            // false for NaN
+            if (IP) {
+                cin_s[t] = -2.0 * (double)nextafterf(r, INFINITY);
+                cout_s[t] = -2.0 * (double)r;
+            } else {
+                cin_s[t] = (double)nextafterf(r, -INFINITY) - a;
+                cout_s[t] = (double)r - a;
             }
+            qn_s[t] = sqrt(a);
+            live_s[t] = live ? 1 : 0;
         }
     }
     __syncthreads();
 
     const int j = lane & 15;            // query column (within each sub-tile) this lane owns in C/D
-    const int ksub = lane >> 4;         // k sub-slice this lane feeds in the A/B layout; in C/D the lane owns rows 4 ksub + r
-    const int arow = lane & 15;         // tile row this lane feeds in the A layout
+    const int ksub = lane >> 4;         // in C/D the lane owns rows 4 ksub + r of the tile
     double cin[J], cout[J], qn[J];
     bool live[J];
 #pragma unroll
@@ -243,55 +176,19 @@ __global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(RangeParams prm) 
         live[jj] = live_s[16 * jj + j] != 0;
     }
 
-    // tiles of this block: T = it * G + g
-    const int64_t my_tiles = (prm.ntiles > g) ? (prm.ntiles - 1 - g) / prm.G + 1 : 0;
-    const int ng = prm.ng;
-    const int64_t total = my_tiles * ng;
-
-    f32x4 buf[2][kGroup];
-    int64_t pf_tile = 0;
-    int pf_grp = 0;
-    const float* pf_ptr;
-    auto tile_rowptr = [&](int64_t it) -> const float* {
-        int64_t row = (it * prm.G + g) * (int64_t)(kWaves * 16) + wave * 16 + arow;
-        if (row > prm.N - 1) row = prm.N - 1;             // past the end: the last row again (its bits are masked below)
-        return prm.P + (size_t)row * prm.ldP;
-    };
-    pf_ptr = tile_rowptr(0);
-
-#define AC_PREFETCH(B)                                                                   \
-    do {                                                                                 \
-        const int kb0 = pf_grp * kGroup;                                                 \
-        if ((kb0 + kGroup) * 16 <= prm.Dp) { /* wave-uniform: whole group in bounds */   \
-            _Pragma("unroll") for (int u = 0; u < kGroup; ++u)                           \
-                buf[B][u] = *reinterpret_cast<const f32x4*>(pf_ptr + 4 * ksub + (kb0 + u) * 16); \
-        } else { /* tail group: out-of-range float4s are fetched from a zero block instead */ \
-            _Pragma("unroll") for (int u = 0; u < kGroup; ++u) {                         \
-                const int col = (kb0 + u) * 16 + 4 * ksub;                               \
-                const float* src = col < prm.Dp ? pf_ptr + col : prm.zeros;              \
-                buf[B][u] = *reinterpret_cast<const f32x4*>(src);                        \
-            }                                                                            \
-        }                                                                                \
-        if (++pf_grp == ng) { pf_grp = 0; ++pf_tile; pf_ptr = tile_rowptr(pf_tile); }    \
-    } while (0)
-
-    f32x4 acc[J];
-    float nsq = 0.f;
-    int64_t cur_tile = 0;
-    int cur_grp = 0;
     const size_t pieces = (size_t)prm.W * 4;          // 16-bit pieces per query
     uint16_t* in16 = reinterpret_cast<uint16_t*>(prm.bm_in);
     uint16_t* amb16 = reinterpret_cast<uint16_t*>(prm.bm_amb);
 
-    auto epilogue = [&]() {
+    // per 16-row tile of this wave: classify 4 rows x J queries per lane, store the non-zero pieces
+    auto epilogue = [&](f32x4 (&acc)[J], float nsq, int64_t row_base) {
         // |p|^2 of the lane's four C/D rows: A = the lane's partial sum of squares, B = 1 (every column gets its row's sum)
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-        const f32x4 pn2 = mfma16(nsq, 1.0f, zero4);
+        const f32x4 pn2 = Shape::mfma(nsq, 1.0f, zero4);
         if constexpr (!IP) {                          // the same fold as knn_sweep: v = |p|^2 - 2 p.q
 #pragma unroll
-            for (int jj = 0; jj < J; ++jj) acc[jj] = mfma16(nsq, 1.0f, acc[jj]);
+            for (int jj = 0; jj < J; ++jj) acc[jj] = Shape::mfma(nsq, 1.0f, acc[jj]);
         }
-        const int64_t row_base = (cur_tile * prm.G + g) * (int64_t)(kWaves * 16) + wave * 16;
         double pn[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) pn[r] = (double)__builtin_amdgcn_sqrtf(pn2[r]);
@@ -320,50 +217,8 @@ __global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(RangeParams prm) 
                 if (bits >> 16) amb16[at] = (uint16_t)(bits >> 16);
             }
         }
-        nsq = 0.f;
     };
-
-#define AC_COMPUTE(B)                                                                    \
-    do {                                                                                 \
-        if (cur_grp == 0) {                                                              \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj)                             \
-                _Pragma("unroll") for (int r = 0; r < 4; ++r) acc[jj][r] = 0.f;          \
-        }                                                                                \
-        const f32x4* qsrc = Qs + (size_t)cur_grp * kGroup * 64 + lane;                   \
-        const size_t jstride = (size_t)ng * kGroup * 64;                                 \
-        f32x4 bq[J];                                                                     \
-        _Pragma("unroll") for (int jj = 0; jj < J; ++jj) bq[jj] = qsrc[jj * jstride];    \
-        _Pragma("unroll") for (int u = 0; u < kGroup; ++u) {                             \
-            const f32x4 a = buf[B][u];                                                   \
-            f32x4 b[J];                                                                  \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) b[jj] = bq[jj];             \
-            if (u + 1 < kGroup) { /* LDS reads one step ahead */                         \
-                _Pragma("unroll") for (int jj = 0; jj < J; ++jj) bq[jj] = qsrc[jj * jstride + (u + 1) * 64]; \
-            }                                                                            \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = mfma16(a.x, b[jj].x, acc[jj]); \
-            nsq = fmaf(a.x, a.x, nsq); nsq = fmaf(a.y, a.y, nsq);                        \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = mfma16(a.y, b[jj].y, acc[jj]); \
-            nsq = fmaf(a.z, a.z, nsq); nsq = fmaf(a.w, a.w, nsq);                        \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = mfma16(a.z, b[jj].z, acc[jj]); \
-            _Pragma("unroll") for (int jj = 0; jj < J; ++jj) acc[jj] = mfma16(a.w, b[jj].w, acc[jj]); \
-            __builtin_amdgcn_sched_barrier(0); /* keep the per-load consume order */     \
-        }                                                                                \
-        if (++cur_grp == ng) { epilogue(); cur_grp = 0; ++cur_tile; }                    \
-    } while (0)
-
-    // Loads are issued unconditionally (past the end they re-read the last row, clamped in tile_rowptr) so that every path has
-    // the same number of loads in flight, as in knn_sweep.
-    if (total > 0) {
-        AC_PREFETCH(0);
-        for (int64_t gg = 0; gg < total; gg += 2) {
-            AC_PREFETCH(1);
-            AC_COMPUTE(0);
-            AC_PREFETCH(0);
-            if (gg + 1 < total) AC_COMPUTE(1);
-        }
-    }
-#undef AC_PREFETCH
-#undef AC_COMPUTE
+    stream_tiles<J>(prm.P, prm.N, prm.ldP, prm.Dp, prm.ng, prm.G, g, prm.ntiles, prm.zeros, Qs, lane, wave, epilogue);
 }
 
 // one wave per (query, strip): decide the ambiguous pairs exactly, merge them into `in`, count the strip's hits
@@ -392,7 +247,7 @@ __global__ __launch_bounds__(kPostWaves * 64) void knn_range_resolve(RangeParams
             while (aw) {
                 const int b = __builtin_ctzll(aw);
                 aw &= aw - 1;
-                const double x = exact_wave<IP>(prm.P + (size_t)(row0 + b) * prm.ldP, qrow, prm.D, nc4, lane);      // (row < N: the sweep masks)
+                const double x = exact_wave_global<IP>(prm.P + (size_t)(row0 + b) * prm.ldP, qrow, prm.D, nc4, lane);      // (row < N: the sweep masks)
                 if (lane == l && is_hit<IP>(x, r)) in |= 1ull << b;
                 ++decided;
             }
@@ -505,7 +360,7 @@ __global__ __launch_bounds__(kPostWaves * 64) void knn_range_fill(RangeParams pr
             while (iw) {
                 const int b = __builtin_ctzll(iw);
                 iw &= iw - 1;
-                const double x = exact_wave<IP>(prm.P + (size_t)(row0 + b) * prm.ldP, qrow, prm.D, nc4, lane);
+                const double x = exact_wave_global<IP>(prm.P + (size_t)(row0 + b) * prm.ldP, qrow, prm.D, nc4, lane);
                 if (lane == 0) {                          // pos < lims[nq] <= capacity
                     prm.outD[pos] = (float)x;
                     if (prm.outD64) prm.outD64[pos] = x;
@@ -529,24 +384,21 @@ struct RangePlan {
 
 // The layout depends on (N, D, nq) alone (count and fill plan it independently and must agree); the sweep's grid is chosen at launch.
 int make_range_plan(int64_t N, int D, int nq, RangePlan* pl) {
-    // accept / reject and error texts are the top-k planner's at k = 1
-    size_t topk_bytes = 0;
-    const int rc = ac_knn_l2_topk_workspace(N, D, nq, 1, &topk_bytes);
+    // accept / reject, error texts and the small-store verdict are the top-k planner's at k = 1 (the sweep keeps no lists, but a
+    // (N, D) that one search takes the other takes too)
+    ac::KnnSweepShape sh;
+    const int rc = ac::knn_sweep_shape(N, D, nq, 1, &sh);
     if (rc != AC_OK) return rc;
     *pl = RangePlan{};
-    pl->Dp = (D + 3) / 4 * 4;
-    pl->ng = (pl->Dp + 16 * kGroup - 1) / (16 * kGroup);
-    // the rule of knn_l2.hip's make_plan at k = 1 (kp = 9, cap = 64): does a 16-query tile and its lists fit in LDS?
-    const size_t lds16 = (size_t)pl->ng * kGroup * 64 * 16 + (size_t)16 * 64 * 8 + 16 * 8 + kWaves * 4 + 64;
-    pl->small = lds16 > (size_t)kLdsLimit;               // (then N <= kKnnSmallN, or the planner above has refused)
+    pl->Dp = sh.Dp; pl->ng = sh.ng; pl->small = sh.small;
     pl->W = (N + 63) / 64;
     pl->S = pl->small ? pl->W : (pl->W + kStripWords - 1) / kStripWords;
-    auto lds_for = [&](int TQ) { return (size_t)(TQ / 16) * pl->ng * kGroup * 64 * 16 + (size_t)TQ * 28 + 64; };
+    auto lds_for = [&](int TQ) { return ac::knn_query_tile_bytes(TQ, pl->ng) + (size_t)TQ * 28 + 64; };
     pl->TQ = (nq > 16 && lds_for(32) <= (size_t)kLdsLimit) ? 32 : 16;
     pl->sweep_lds = lds_for(pl->TQ);
     pl->nqt = nq > 0 ? (nq + pl->TQ - 1) / pl->TQ : 1;
     pl->ntiles = (N + kWaves * 16 - 1) / (kWaves * 16);
-    pl->gamma = 1.02 * (1.01 * (double)(pl->ng * kGroup * 16 + 16) * 5.9604644775390625e-08);
+    pl->gamma = 1.02 * ac::knn_sweep_gamma0(pl->ng);
     const size_t nqs = (size_t)(nq > 0 ? nq : 1);
     ac::WsTake take;
     pl->off_in = take(nqs * pl->W * 8);
@@ -557,27 +409,12 @@ int make_range_plan(int64_t N, int D, int nq, RangePlan* pl) {
     return AC_OK;
 }
 
-const float* range_zeros_device() {
-    static const float* cache[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) dev = 0;
-    if (!cache[dev]) { void* q = nullptr; (void)hipGetSymbolAddress(&q, HIP_SYMBOL(g_range_zeros)); cache[dev] = (const float*)q; }
-    return cache[dev];
-}
-
 int range_validate(const RangePlan& pl, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int64_t ldQ, void* d_ws,
                    size_t ws_bytes) {
     AC_REQUIRE(d_Q != nullptr, AC_EINVAL, "knn range: null pointer");
     AC_REQUIRE(ldQ >= D, AC_EINVAL, "knn range: ldQ=%lld < D=%d", (long long)ldQ, D);
     AC_REQUIRE(ws_bytes >= pl.total && d_ws, AC_EWORKSPACE, "knn range: workspace %zu < required %zu", ws_bytes, pl.total);
-    if (N > 0) {
-        AC_REQUIRE(d_P != nullptr, AC_EINVAL, "knn range: d_P is NULL");
-        AC_REQUIRE(ldP >= pl.Dp && (ldP % 4) == 0, AC_EINVAL,
-                   "knn range: ldP=%lld must be a multiple of 4 and >= round_up(D,4)=%d", (long long)ldP, pl.Dp);
-        AC_REQUIRE((((uintptr_t)d_P) & 15) == 0, AC_EINVAL, "knn range: d_P must be 16-byte aligned");
-    }
-    return AC_OK;
+    return N > 0 ? ac::knn_check_store("knn range", d_P, ldP, pl.Dp) : AC_OK;
 }
 
 RangeParams range_params(const RangePlan& pl, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ,
@@ -624,16 +461,9 @@ int range_count(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const 
         if (pl.TQ == 32) sweep_fn = ip ? knn_range_sweep<2, true> : knn_range_sweep<2, false>;
         else sweep_fn = ip ? knn_range_sweep<1, true> : knn_range_sweep<1, false>;
         AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
-        // one residency round, as knn_sweep's planner: blocks that are co-resident on a CU (VGPR / LDS limited)
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sweep_fn, kThreads, pl.sweep_lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 1; }
-        if (per_cu < 1) per_cu = 1;
-        if (per_cu > 2) per_cu = 2;
-        int64_t G = ((int64_t)ac::dev_info().cus * per_cu) / pl.nqt;
-        if (G > pl.ntiles) G = pl.ntiles;
-        if (G < 1) G = 1;
+        const int64_t G = ac::knn_residency_groups((const void*)sweep_fn, pl.sweep_lds, pl.nqt, pl.ntiles);
         p.G = (int)G;
-        p.zeros = range_zeros_device();
+        p.zeros = ac::knn_zeros_device();
         hipLaunchKernelGGL(sweep_fn, dim3((unsigned)(G * pl.nqt)), dim3(kThreads), pl.sweep_lds, stream, p);
         AC_LAUNCH_CHECK();
         void (*res_fn)(RangeParams) = ip ? knn_range_resolve<true> : knn_range_resolve<false>;

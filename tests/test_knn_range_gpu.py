@@ -216,6 +216,13 @@ def test_edge_radii_empty_inputs_offsets_and_capacity(cuda_dev):
         assert L.ac_knn_l2_range_count(nv.ptr(store), 1000, store.stride(0), 48, nv.ptr(Qd), 6, Qd.stride(0), nv.ptr(rd), nv.ptr(lims_d),
                                        nv.ptr(ws), 16, nv.ptr(stats), nv.stream_ptr(cuda_dev)) == -3
     assert ix.knn_range_workspace_bytes(1000, 48, 6) == b.value
+    # one planner rule for both searches (a 16-query tile + the k = 1 lists against the LDS limit): D = 2304 is the last dimension
+    # the sweep takes (ng = 18: 155 872 B), D = 2308 the first it does not (ng = 19: 164 064 B > 163 840), and then only a store of
+    # <= 8192 rows is searched.  Host-only calls.
+    t = ctypes.c_size_t(0)
+    for N, D, want in ((8193, 2304, 0), (8192, 2308, 0), (8193, 2308, -2)):
+        assert L.ac_knn_range_workspace(N, D, 6, ctypes.byref(b)) == want, (N, D)
+        assert L.ac_knn_l2_topk_workspace(N, D, 6, 1, ctypes.byref(t)) == want, (N, D)
 
 
 # ---- 5. consistency with search ------------------------------------------------------------------------------------------------

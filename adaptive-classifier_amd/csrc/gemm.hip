@@ -23,6 +23,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <type_traits>
 
 namespace {
 
@@ -32,8 +33,8 @@ using namespace acg;
 // LDS-tiled NT kernel: (64*TM) x 128 x 32 block tile, 4 waves as 2(M) x 2(N), wave tile (32*TM) x 64.
 //   TM = 2: 128x128 tile, 64 KB LDS, 2 blocks/CU        TM = 1: 64x128 tile, 48 KB LDS, 3 blocks/CU
 // ---------------------------------------------------------------------------------------------
-constexpr int BN = 128, BK = 32;
-constexpr int kTileThreads = 256;
+constexpr int BN = kTileN, BK = kStageK;
+constexpr int kTileThreads = kBlock4;
 
 // slot of (row, c4) inside an operand image laid out [row groups of 32][4 k-blocks of 8][64 float4]
 __device__ __forceinline__ int tile_slot(int row, int c4) {   // c4 in [0,8)
@@ -644,7 +645,7 @@ __global__ __launch_bounds__(256) void gemm_direct_pair(DirectProblem p1, Direct
 // fp32 products, fp32 accumulation), the next slot's loads are in flight under the current slot's 8 MFMAs, and the 8 partial
 // tiles meet in LDS in a fixed order.  One launch, ~5 us for the head's layers.
 // ---------------------------------------------------------------------------------------------
-constexpr int kFtWaves = 8;
+constexpr int kFtWaves = kBlock8 / 64;
 __global__ __launch_bounds__(kFtWaves * 64) void gemm_fewtiles_nt(const float* __restrict__ A, int64_t lda,
                                                                   const float* __restrict__ W, int64_t ldw,
                                                                   float* __restrict__ C, int64_t ldc, int M, int N, int K,
@@ -700,14 +701,6 @@ __global__ __launch_bounds__(kFtWaves * 64) void gemm_fewtiles_nt(const float* _
         if (row < M && col < N) C[row * ldc + col] = apply_epilogue(epi, v, row, col, C, ldc, N);
     }
 }
-// (the shapes it takes: see the comment above; `aligned` = 16-byte aligned bases and lda, ldw multiples of 4)
-static bool fewtiles_takes(int M, int N, int K, bool aligned) {
-    if (const char* e = getenv("AC_GEMM_FEWTILES")) { if (atoi(e) == 0) return false; }
-    const int64_t t64 = (int64_t)((M + 63) / 64) * ((N + BN - 1) / BN);
-    // (<= 512 rows and <= 2^30 multiply-adds: beyond, the fp32 matrix pipe -- 1/16 of the bf16 one -- is the bound, not latency)
-    return aligned && M >= 65 && M <= 512 && (K % 8) == 0 && K >= 64 && 2 * t64 <= ac::dev_info().cus &&
-           (int64_t)M * N * K <= ((int64_t)1 << 30);
-}
 
 // ---------------------------------------------------------------------------------------------
 // small-M NT kernel (M <= 64): weight streaming.  out[m][n] = sum_k X[m][k] W[n][k] is computed as
@@ -717,7 +710,7 @@ static bool fewtiles_takes(int M, int N, int K, bool aligned) {
 // reduced through LDS in a fixed order.  With M this small the GEMM is bound by streaming W once, so
 // parallelism over (N/16 blocks) x (8 waves) and loads-in-flight matter, not MFMA efficiency.
 // ---------------------------------------------------------------------------------------------
-constexpr int kSmWaves = 8;
+constexpr int kSmWaves = kBlock8 / 64;
 // k-blocks (16 columns each) per register buffer; two buffers of (1 + J) float4 per k-block
 template <int J> struct SmGroup { static constexpr int value = (J >= 4) ? 3 : 6; };
 
@@ -796,137 +789,60 @@ __global__ __launch_bounds__(kSmWaves * 64) void gemm_smallm_nt(const float* __r
     }
 }
 
-static int launch_gemm(bool a_kmaj, bool b_kmaj, const float* A, int64_t lda, const float* B, int64_t ldb,
-                       float* C, int64_t ldc, int M, int N, int K, const Epilogue& epi, hipStream_t stream,
-                       const uint16_t* Bp = nullptr, int64_t b_rows = 0, const uint16_t* Ap = nullptr,
+// ---- plan -> launch: gemm_plan.h decides; one template per kernel family turns the plan's runtime selectors into template arguments
+// and hands the instantiation to `go`, which launches it with the family's argument list ----
+// f(std::integral_constant<int, V>) for the V among Vs that equals v; false when none does (the kernel is not built)
+template <int... Vs, class F> static bool pick(int v, F&& f) { return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+template <class L> static bool launch_smallm(const GemmPlan& p, L&& go) { return pick<1, 2, 4>(p.J, [&](auto J) { go(gemm_smallm_nt<decltype(J)::value>); }); }
+template <bool SPLIT, class L> static bool launch_tiled(const GemmPlan& p, L&& go) {           // fp32 operands: gemm_split_nt | gemm_tile_nt
+    return pick<EPI_GENERIC, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_BIAS_RELU>(p.cls, [&](auto E) { pick<1, 2>(p.tm, [&](auto TM) {
+        if constexpr (SPLIT) go(gemm_split_nt<decltype(E)::value, decltype(TM)::value>); else go(gemm_tile_nt<decltype(E)::value, decltype(TM)::value>);
+    }); });
+}
+// W as planes.  Built: fp32 rows out -- all five classes on the 4-wave tile (A fp32 or planes), bias / +GELU / +residual on the 8-wave
+// one; planes out (A as planes) -- bias / +GELU / GeGLU on both
+template <bool CP, int WMW, class L> static bool launch_planes(const GemmPlan& p, L&& go) {
+    auto one = [&](auto E) {
+        if constexpr (WMW == 4) go(gemm_planes_nt<decltype(E)::value, 2, true, CP, 4>);
+        else pick<1, 2>(p.tm, [&](auto TM) {
+            if (CP || p.a_planes) go(gemm_planes_nt<decltype(E)::value, decltype(TM)::value, true, CP, 2>);
+            else if constexpr (!CP) go(gemm_planes_nt<decltype(E)::value, decltype(TM)::value, false, false, 2>);
+        });
+    };
+    if constexpr (CP) return pick<EPI_BIAS, EPI_BIAS_GELU, EPI_GEGLU32>(p.cls, one);
+    else if constexpr (WMW == 4) return pick<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES>(p.cls, one);
+    else return pick<EPI_GENERIC, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RES, EPI_BIAS_RELU>(p.cls, one);
+}
+template <class L> static void launch_direct(bool ak, bool bk, L&& go) { pick<0, 1>(ak, [&](auto AK) { pick<0, 1>(bk, [&](auto BKM) { go(gemm_direct<decltype(AK)::value != 0, decltype(BKM)::value != 0>); }); }); }
+
+static int launch_gemm(bool a_kmaj, bool b_kmaj, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
+                       const Epilogue& epi, hipStream_t stream, const uint16_t* Bp = nullptr, int64_t b_rows = 0, const uint16_t* Ap = nullptr,
                        int64_t a_rows = 0, uint16_t* Cp = nullptr) {
     if (M <= 0 || N <= 0) return AC_OK;
-    const bool aligned = ((lda & 3) == 0) && ((ldb & 3) == 0) && ((((uintptr_t)A) & 15) == 0) &&
-                         ((((uintptr_t)B) & 15) == 0);
-    AC_REQUIRE(epi.act != ACT_GEGLU32 || (Cp && Ap), AC_EUNSUPPORTED, "gemm: fused GeGLU needs the pre-split kernel");
-    AC_REQUIRE((!Ap && !Cp) || (a_kmaj && b_kmaj && aligned && ac::linear_takes_planes(M, N, K) && Bp),
-               AC_EUNSUPPORTED, "gemm: operand / result planes given for a shape that does not take the pre-split kernel");
-    if (a_kmaj && b_kmaj && aligned && M <= 64 && K >= 8 && (K % 4) == 0 && N >= 16) {
-        const dim3 grid((N + 15) / 16), block(kSmWaves * 64);
-        if (M <= 16) hipLaunchKernelGGL((gemm_smallm_nt<1>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
-        else if (M <= 32) hipLaunchKernelGGL((gemm_smallm_nt<2>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
-        else hipLaunchKernelGGL((gemm_smallm_nt<4>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
-    } else if (a_kmaj && b_kmaj && !Ap && !Cp && fewtiles_takes(M, N, K, aligned)) {
-        const int tn = (N + 31) / 32;
-        hipLaunchKernelGGL(gemm_fewtiles_nt, dim3((unsigned)(((M + 31) / 32) * tn)), dim3(kFtWaves * 64), 0, stream, A, lda, B, ldb, C, ldc,
-                           M, N, K, epi, tn);
-    } else if (a_kmaj && b_kmaj && aligned && M >= 192 && K >= BK && (K % BK) == 0) {
-        // pick the M-tile that wastes fewer CU-rounds: cost = rounds * (tile rows) * (resident blocks)
-        const int cus = ac::dev_info().cus;
-        const int64_t ntn = (N + BN - 1) / BN;
-        const int64_t b128 = (int64_t)((M + 127) / 128) * ntn, b64 = (int64_t)((M + 63) / 64) * ntn;
-        const int r128 = ac::arith_split() ? 3 : 2, r64 = r128 + 1;   // resident blocks per CU
-        const int64_t cost128 = ((b128 + r128 * cus - 1) / (r128 * cus)) * 128 * r128;
-        const int64_t cost64 = ((b64 + r64 * cus - 1) / (r64 * cus)) * 64 * r64;
-        // the 128-row tile does ~15 % more work per staged byte: take the 64-row one only for a clear win
-        int tm = (double)cost64 * 1.15 < (double)cost128 ? 1 : 2;
-        if (const char* e = getenv("AC_GEMM_TM")) { int v = atoi(e); if (v == 1 || v == 2) tm = v; }
-        const int64_t nblk = tm == 2 ? b128 : b64;
-        const bool plain = epi.alpha == 1.f && epi.beta == 0.f && epi.bias && !epi.mask && !epi.gate &&
-                           epi.drop_p == 0.f;
-        int cls = EPI_GENERIC;
-        if (plain && !epi.residual && epi.act == ACT_NONE) cls = EPI_BIAS;
-        else if (plain && !epi.residual && epi.act == ACT_GELU) cls = EPI_BIAS_GELU;
-        else if (plain && !epi.residual && epi.act == ACT_RELU) cls = EPI_BIAS_RELU;
-        else if (plain && epi.residual && epi.act == ACT_NONE) cls = EPI_BIAS_RES;
-        else if (plain && !epi.residual && epi.act == ACT_GEGLU32) cls = EPI_GEGLU32;
-        AC_REQUIRE(epi.act != ACT_GEGLU32 || (cls == EPI_GEGLU32 && Cp && (N % 64) == 0), AC_EUNSUPPORTED,
-                   "gemm: the fused GeGLU epilogue needs planes output, a bias vector and N %% 64 == 0");
-        const dim3 grid((unsigned)nblk), block(kTileThreads);
-        const bool split = ac::arith_split();
-        const bool planes = split && Bp != nullptr;      // (K % 32 == 0 here, so K % SBK == 0)
-#define AC_LAUNCH_PLANES(E, AP)                                                                               \
-    do {                                                                                                      \
-        if (tm == 2) hipLaunchKernelGGL((gemm_planes_nt<E, 2, AP, false>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, C, ldc, M, N, K, epi); \
-        else hipLaunchKernelGGL((gemm_planes_nt<E, 1, AP, false>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, C, ldc, M, N, K, epi);         \
-    } while (0)
-#define AC_LAUNCH_TILE(E)                                                                                     \
-    do {                                                                                                      \
-        if (split && tm == 2) hipLaunchKernelGGL((gemm_split_nt<E, 2>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi); \
-        else if (split) hipLaunchKernelGGL((gemm_split_nt<E, 1>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);      \
-        else if (tm == 2) hipLaunchKernelGGL((gemm_tile_nt<E, 2>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);     \
-        else hipLaunchKernelGGL((gemm_tile_nt<E, 1>), grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);                  \
-    } while (0)
-        // ring-staged kernel (gemm_pipe.hip): ac_gemm_set_variant(cfg >= 1000) forces one configuration (A/B harness);
-        // variant 0 = the measured per-shape choice of pipe_choose(), variant 1 = never
-        if (planes && Ap && ac::pipe_takes(M, N, K, cls, Cp != nullptr)) {
-            const int v = ac::gemm_variant();
-            const int cfg = v >= 1000 ? v : (v == 0 ? ac::pipe_choose(M, N, K, cls, Cp != nullptr) : 0);
-            if (cfg) return ac::launch_gemm_pipe(cfg, Ap, a_rows, Bp, b_rows, C, ldc, Cp, M, N, K, cls, epi, stream);
-        }
-        // 8-wave 256 x 128 tile when both operands are pre-split and the grid has >= 1.5 rounds of such tiles
-        const int64_t b256 = (int64_t)((M + 255) / 256) * ntn;
-        static const int tile256_env = getenv("AC_GEMM_TILE256") ? atoi(getenv("AC_GEMM_TILE256")) : -1;
-        // ... or when the 256-row tiles make (almost) exactly ONE residency round (2 workgroups per CU) while the 128-row tiles
-        // would spill > 10 % into a second one (FFN1 at ~5000 packed token rows: 504 vs 984 tiles, 154 vs 173-196 us)
-        const bool one_round256 = b256 <= 2 * (int64_t)cus && 10 * b256 >= 17 * (int64_t)cus && 10 * b128 > 33 * (int64_t)cus;
-        const bool big = planes && Ap && (tile256_env >= 0 ? tile256_env != 0 : (b256 >= 3 * (int64_t)cus || one_round256)) &&
-                         (cls == EPI_BIAS || cls == EPI_BIAS_GELU || cls == EPI_BIAS_RES || cls == EPI_GEGLU32) &&
-                         !(cls == EPI_GEGLU32 && !Cp) && !(cls == EPI_BIAS_RES && Cp);
-        if (big) {
-            const dim3 grid8((unsigned)b256), block8(512);
-            float* Cq = Cp ? reinterpret_cast<float*>(Cp) : C;
-#define AC_L8(E, CP) hipLaunchKernelGGL((gemm_planes_nt<E, 2, true, CP, 4>), grid8, block8, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi)
-            if (Cp) {
-                AC_REQUIRE((N % 8) == 0, AC_EUNSUPPORTED, "gemm: planes output needs N %% 8 == 0");
-                if (cls == EPI_GEGLU32) AC_L8(EPI_GEGLU32, true);
-                else if (cls == EPI_BIAS_GELU) AC_L8(EPI_BIAS_GELU, true);
-                else AC_L8(EPI_BIAS, true);
-            } else if (cls == EPI_BIAS) AC_L8(EPI_BIAS, false);
-            else if (cls == EPI_BIAS_GELU) AC_L8(EPI_BIAS_GELU, false);
-            else AC_L8(EPI_BIAS_RES, false);
-#undef AC_L8
-        } else
-        if (Cp) {
-            // result emitted as planes for the next GEMM: both operands pre-split, bias (+GELU) epilogues only
-            AC_REQUIRE(planes && Ap && (cls == EPI_BIAS || cls == EPI_BIAS_GELU || cls == EPI_GEGLU32) && (N % 8) == 0, AC_EUNSUPPORTED,
-                       "gemm: planes output needs pre-split operands, N %% 8 == 0 and a bias / bias+gelu epilogue");
-            float* Cq = reinterpret_cast<float*>(Cp);
-            if (cls == EPI_GEGLU32) {
-                if (tm == 2) hipLaunchKernelGGL((gemm_planes_nt<EPI_GEGLU32, 2, true, true>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi);
-                else hipLaunchKernelGGL((gemm_planes_nt<EPI_GEGLU32, 1, true, true>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi);
-            } else if (cls == EPI_BIAS_GELU) {
-                if (tm == 2) hipLaunchKernelGGL((gemm_planes_nt<EPI_BIAS_GELU, 2, true, true>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi);
-                else hipLaunchKernelGGL((gemm_planes_nt<EPI_BIAS_GELU, 1, true, true>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi);
-            } else {
-                if (tm == 2) hipLaunchKernelGGL((gemm_planes_nt<EPI_BIAS, 2, true, true>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi);
-                else hipLaunchKernelGGL((gemm_planes_nt<EPI_BIAS, 1, true, true>), grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cq, ldc, M, N, K, epi);
-            }
-        } else if (planes) {
-            const bool ap = Ap != nullptr;
-            switch (cls) {
-                case EPI_BIAS: if (ap) AC_LAUNCH_PLANES(EPI_BIAS, true); else AC_LAUNCH_PLANES(EPI_BIAS, false); break;
-                case EPI_BIAS_GELU: if (ap) AC_LAUNCH_PLANES(EPI_BIAS_GELU, true); else AC_LAUNCH_PLANES(EPI_BIAS_GELU, false); break;
-                case EPI_BIAS_RELU: if (ap) AC_LAUNCH_PLANES(EPI_BIAS_RELU, true); else AC_LAUNCH_PLANES(EPI_BIAS_RELU, false); break;
-                case EPI_BIAS_RES: if (ap) AC_LAUNCH_PLANES(EPI_BIAS_RES, true); else AC_LAUNCH_PLANES(EPI_BIAS_RES, false); break;
-                default: if (ap) AC_LAUNCH_PLANES(EPI_GENERIC, true); else AC_LAUNCH_PLANES(EPI_GENERIC, false); break;
-            }
-        } else
-        switch (cls) {
-            case EPI_BIAS: AC_LAUNCH_TILE(EPI_BIAS); break;
-            case EPI_BIAS_GELU: AC_LAUNCH_TILE(EPI_BIAS_GELU); break;
-            case EPI_BIAS_RELU: AC_LAUNCH_TILE(EPI_BIAS_RELU); break;
-            case EPI_BIAS_RES: AC_LAUNCH_TILE(EPI_BIAS_RES); break;
-            default: AC_LAUNCH_TILE(EPI_GENERIC); break;
-        }
-#undef AC_LAUNCH_TILE
-#undef AC_LAUNCH_PLANES
-    } else {
-        dim3 grid((N + 31) / 32, (M + 31) / 32);
-        if (a_kmaj && b_kmaj)
-            hipLaunchKernelGGL((gemm_direct<true, true>), grid, dim3(256), 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
-        else if (a_kmaj && !b_kmaj)
-            hipLaunchKernelGGL((gemm_direct<true, false>), grid, dim3(256), 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
-        else if (!a_kmaj && b_kmaj)
-            hipLaunchKernelGGL((gemm_direct<false, true>), grid, dim3(256), 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
-        else
-            hipLaunchKernelGGL((gemm_direct<false, false>), grid, dim3(256), 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi);
+    GemmQuery q;
+    q.M = M; q.N = N; q.K = K; q.a_kmaj = a_kmaj; q.b_kmaj = b_kmaj;
+    q.aligned = ((lda & 3) == 0) && ((ldb & 3) == 0) && ((((uintptr_t)A) & 15) == 0) && ((((uintptr_t)B) & 15) == 0);
+    q.a_planes = Ap != nullptr; q.w_planes = Bp != nullptr; q.c_planes = Cp != nullptr;
+    q.act = epi.act; q.alpha = epi.alpha; q.beta = epi.beta; q.drop_p = epi.drop_p;
+    q.bias = epi.bias != nullptr; q.residual = epi.residual != nullptr; q.mask = epi.mask != nullptr; q.gate = epi.gate != nullptr;
+    const GemmPlan p = gemm_plan(q, ac::gemm_env());
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    // fp32 operands | W (and A, C) as planes
+    auto nt = [&](auto* kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi); };
+    auto pl = [&](auto* kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, A, lda, Ap, a_rows, Bp, b_rows, Cp ? reinterpret_cast<float*>(Cp) : C, ldc, M, N, K, epi); };
+    bool built = true;
+    switch (p.family) {
+        case GEMM_REFUSE: ac::set_error(p.refusal, M, N, K); return AC_EUNSUPPORTED;
+        case GEMM_RING: return ac::launch_gemm_pipe(p.cfg, Ap, a_rows, Bp, b_rows, C, ldc, Cp, M, N, K, p.cls, epi, stream);
+        case GEMM_SMALLM: built = launch_smallm(p, nt); break;
+        case GEMM_FEWTILES: hipLaunchKernelGGL(gemm_fewtiles_nt, grid, block, 0, stream, A, lda, B, ldb, C, ldc, M, N, K, epi, (N + 31) / 32); break;
+        case GEMM_PLANES8: built = Cp ? launch_planes<true, 4>(p, pl) : launch_planes<false, 4>(p, pl); break;
+        case GEMM_PLANES: built = Cp ? launch_planes<true, 2>(p, pl) : launch_planes<false, 2>(p, pl); break;
+        case GEMM_SPLIT: built = launch_tiled<true>(p, nt); break;
+        case GEMM_TILE: built = launch_tiled<false>(p, nt); break;
+        default: launch_direct(a_kmaj, b_kmaj, nt); break;
     }
+    AC_REQUIRE(built, AC_EUNSUPPORTED, "gemm: the plan names a kernel that is not built (family %d, class %d)", p.family, p.cls);
     AC_LAUNCH_CHECK();
     return AC_OK;
 }
@@ -957,39 +873,44 @@ int gemm_variant() {
     }
     return v;
 }
-bool linear_takes_planes(int M, int N, int K) {
-    // mirrors launch_gemm: not the small-M kernel, the LDS-tiled path, split arithmetic
-    return arith_split() && !(M <= 64 && N >= 16) && M >= 192 && K >= 32 && (K % 32) == 0 && N >= 1;
+// The planner's inputs that are not the shape.  The only place that reads the environment, the device, the call's options and the
+// test hooks for dispatch: AC_GEMM_TM and AC_GEMM_FEWTILES are live on every call, AC_GEMM_TILE256 is read once.
+acg::PipeTable g_pipe_table, g_pipe_table_f16;     // ac_gemm_set_pipe_table / _f16
+acg::GemmEnv gemm_env() {
+    acg::GemmEnv e;
+    e.cus = dev_info().cus; e.arith = gemm_arith(); e.variant = gemm_variant();
+    if (const char* s = getenv("AC_GEMM_TM")) e.force_tm = atoi(s);
+    if (const char* s = getenv("AC_GEMM_FEWTILES")) e.fewtiles = atoi(s) != 0;
+    static const int tile256_env = getenv("AC_GEMM_TILE256") ? atoi(getenv("AC_GEMM_TILE256")) : -1;
+    e.force_tile256 = tile256_env;
+    e.table = g_pipe_table; e.table_f16 = g_pipe_table_f16;
+    return e;
 }
+bool linear_takes_planes(int M, int N, int K) { return acg::linear_takes_planes(M, N, K, gemm_env()); }
 // internal entry used by head.hip / bert.hip
 int linear_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
                const float* residual, int64_t ldr, float* C, int64_t ldc, int M, int N, int K, int act,
                const uint8_t* mask, float mask_scale, hipStream_t stream, float drop_p, uint64_t drop_seed,
                const uint16_t* Wp, const uint16_t* Ap, uint16_t* Cp, int64_t w_plane_rows) {
     Epilogue e;
-    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act; e.alpha = 1.f; e.beta = 0.f;
-    e.mask = mask; e.mask_scale = mask_scale; e.gate = nullptr; e.ldg = 0; e.gate_scale = 1.f;
+    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act; e.mask = mask; e.mask_scale = mask_scale;
     e.drop_p = mask ? 0.f : drop_p; e.drop_seed = drop_seed;
     return launch_gemm(true, true, A, lda, W, ldw, C, ldc, M, N, K, e, stream, Wp, w_plane_rows > 0 ? w_plane_rows : N, Ap, M, Cp);
 }
 // fp16x2 planes in, ring-staged kernels only (the BERT encoder under AC_GEMM_F16X2; ac_linear_f16x2)
-bool linear_f16x2_takes(int M, int N, int K) {
-    const int v = gemm_variant();
-    return (v == 0 || v >= 1000) && M >= 192 && N >= 8 && (N % 8) == 0 && (K % 32) == 0 && K >= 64;
-}
+bool linear_f16x2_takes(int M, int N, int K) { return acg::linear_f16x2_takes(M, N, K, gemm_env()); }
 int linear_f16x2(const uint16_t* Ap, const uint16_t* Wp, const float* bias, const float* residual, int64_t ldr, float* C,
                  int64_t ldc, uint16_t* Cp, int M, int N, int K, int act, hipStream_t stream, int64_t w_plane_rows) {
     AC_REQUIRE(Ap && Wp && bias && (C || Cp), AC_EINVAL, "linear_f16x2: null pointer");
-    AC_REQUIRE(linear_f16x2_takes(M, N, K), AC_EUNSUPPORTED, "linear_f16x2: %d x %d x %d does not take the ring-staged kernel", M, N, K);
+    GemmQuery q;
+    q.M = M; q.N = N; q.K = K; q.f16 = q.a_planes = q.w_planes = q.bias = true; q.c_planes = Cp != nullptr; q.act = act; q.residual = residual != nullptr;
+    const GemmPlan p = gemm_plan(q, gemm_env());
+    AC_REQUIRE(p.family == GEMM_RING, AC_EUNSUPPORTED, p.refusal, M, N, K);
     AC_REQUIRE((act == ACT_NONE || (act == ACT_GELU && Cp)) && !(Cp && residual), AC_EUNSUPPORTED,
                "linear_f16x2: act %d / residual / planes-out combination not built", act);
     Epilogue e;
-    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act; e.alpha = 1.f; e.beta = 0.f; e.mask = nullptr;
-    e.mask_scale = 1.f; e.gate = nullptr; e.ldg = 0; e.gate_scale = 1.f; e.drop_p = 0.f; e.drop_seed = 0;
-    const int cls = act == ACT_GELU ? EPI_BIAS_GELU : (residual ? EPI_BIAS_RES : EPI_BIAS);
-    const int v = gemm_variant();
-    const int cfg = v >= 1000 ? v : pipe_choose_f16(M, N, K);
-    return launch_gemm_pipe(cfg, Ap, M, Wp, w_plane_rows > 0 ? w_plane_rows : N, C, ldc, Cp, M, N, K, cls, e, stream, 1);
+    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act;
+    return launch_gemm_pipe(p.cfg, Ap, M, Wp, w_plane_rows > 0 ? w_plane_rows : N, C, ldc, Cp, M, N, K, p.cls, e, stream, 1);
 }
 // linear_f32 for shapes with few output tiles: split-K over `scratch` (see gemm_planes_splitk_nt); falls back to
 // linear_f32 when the shape has enough tiles, the arithmetic is not bf16x3, or the scratch is too small.
@@ -1000,19 +921,14 @@ int linear_f32_splitk(const float* A, int64_t lda, const float* W, int64_t ldw, 
     // one launch): on return *partials_only = the number of [M, N] slices left in `scratch` and NOTHING was written to C -- or 0, and
     // the whole linear ran as usual
     if (partials_only) *partials_only = 0;
-    const int cus = dev_info().cus;
-    const int64_t tiles = (int64_t)((M + 63) / 64) * ((N + BN - 1) / BN);
-    int ksplit = 1;
+    const acg::GemmEnv env = gemm_env();
+    const int64_t tiles = tiles_of(M, N, 64, BN);
+    const bool a_aligned = (lda % 4) == 0 && ((((uintptr_t)A) & 15) == 0);
     // (the few-tile fp32 kernel runs such a shape in ONE launch; its fp32 matrix pipe is 1/16 of the bf16 one, so only up to the
     //  size of 256 x 768 x 768 -- 8.6 us against 10 + 6 for split-K and its reduce; at the FFN shapes the two are level)
-    const bool direct = W && (int64_t)M * N * K <= (int64_t)160 << 20 && fewtiles_takes(M, N, K, (lda % 4) == 0 && (ldw % 4) == 0 && ((((uintptr_t)A) | ((uintptr_t)W)) & 15) == 0);
-    if (!direct && Wp && scratch && arith_split() && gemm_variant() == 0 && M >= 65 && M <= 512 && (N % 4) == 0 &&
-        (K % 32) == 0 && (lda % 4) == 0 && ((((uintptr_t)A) & 15) == 0) && 2 * tiles <= cus) {
-        const int nk = K / SBK;
-        // as many slices as fill ~1.5 workgroups per CU, each at least 6 stages long, dividing the stage count
-        for (int c = 2; c <= 32; ++c)
-            if (nk % c == 0 && nk / c >= 6 && tiles * c <= (int64_t)cus * 3 / 2 && (size_t)c * M * N * sizeof(float) <= scratch_bytes) ksplit = c;
-    }
+    const bool direct = W && (int64_t)M * N * K <= kSplitKFewMaxMac &&
+                        fewtiles_takes(M, N, K, a_aligned && (ldw % 4) == 0 && ((((uintptr_t)W) & 15) == 0), env);
+    const int ksplit = direct ? 1 : splitk_slices(M, N, K, a_aligned, Wp && scratch ? scratch_bytes : 0, env);
     if (ksplit == 1)
         return linear_f32(A, lda, W, ldw, bias, residual, ldr, C, ldc, M, N, K, act, nullptr, 1.f, stream, 0.f, 0, Wp, nullptr, nullptr, w_plane_rows);
     hipLaunchKernelGGL(gemm_planes_splitk_nt, dim3((unsigned)(tiles * ksplit)), dim3(256), 0, stream, A, lda, Wp,
@@ -1020,8 +936,7 @@ int linear_f32_splitk(const float* A, int64_t lda, const float* W, int64_t ldw, 
     AC_LAUNCH_CHECK();
     if (partials_only) { *partials_only = ksplit; return AC_OK; }
     Epilogue e;
-    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act; e.alpha = 1.f; e.beta = 0.f;
-    e.mask = nullptr; e.mask_scale = 1.f; e.gate = nullptr; e.ldg = 0; e.gate_scale = 1.f; e.drop_p = 0.f; e.drop_seed = 0;
+    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act;
     const int64_t n4 = (int64_t)M * (N / 4);
     hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, scratch, ksplit, M, N, C, ldc, e);
     AC_LAUNCH_CHECK();
@@ -1031,16 +946,10 @@ int head_backward_pair(const float* dY, int64_t ldy, const float* Aact, int64_t 
                        int Hout, int Hin, float gate_scale, float* gW, float* dA, float* gb_in, hipStream_t stream) {
     // problem 1: gW[Hout, Hin] = dY^T Aact (K = B);  problem 2: dA[B, Hin] = (dY W) gated by Aact != 0, K = Hout; gb_in = colsum(dA)
     AC_REQUIRE(B >= 1 && B <= 32, AC_EUNSUPPORTED, "head_backward_pair: B=%d (<= 32)", B);
-    DirectProblem p1, p2;
-    Epilogue e;
-    e.bias = nullptr; e.residual = nullptr; e.ldr = 0; e.act = ACT_NONE; e.alpha = 1.f; e.beta = 0.f; e.mask = nullptr;
-    e.mask_scale = 1.f; e.gate = nullptr; e.ldg = 0; e.gate_scale = 1.f; e.drop_p = 0.f; e.drop_seed = 0;
-    p1.A = dY; p1.lda = ldy; p1.B = Aact; p1.ldb = lda_act; p1.C = gW; p1.ldc = Hin; p1.M = Hout; p1.N = Hin; p1.K = B; p1.epi = e;
-    p1.colsum = nullptr;
-    Epilogue g = e;
+    Epilogue g;
     g.gate = Aact; g.ldg = lda_act; g.gate_scale = gate_scale;
-    p2.A = dY; p2.lda = ldy; p2.B = W; p2.ldb = ldw; p2.C = dA; p2.ldc = Hin; p2.M = B; p2.N = Hin; p2.K = Hout; p2.epi = g;
-    p2.colsum = gb_in;
+    const DirectProblem p1{dY, ldy, Aact, lda_act, gW, Hin, Hout, Hin, B, Epilogue{}, nullptr};
+    const DirectProblem p2{dY, ldy, W, ldw, dA, Hin, B, Hin, Hout, g, gb_in};
     const int nblk1 = ((Hout + 31) / 32) * ((Hin + 31) / 32), nblk2 = (Hin + 31) / 32;
     hipLaunchKernelGGL(gemm_direct_pair, dim3(nblk1 + nblk2), dim3(256), 0, stream, p1, p2, nblk1);
     AC_LAUNCH_CHECK();
@@ -1050,9 +959,7 @@ int gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const flo
              const float* B, int64_t ldb, float beta, float* C, int64_t ldc, const float* gate, int64_t ldg,
              float gate_scale, hipStream_t stream) {
     Epilogue e;
-    e.bias = nullptr; e.residual = nullptr; e.ldr = 0; e.act = ACT_NONE; e.alpha = alpha; e.beta = beta;
-    e.mask = nullptr; e.mask_scale = 1.f; e.gate = gate; e.ldg = ldg; e.gate_scale = gate_scale;
-    e.drop_p = 0.f; e.drop_seed = 0;
+    e.alpha = alpha; e.beta = beta; e.gate = gate; e.ldg = ldg; e.gate_scale = gate_scale;
     return launch_gemm(transA == 0, transB != 0, A, lda, B, ldb, C, ldc, M, N, K, e, stream);
 }
 }  // namespace ac

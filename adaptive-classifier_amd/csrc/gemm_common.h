@@ -3,6 +3,7 @@
 // Device code only; include inside an anonymous namespace user.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"
 
 #include <math.h>
 
@@ -11,26 +12,24 @@ namespace acg {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_GEGLU32 = 3 };
-
-struct Epilogue {
-    const float* bias;      // [N] or null
-    const float* residual;  // [M, ldr] or null  (added after the activation)
-    int64_t ldr;
-    int act;
-    float alpha;            // C = alpha * acc (+ beta * Cold) before bias/act
-    float beta;
+struct Epilogue {             // (a kernel argument: the defaults change no layout; a site sets only what differs)
+    const float* bias = nullptr;      // [N] or null
+    const float* residual = nullptr;  // [M, ldr] or null  (added after the activation)
+    int64_t ldr = 0;
+    int act = ACT_NONE;
+    float alpha = 1.f;                // C = alpha * acc (+ beta * Cold) before bias/act
+    float beta = 0.f;
     // inverted-dropout mask applied after the activation (train-mode head): 1 = keep
-    const uint8_t* mask;    // [M, N] or null
-    float mask_scale;
+    const uint8_t* mask = nullptr;    // [M, N] or null
+    float mask_scale = 1.f;
     // ... or generated in-kernel from a counter-based hash (no mask tensor, no torch RNG launch):
     // keep element (row, col) iff u(drop_seed, row * N + col) >= drop_p
-    uint64_t drop_seed;
-    float drop_p;
+    uint64_t drop_seed = 0;
+    float drop_p = 0.f;
     // relu/dropout backward gate: out = gate[row,col] != 0 ? out * gate_scale : 0
-    const float* gate;      // [M, ldg] or null
-    int64_t ldg;
-    float gate_scale;
+    const float* gate = nullptr;      // [M, ldg] or null
+    int64_t ldg = 0;
+    float gate_scale = 1.f;
 };
 
 // EPI_BIAS_RES_LN (gemm_pipe.hip): LayerNorm of the output rows fused into the epilogue.  The tiles of one row panel
@@ -87,15 +86,6 @@ __device__ __forceinline__ float apply_epilogue(const Epilogue& e, float acc, in
     if (e.gate) v = (e.gate[row * e.ldg + col] != 0.f) ? v * e.gate_scale : 0.f;
     return v;
 }
-
-// compile-time epilogue classes for the hot encoder/head shapes; EPI_GENERIC keeps the runtime flags
-enum { EPI_GENERIC = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_BIAS_RES = 3, EPI_BIAS_RELU = 4,
-       // GeGLU over 32-column blocks: output columns [64t, 64t+32) are the inputs and [64t+32, 64t+64) the gates of
-       // result columns [32t, 32t+32) -- a wave's two 32x32 tiles hold input_j and gate_j in the same lane/register
-       EPI_GEGLU32 = 5,
-       EPI_IDENT = 6,          // store the accumulators as they are (second half of the fused-LayerNorm epilogue)
-       EPI_BIAS_RES_LN = 7,    // bias + residual, then LayerNorm over the whole row (gemm_pipe.hip)
-       EPI_QKV_ATTN = 8 };     // the fused QKV projection's tile = one head's q | k | v: self-attention in the epilogue (gemm_pipe.hip)
 
 template <int EPI>
 __device__ __forceinline__ float fast_epilogue(float acc, float bias, float res) {
@@ -237,9 +227,8 @@ __device__ __forceinline__ int xcd_tile_id(int wg, int nwg) {
 
 namespace ac {
 // gemm_pipe.hip: the planes GEMM with its operand stages in an LDS ring (counted vmcnt, raw barrier)
-bool pipe_takes(int M, int N, int K, int cls, bool c_planes);
-int pipe_choose(int M, int N, int K, int cls, bool c_planes);   // 0 = keep the two-buffer tile kernels of gemm.hip
-int pipe_choose_f16(int M, int N, int K);                        // fp16x2 operands (never 0: there is no other kernel for them)
+acg::GemmEnv gemm_env();       // gemm.hip: the planner's inputs that are not the shape (gemm_plan.h), filled once per call
+extern acg::PipeTable g_pipe_table, g_pipe_table_f16;           // runtime ring tables (ac_gemm_set_pipe_table*), read by gemm_env()
 int launch_gemm_pipe(int cfg, const uint16_t* Ap, int64_t a_rows, const uint16_t* Wp, int64_t w_rows, float* C, int64_t ldc,
                      uint16_t* Cp, int M, int N, int K, int cls, const acg::Epilogue& epi, hipStream_t stream, int f16 = 0);
 int gemm_variant();            // diagnostic switch (ac_gemm_set_variant): 0 = default dispatch, 1 = two-buffer kernels only, >= 1000 = one ring configuration

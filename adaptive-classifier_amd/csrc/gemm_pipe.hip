@@ -610,6 +610,7 @@ int64_t g_stamp_cap = 0;
 template <int EPI, int TM, int TN, int WMW, int WNW, int NS, bool CP, int PIPE, int AR = 3>
 int launch_one(PipeParams p, hipStream_t stream) {
     using G = PipeGeom<TM, TN, WMW, WNW, NS, AR>;
+    static_assert(G::BM == 32 * TM * WMW && G::BN == 32 * TN * WNW && G::NW == WMW * WNW, "gemm_plan.h derives a ring cfg's grid and block from its digits");
     const int64_t tiles = (int64_t)((p.M + G::BM - 1) / G::BM) * ((p.N + G::BN - 1) / G::BN);
     constexpr int LN_BYTES = G::TR_BYTES + (WNW + 1) * G::BM * 8 + 16;                       // EPI_BIAS_RES_LN scratch
     const size_t lds = EPI == EPI_BIAS_RES_LN ? (size_t)(G::LDS_BYTES > LN_BYTES ? G::LDS_BYTES : LN_BYTES)
@@ -630,33 +631,18 @@ int launch_one(PipeParams p, hipStream_t stream) {
     return AC_OK;
 }
 
-// fp16x2 operands: what the BERT layer needs -- QKV (bias), FFN1 (bias + GELU -> planes), AO / FFN2 (bias + residual [+ LN])
-template <int TM, int TN, int WMW, int WNW, int NS, int PIPE>
-int launch_cfg_f16(int cls, bool cp, const PipeParams& p, hipStream_t stream) {
-    if (cp && cls == EPI_BIAS_GELU) return launch_one<EPI_BIAS_GELU, TM, TN, WMW, WNW, NS, true, PIPE, 2>(p, stream);
-    if (cp && cls == EPI_BIAS) return launch_one<EPI_BIAS, TM, TN, WMW, WNW, NS, true, PIPE, 2>(p, stream);
-    if (!cp && cls == EPI_BIAS) return launch_one<EPI_BIAS, TM, TN, WMW, WNW, NS, false, PIPE, 2>(p, stream);
-    if (!cp && cls == EPI_BIAS_RES) return launch_one<EPI_BIAS_RES, TM, TN, WMW, WNW, NS, false, PIPE, 2>(p, stream);
-    if constexpr (TM == 1 && TN == 2 && WMW == 4 && WNW == 2 && NS == 6 && PIPE == 2)
-        if (!cp && cls == EPI_BIAS_RES_LN) return launch_one<EPI_BIAS_RES_LN, TM, TN, WMW, WNW, NS, false, PIPE, 2>(p, stream);
-    ac::set_error("gemm_pipe: epilogue class %d (planes out %d) not built for fp16x2 operands", cls, (int)cp);
-    return AC_EUNSUPPORTED;
-}
-
-// the (EPI, C_PLANES) combinations the encoders use
-template <int TM, int TN, int WMW, int WNW, int NS, int PIPE>
+// the (EPI, C_PLANES) combinations the encoders use.  AR = 2 (fp16x2 operands): what the BERT layer needs -- QKV (bias), FFN1 (bias +
+// GELU -> planes), AO / FFN2 (bias + residual [+ LN])
+template <int TM, int TN, int WMW, int WNW, int NS, int PIPE, int AR = 3>
 int launch_cfg(int cls, bool cp, const PipeParams& p, hipStream_t stream) {
-    if (cp) {
-        if (cls == EPI_BIAS_GELU) return launch_one<EPI_BIAS_GELU, TM, TN, WMW, WNW, NS, true, PIPE>(p, stream);
-        if (cls == EPI_BIAS) return launch_one<EPI_BIAS, TM, TN, WMW, WNW, NS, true, PIPE>(p, stream);
-        if constexpr (TN == 2) if (cls == EPI_GEGLU32) return launch_one<EPI_GEGLU32, TM, TN, WMW, WNW, NS, true, PIPE>(p, stream);
-    } else {
-        if (cls == EPI_BIAS) return launch_one<EPI_BIAS, TM, TN, WMW, WNW, NS, false, PIPE>(p, stream);
-        if (cls == EPI_BIAS_RES) return launch_one<EPI_BIAS_RES, TM, TN, WMW, WNW, NS, false, PIPE>(p, stream);
-        if constexpr (TM == 1 && TN == 2 && WMW == 4 && WNW == 2 && NS == 6 && PIPE == 2)      // (built for the one tile that uses it)
-            if (cls == EPI_BIAS_RES_LN) return launch_one<EPI_BIAS_RES_LN, TM, TN, WMW, WNW, NS, false, PIPE>(p, stream);
-    }
-    ac::set_error("gemm_pipe: epilogue class %d (planes out %d) not built for this tile", cls, (int)cp);
+    if (cp && cls == EPI_BIAS_GELU) return launch_one<EPI_BIAS_GELU, TM, TN, WMW, WNW, NS, true, PIPE, AR>(p, stream);
+    if (cp && cls == EPI_BIAS) return launch_one<EPI_BIAS, TM, TN, WMW, WNW, NS, true, PIPE, AR>(p, stream);
+    if constexpr (TN == 2 && AR == 3) if (cp && cls == EPI_GEGLU32) return launch_one<EPI_GEGLU32, TM, TN, WMW, WNW, NS, true, PIPE>(p, stream);
+    if (!cp && cls == EPI_BIAS) return launch_one<EPI_BIAS, TM, TN, WMW, WNW, NS, false, PIPE, AR>(p, stream);
+    if (!cp && cls == EPI_BIAS_RES) return launch_one<EPI_BIAS_RES, TM, TN, WMW, WNW, NS, false, PIPE, AR>(p, stream);
+    if constexpr (TM == 1 && TN == 2 && WMW == 4 && WNW == 2 && NS == 6 && PIPE == 2)          // (built for the one tile that uses it)
+        if (!cp && cls == EPI_BIAS_RES_LN) return launch_one<EPI_BIAS_RES_LN, TM, TN, WMW, WNW, NS, false, PIPE, AR>(p, stream);
+    ac::set_error("gemm_pipe: epilogue class %d (planes out %d) not built for %s", cls, (int)cp, AR == 2 ? "fp16x2 operands" : "this tile");
     return AC_EUNSUPPORTED;
 }
 
@@ -679,12 +665,6 @@ extern "C" int ac_gemm_debug_stamps(unsigned long long* d_buf, int64_t capacity_
 
 namespace ac {
 
-bool pipe_takes(int M, int N, int K, int cls, bool c_planes) {
-    if (M < 192 || N < 1 || (K % 32) != 0 || K < 64) return false;
-    if (c_planes) return (cls == EPI_BIAS || cls == EPI_BIAS_GELU || cls == EPI_GEGLU32) && (N % 8) == 0;
-    return cls == EPI_BIAS || cls == EPI_BIAS_RES;
-}
-
 // cfg = tm tn wmw wnw ns pipe, one decimal digit each (e.g. 234232: wave tile 64 x 96, 4 x 2 waves = 256 x 192, ring of 3, pinned)
 // The set that survived the sweeps of profiles/r03/gemm_sweep*.txt (dropped there: unpinned / non-pipelined forms of the
 // same tiles, 64 x 128, 256 x 128 with two buffers, 256 x 256 as 8 waves of 128 x 64 or 16 waves of 64 x 64, 128 x 256).
@@ -703,76 +683,18 @@ bool pipe_takes(int M, int N, int K, int cls, bool c_planes) {
     X(2, 2, 4, 2, 6, 2) /* 256 x 128, ring of 6 */                                                   \
     X(1, 2, 4, 2, 8, 2) /* 128 x 128, 8 waves, ring of 8 */
 
-// per-shape configuration of the default dispatch (0 = the two-buffer tile kernels).  A runtime table (ac_gemm_set_pipe_table,
-// tuning / A-B runs) takes precedence over the built-in choice.
-struct PipeRule { int N, K, cfg; };
-static PipeRule g_rules[16];
-static int g_nrules = -1;          // -1: no runtime table
-
-// Built-in choice.  Every CU works through ceil(tiles / CUs) tiles whatever the residency, so a configuration's time goes as
-//     ceil(tiles / CUs) * BM * BN / s(cfg)
-// with s = its relative per-CU throughput once the chip is full (8192^3 and 20564-row sweeps of profiles/r03/gemm_sweep3.txt;
-// the chip is power-limited at ~0.5 - 0.6 of the bf16x3 ceiling there, and bigger tiles move fewer bytes per MFMA).  The rule
-// reproduces the measured best (or a configuration within ~2 % of it) on every bert-base / bert-large shape at ~5 k and ~20 k
-// packed token rows.  The two-buffer kernels of gemm.hip are not candidates: no measured shape has them ahead of the best
-// ring configuration (they stay for A given as fp32, for epilogues outside pipe_takes, and behind ac_gemm_set_variant(1)).
-static PipeRule g_rules_f16[16];
-static int g_nrules_f16 = -1;
-static int builtin_choose(int M, int N, int K, int cls, bool f16 = false);
-int pipe_choose(int M, int N, int K, int cls, bool c_planes) {
-    (void)c_planes;
-    if (g_nrules >= 0) {
-        for (int i = 0; i < g_nrules; ++i) if (g_rules[i].N == N && g_rules[i].K == K) return g_rules[i].cfg;
-        return 0;
-    }
-    return builtin_choose(M, N, K, cls);
-}
-// fp16x2 operands: its own runtime table (ac_gemm_set_pipe_table_f16), else the tile the bf16x3 rule picks -- the round
-// quantisation argument is the same, and the fused-LayerNorm launches need the same 128 x 128 tile in both arithmetics
-int pipe_choose_f16(int M, int N, int K) {
-    if (g_nrules_f16 >= 0)
-        for (int i = 0; i < g_nrules_f16; ++i) if (g_rules_f16[i].N == N && g_rules_f16[i].K == K && g_rules_f16[i].cfg) return g_rules_f16[i].cfg;
-    return builtin_choose(M, N, K, EPI_BIAS, true);
-}
-// f16: the fp16x2 kernels' relative throughputs differ in one place (profiles/r04/f16x2_probe_base.txt: QKV at 5141 rows 256 x 192
-// ring of 4 60 us, 192 x 256 68 us) -- their loop is paced by the operand fetch, and 256 x 192 with a ring of 4 fetches best
-static int builtin_choose(int M, int N, int K, int cls, bool f16) {
-    (void)K;
-    const int64_t cus = dev_info().cus;
-    struct Cand { int cfg, bm, bn; double s; };
-    static const Cand cands[] = {
-        {244232, 256, 256, 1.05}, {234232, 256, 192, 0.90}, {322432, 192, 256, 0.92},
-        {224242, 256, 128, 0.90}, {124262, 128, 128, 0.82}, {222232, 128, 128, 0.87},
-    };
-    int best = 0;
-    double best_cost = 0;
-    for (const Cand& c : cands) {
-        if (cls == EPI_GEGLU32 && (c.cfg / 10000) % 10 != 2) continue;       // (fused GeGLU pairs the two column tiles of a 64-column wave tile)
-        const int64_t tiles = (int64_t)((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
-        double sp = c.s;
-        if (f16 && c.cfg == 234232) sp = 0.95;
-        if (c.cfg == 222232 && 2 * tiles < 3 * cus) sp = 0.78;               // two-per-CU kernel with mostly one workgroup per CU
-        const double t = (double)((tiles + cus - 1) / cus) * c.bm * c.bn / sp;
-        if (best == 0 || t < best_cost) { best_cost = t; best = c.cfg; }
-    }
-    if (f16 && best == 234232) best = 234242;
-    return best;
-}
-
 int launch_gemm_pipe(int cfg, const uint16_t* Ap, int64_t a_rows, const uint16_t* Wp, int64_t w_rows, float* C, int64_t ldc,
                      uint16_t* Cp, int M, int N, int K, int cls, const acg::Epilogue& epi, hipStream_t stream, int f16) {
-    PipeParams p;
+    PipeParams p{};                     // (everything a launch does not set is zero / the Epilogue defaults)
     p.Ap = Ap; p.a_rows = a_rows; p.Wp = Wp; p.w_rows = w_rows;
     p.C = Cp ? reinterpret_cast<float*>(Cp) : C; p.ldc = ldc; p.M = M; p.N = N; p.K = K; p.epi = epi;
-    p.ln = LnFuse{};
-    p.stamps = nullptr;
     const bool cp = Cp != nullptr;
 #define AC_CASE(TM, TN, WMW, WNW, NS, PIPE) \
     if (!f16 && cfg == (((((TM * 10 + TN) * 10 + WMW) * 10 + WNW) * 10 + NS) * 10 + PIPE)) return launch_cfg<TM, TN, WMW, WNW, NS, PIPE>(cls, cp, p, stream);
     AC_PIPE_CONFIGS(AC_CASE)
 #undef AC_CASE
 #define AC_CASE(TM, TN, WMW, WNW, NS, PIPE) \
-    if (f16 && cfg == (((((TM * 10 + TN) * 10 + WMW) * 10 + WNW) * 10 + NS) * 10 + PIPE)) return launch_cfg_f16<TM, TN, WMW, WNW, NS, PIPE>(cls, cp, p, stream);
+    if (f16 && cfg == (((((TM * 10 + TN) * 10 + WMW) * 10 + WNW) * 10 + NS) * 10 + PIPE)) return launch_cfg<TM, TN, WMW, WNW, NS, PIPE, 2>(cls, cp, p, stream);
     AC_PIPE_CONFIGS(AC_CASE)
     AC_PIPE_CONFIGS_F16(AC_CASE)
 #undef AC_CASE
@@ -791,8 +713,7 @@ static int exchange_fences() {
 static std::atomic<long long> g_qkv_attn_launches{0};
 bool qkv_attn_applies(int M, int H, int heads, int smax) {
     if (const char* e = getenv("AC_QKV_ATTN_FUSION"); e && atoi(e) == 0) return false;      // (A/B runs and the two-launch route's tests)
-    return arith_split() && gemm_variant() == 0 && M >= 192 && heads >= 1 && H == heads * 64 && (H % 32) == 0 && H >= 64 &&
-           smax >= 1 && smax <= 64 && pipe_choose(M, 3 * H, H, EPI_BIAS, false) != 0;      // (a table that switches the ring kernels off)
+    return qkv_attn_shape(M, H, heads, smax, gemm_env());
 }
 // The per-forward sequence table of the attention epilogue: row t (kAtCu words) describes row tile t = rows [256 t, 256 t + 256):
 // [0] = n = the sequences that START in it, [1 + i] = the first row of the i-th of them (i < n), [1 + n] = the first row of the next
@@ -814,31 +735,22 @@ int qkv_attn_tile_seq(const int32_t* cu, int b, int M, int32_t* tile_seq, hipStr
     AC_LAUNCH_CHECK();
     return AC_OK;
 }
-// Residency proof for the in-launch exchange of straddling sequences (as ln_resident_capacity above): the whole grid resident at once
-static int64_t qkv_attn_resident_capacity(int f16) {
-    static std::atomic<int> occ_cache[2][64];
+// Residency proof of an in-launch exchange, made at launch: workgroups of the fused kernel `fn` that fit one CU (occupancy query, once
+// per device and cache slot) x the CUs this process's workgroups can land on (dev_info().cus: MEASURED, so a CU mask counts) must
+// hold the whole grid -- then every tile is resident together; else the fused form is simply not chosen.  (No launch-time check sees
+// another process's kernels on the same CUs: the epilogues' bounded waits stay for that and for bugs -- NaN rows, not a hung GPU.)
+enum { OCC_LN = 0, OCC_QKV_ATTN = 1, OCC_QKV_ATTN_F16 = 2 };
+static int64_t resident_capacity(int slot, const void* fn, int threads, int lds) {
+    static std::atomic<int> occ_cache[3][64];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-    int occ = occ_cache[f16 ? 1 : 0][dev].load(std::memory_order_relaxed);
+    int occ = occ_cache[slot][dev].load(std::memory_order_relaxed);
     if (occ <= 0) {
         int per_cu = 0;
-        hipError_t e;
-        if (f16) {
-            using G = PipeGeom<2, 3, 4, 2, 4, 2>;
-            const int lds = G::LDS_BYTES > kAtBytes ? G::LDS_BYTES : kAtBytes;
-            const void* fn = (const void*)gemm_pipe_nt<EPI_QKV_ATTN, 2, 3, 4, 2, 4, false, 2, 2>;
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * G::NW, lds);
-        } else {
-            using G = PipeGeom<2, 3, 4, 2, 3, 3>;
-            const int lds = G::LDS_BYTES > kAtBytes ? G::LDS_BYTES : kAtBytes;
-            const void* fn = (const void*)gemm_pipe_nt<EPI_QKV_ATTN, 2, 3, 4, 2, 3, false, 2, 3>;
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * G::NW, lds);
-        }
-        if (e != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
+        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
         occ = per_cu > 0 ? per_cu : -1;
-        occ_cache[f16 ? 1 : 0][dev].store(occ, std::memory_order_relaxed);
+        occ_cache[slot][dev].store(occ, std::memory_order_relaxed);
     }
     return occ > 0 ? (int64_t)occ * dev_info().cus : 0;
 }
@@ -847,7 +759,11 @@ bool qkv_attn_exchange_applies(int M, int heads, int f16) {
     if (!ln_fusion_enabled()) return false;              // (the encoder's "no in-launch exchanges" switch covers this one too)
     if (const char* e = getenv("AC_QKV_ATTN_EXCHANGE"); e && atoi(e) == 0) return false;       // (A/B runs, the boundary launch's tests)
     const int64_t tiles = (int64_t)((M + kQkvAttnRows - 1) / kQkvAttnRows) * heads;
-    return tiles <= qkv_attn_resident_capacity(f16);
+    using G16 = PipeGeom<2, 3, 4, 2, 4, 2>; using G = PipeGeom<2, 3, 4, 2, 3, 3>;
+    if (f16) return tiles <= resident_capacity(OCC_QKV_ATTN_F16, (const void*)gemm_pipe_nt<EPI_QKV_ATTN, 2, 3, 4, 2, 4, false, 2, 2>, 64 * G16::NW,
+                                               G16::LDS_BYTES > kAtBytes ? G16::LDS_BYTES : kAtBytes);
+    return tiles <= resident_capacity(OCC_QKV_ATTN, (const void*)gemm_pipe_nt<EPI_QKV_ATTN, 2, 3, 4, 2, 3, false, 2, 3>, 64 * G::NW,
+                                      G::LDS_BYTES > kAtBytes ? G::LDS_BYTES : kAtBytes);
 }
 int launch_gemm_pipe_qkv_attn(const uint16_t* Ap, int64_t a_rows, const uint16_t* Wp, int64_t w_rows, const float* bias, int M, int H,
                               int heads, const int32_t* cu, const int32_t* tile_seq, int b, int smax, float scale, uint16_t* ctx_planes,
@@ -855,26 +771,20 @@ int launch_gemm_pipe_qkv_attn(const uint16_t* Ap, int64_t a_rows, const uint16_t
     AC_REQUIRE(qkv_attn_applies(M, H, heads, smax), AC_EUNSUPPORTED, "gemm_pipe: fused attention epilogue not applicable (M %d H %d heads %d longest %d)",
                M, H, heads, smax);
     AC_REQUIRE(Ap && Wp && bias && cu && tile_seq && ctx_planes && qkv && b >= 1, AC_EINVAL, "gemm_pipe_qkv_attn: null pointer");
-    PipeParams p;
+    PipeParams p{};                     // (everything a launch does not set is zero / the Epilogue defaults)
     p.Ap = Ap; p.a_rows = a_rows; p.Wp = Wp; p.w_rows = w_rows; p.C = qkv; p.ldc = 3 * (int64_t)H; p.M = M; p.N = 3 * H; p.K = H;
-    Epilogue e;
-    e.bias = bias; e.residual = nullptr; e.ldr = 0; e.act = ACT_NONE; e.alpha = 1.f; e.beta = 0.f; e.mask = nullptr;
-    e.mask_scale = 1.f; e.gate = nullptr; e.ldg = 0; e.gate_scale = 1.f; e.drop_p = 0.f; e.drop_seed = 0;
-    p.epi = e;
-    p.ln = LnFuse{};
+    p.epi.bias = bias;
     p.at.cu = cu; p.at.tile_seq = tile_seq; p.at.b = b; p.at.H = H; p.at.smax = smax; p.at.scale = scale; p.at.ctx_planes = ctx_planes;
     p.at.qkv = qkv;
     AC_REQUIRE(!exchange || (abort_flag && qkv_attn_exchange_applies(M, heads, f16)), AC_EINVAL,
                "gemm_pipe_qkv_attn: the in-launch exchange needs every tile resident (%d rows x %d heads) and an abort word", M, heads);
     p.at.exchange = exchange; p.at.epoch = epoch; p.at.abort_ = abort_flag; p.at.fences = exchange_fences();
-    p.stamps = nullptr;
     g_qkv_attn_launches.fetch_add(1, std::memory_order_relaxed);
     return f16 ? launch_one<EPI_QKV_ATTN, 2, 3, 4, 2, 4, false, 2, 2>(p, stream)
                : launch_one<EPI_QKV_ATTN, 2, 3, 4, 2, 3, false, 2, 3>(p, stream);
 }
 
 // ---- bias + residual + LayerNorm fused into the N-wide GEMMs of an encoder layer (EPI_BIAS_RES_LN) ----
-constexpr int kLnCfg = 124262, kLnBM = 128, kLnBN = 128;     // the one tile the fused epilogue is built for
 static std::atomic<int> g_ln_fusion{-1};
 static std::atomic<long long> g_ln_launches{0};
 bool ln_fusion_enabled() {
@@ -889,35 +799,15 @@ bool ln_fusion_enabled() {
 }
 // The launch must be ONE round of one workgroup per CU (all tiles of a row panel co-resident) and the default dispatch must
 // pick the 128 x 128 eight-wave tile for the shape anyway.
-// Residency proof of the exchange, made at launch: workgroups of the fused kernel that fit one CU (occupancy query, once per
-// device) x the CUs this process's workgroups can land on (dev_info().cus: MEASURED, so a CU mask counts) must hold the whole
-// grid -- then every tile of every row panel is resident together and the panel counters fill.  When it does not hold the fused
-// form is simply not chosen.  (What no launch-time check can see is another process's kernels on the same CUs: the bounded wait
-// in store_tile_ln stays for that and for bugs, as an assertion that turns into NaN rows instead of a hung GPU.)
 static int64_t ln_resident_capacity() {
-    static std::atomic<int> occ_cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-    int occ = occ_cache[dev].load(std::memory_order_relaxed);
-    if (occ <= 0) {
-        using G = PipeGeom<1, 2, 4, 2, 6, 3>;
-        constexpr int LN_BYTES = G::TR_BYTES + (2 + 1) * G::BM * 8 + 16;
-        const int lds = G::LDS_BYTES > LN_BYTES ? G::LDS_BYTES : LN_BYTES;
-        const void* fn = (const void*)gemm_pipe_nt<EPI_BIAS_RES_LN, 1, 2, 4, 2, 6, false, 2, 3>;
-        (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * G::NW, lds) != hipSuccess) { (void)hipGetLastError(); per_cu = 0; }
-        occ = per_cu > 0 ? per_cu : -1;
-        occ_cache[dev].store(occ, std::memory_order_relaxed);
-    }
-    return occ > 0 ? (int64_t)occ * dev_info().cus : 0;
+    using G = PipeGeom<1, 2, 4, 2, 6, 3>;
+    constexpr int LN_BYTES = G::TR_BYTES + (2 + 1) * G::BM * 8 + 16;
+    return resident_capacity(OCC_LN, (const void*)gemm_pipe_nt<EPI_BIAS_RES_LN, 1, 2, 4, 2, 6, false, 2, 3>, 64 * G::NW,
+                             G::LDS_BYTES > LN_BYTES ? G::LDS_BYTES : LN_BYTES);
 }
 bool pipe_ln_applies(int M, int N, int K) {
-    if (!ln_fusion_enabled() || !arith_split() || gemm_variant() != 0) return false;
-    if (M < 192 || (N % kLnBN) != 0 || N / kLnBN > 8 || (K % 32) != 0 || K < 64) return false;
-    const int64_t tiles = (int64_t)((M + kLnBM - 1) / kLnBM) * (N / kLnBN);
-    // one tile per CU is what the kernel is tuned for (tiles <= CUs); the proof is tiles <= resident capacity
-    return tiles <= dev_info().cus && tiles <= ln_resident_capacity() && pipe_choose(M, N, K, EPI_BIAS_RES, false) == kLnCfg;
+    // one tile per CU is what the kernel is tuned for (the shape half: tiles <= CUs); the proof is tiles <= resident capacity
+    return ln_fusion_enabled() && pipe_ln_shape(M, N, K, gemm_env()) && tiles_of(M, N, kLnBM, kLnBN) <= ln_resident_capacity();
 }
 size_t pipe_ln_part_bytes(int M, int N) { return (size_t)((M + kLnBM - 1) / kLnBM) * (size_t)(N / kLnBN) * kLnBM * sizeof(float2); }
 int pipe_ln_panels(int M) { return (M + kLnBM - 1) / kLnBM; }
@@ -928,18 +818,14 @@ int launch_gemm_pipe_ln(const uint16_t* Ap, int64_t a_rows, const uint16_t* Wp, 
                         hipStream_t stream, int f16) {
     AC_REQUIRE(pipe_ln_applies(M, N, K), AC_EUNSUPPORTED, "gemm_pipe: fused LayerNorm epilogue not applicable to %d x %d x %d", M, N, K);
     AC_REQUIRE(Ap && Wp && bias && residual && C && gamma && beta && part && count && abort_flag, AC_EINVAL, "gemm_pipe_ln: null pointer");
-    PipeParams p;
+    PipeParams p{};                     // (everything a launch does not set is zero / the Epilogue defaults)
     p.Ap = Ap; p.a_rows = a_rows; p.Wp = Wp; p.w_rows = w_rows; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-    Epilogue e;
-    e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = ACT_NONE; e.alpha = 1.f; e.beta = 0.f; e.mask = nullptr;
-    e.mask_scale = 1.f; e.gate = nullptr; e.ldg = 0; e.gate_scale = 1.f; e.drop_p = 0.f; e.drop_seed = 0;
-    p.epi = e;
+    p.epi.bias = bias; p.epi.residual = residual; p.epi.ldr = ldr;
     p.ln.gamma = gamma; p.ln.beta = beta; p.ln.eps = eps; p.ln.part = (float2*)part; p.ln.count = count; p.ln.abort_ = abort_flag;
     p.ln.fences = exchange_fences();
     p.ln.planes = planes; p.ln.starve = (call_opts().ln_fusion >= 0 ? call_opts().ln_fusion : g_ln_fusion.load(std::memory_order_relaxed)) == 2 ? 1 : 0;
-    p.stamps = nullptr;
     g_ln_launches.fetch_add(1, std::memory_order_relaxed);
-    return f16 ? launch_cfg_f16<1, 2, 4, 2, 6, 2>(EPI_BIAS_RES_LN, false, p, stream)
+    return f16 ? launch_cfg<1, 2, 4, 2, 6, 2, 2>(EPI_BIAS_RES_LN, false, p, stream)
                : launch_cfg<1, 2, 4, 2, 6, 2>(EPI_BIAS_RES_LN, false, p, stream);
 }
 }  // namespace ac
@@ -958,26 +844,26 @@ extern "C" int64_t ac_gemm_ln_fusion_launches(void) { return (int64_t)ac::g_ln_l
 /* diagnostic (tests assert that the fused route really ran): launches of the QKV GEMM with the attention epilogue so far */
 extern "C" int64_t ac_gemm_qkv_attn_launches(void) { return (int64_t)ac::g_qkv_attn_launches.load(std::memory_order_relaxed); }
 
-static int parse_pipe_table(const char* spec, ac::PipeRule* rules, int* nrules) {
-    if (!spec) { *nrules = -1; return AC_OK; }
+static int parse_pipe_table(const char* spec, acg::PipeTable* t) {
+    if (!spec) { t->n = -1; return AC_OK; }
     int n = 0;
     const char* p = spec;
     while (*p && n < 16) {
         int N = 0, K = 0, cfg = 0, used = 0;
         if (sscanf(p, "%dx%d=%d%n", &N, &K, &cfg, &used) != 3) { ac::set_error("gemm pipe table: cannot parse '%s'", p); return AC_EINVAL; }
-        rules[n++] = {N, K, cfg};
+        t->rules[n++] = {N, K, cfg};
         p += used;
         if (*p == ';') ++p;
     }
-    *nrules = n;
+    t->n = n;
     return AC_OK;
 }
 extern "C" int ac_gemm_set_pipe_table(const char* spec) {
     AC_TEST_HOOK_ONLY("ac_gemm_set_pipe_table");
-    return parse_pipe_table(spec, ac::g_rules, &ac::g_nrules);
+    return parse_pipe_table(spec, &ac::g_pipe_table);
 }
 /* the same for the fp16x2 kernels (AC_GEMM_F16X2); shapes the table does not name keep the built-in choice */
 extern "C" int ac_gemm_set_pipe_table_f16(const char* spec) {
     AC_TEST_HOOK_ONLY("ac_gemm_set_pipe_table_f16");
-    return parse_pipe_table(spec, ac::g_rules_f16, &ac::g_nrules_f16);
+    return parse_pipe_table(spec, &ac::g_pipe_table_f16);
 }

@@ -476,13 +476,15 @@ TAIL_OFF = (("AC_BERT_TAIL_FUSED", "0"),)
 L = 3            # first, middle and CLS-only last: every layer-loop branch of bert_encode_impl
 
 # Dispatch conditions read off csrc/bert.hip (bert_encode_impl, encode_plan, ac_bert_encode_cls_opts, ac_bert_encode_cls_unpad),
-# csrc/gemm.hip (linear_takes_planes), csrc/gemm_pipe.hip (qkv_attn_applies, pipe_ln_applies) and encoder.py (_run_chunks),
-# with T = the token rows of the forward (b * S, or the real tokens on the packed path):
+# csrc/gemm_plan.h (the GEMM side: linear_takes_planes, pipe_ln_shape, qkv_attn_shape and the thresholds they share -- the rules
+# live there and are not restated here; the lines below only name which counter shows each branch), csrc/gemm_pipe.hip (the
+# residency halves of qkv_attn_applies, pipe_ln_applies) and encoder.py (_run_chunks), with T = the token rows of the forward
+# (b * S, or the real tokens on the packed path):
 #   one launch          b * S <= 32, head dim 64, not AC_BERT_LAYERED                      [used_one_launch]
 #   unpad entry         a mask is passed, S > 1, b * S > 32: packed (ones are a prefix of every row, some row short), padded
 #                       (every row full), padded_mask (anything else: left padding, holes, an empty row)   [path, total_tokens]
-#   planes              bf16x3 arithmetic and T >= 192 (K % 32 == 0)                       [no counter: T and arith decide]
-#   LayerNorm fusion    planes, layers > 1, fusion on, H % 128 == 0, H / 128 <= 8, ceil(T / 128) * H / 128 <= CUs
+#   planes              gemm_plan.h linear_takes_planes(T, H, H) and (T, H, I)             [no counter: T and arith decide]
+#   LayerNorm fusion    planes, layers > 1, fusion on, gemm_plan.h pipe_ln_shape, the grid resident at once
 #                       -> 2 launches per layer but the last                               [ac_gemm_ln_fusion_launches]
 #   attention fusion    planes, layers > 1, head dim 64, packed or no mask, longest <= 64  -> 1 launch per layer but the last
 #                                                                                          [ac_gemm_qkv_attn_launches]

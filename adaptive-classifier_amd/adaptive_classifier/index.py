@@ -14,6 +14,9 @@ Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `
 the fp32 rows.  search(x, k, sel=...) is the FILTERED search (faiss SearchParameters(sel=IDSelector...)): the k best among the
 rows a `RowSelector` names, through `ac_knn_*_topk_ids` (a short id list), `ac_knn_*_topk_batch_sel` (bitmap over the prepared
 store: a selection known to hold >= 1 / SEL_BATCH_MAX_SPARSITY of the rows) or `ac_knn_*_topk_sel` (bitmap over the fp32 rows).
+range_search(x, r, sel=...) is the FILTERED range search (faiss range_search with SearchParameters(sel=...)): the hits among the
+selected rows, through `ac_knn_*_range_count_ids` / `_fill_ids` (a short id list) or `ac_knn_*_range_count_sel` + the unfiltered
+fill (bitmap over the fp32 rows; there is no prepared-store range search).
 """
 import ctypes
 
@@ -405,7 +408,8 @@ def stitch_range_chunks(parts, device=None):
     return (torch.cat(lims), torch.cat([d for _, d, _ in parts]), torch.cat([i for _, _, i in parts]))
 
 
-def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=False, max_ws_bytes=256 << 20, stats=None):
+def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=False, max_ws_bytes=256 << 20, stats=None, sel=None,
+                     sel_bit0=0):
     """Exact range search (`ac_knn_l2_range_count` / `_fill`, or the `ip` pair): every row of P[:N] with float32(exact squared
     distance) < radius (metric "l2"), or float32(exact inner product) > radius ("ip"); faiss range_search semantics, strict.
 
@@ -413,18 +417,30 @@ def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=Fa
     hits of query q are D / I[lims[q]:lims[q + 1]], by ascending row id (+ row_offset); exact_out=True appends the exact fp64
     values.  Queries go in chunks whose workspace stays within max_ws_bytes; the result does not depend on the chunking.  One
     host read (the hit count) per chunk.  stats: optional int32 [4] cuda tensor, the d_stats of the LAST chunk's calls ([0] =
-    pairs the count phase decided by exact arithmetic, [1] = 1 if the fill did not fit -- it always fits here)."""
+    pairs the count phase decided by exact arithmetic, [1] = 1 if the fill did not fit -- it always fits here).
+    sel: the FILTERED range search (`ac_knn_*_range_count_sel`; the fill is the unfiltered one) -- a RowSelector or its int64
+    words tensor; local row r can be a hit iff bit sel_bit0 + r is set (a row shard passes sel_bit0 = its first row and the
+    replicated global bitmap).  Raises ValueError when the bitmap does not cover [sel_bit0, sel_bit0 + N).  An unselected pair
+    is never decided exactly (stats[0] counts selected pairs only); an all-ones selection returns the unfiltered bits."""
     nv.require_gpu()
     assert metric in ("l2", "ip")
     assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
     assert P.stride(1) == 1 and Q.stride(1) == 1
     nq, dev = Q.shape[0], Q.device
+    sel_args = ()
+    if sel is not None:
+        words = sel.words if isinstance(sel, RowSelector) else sel
+        assert words.dtype == torch.int64 and words.is_cuda and words.is_contiguous()
+        if int(sel_bit0) + N > words.numel() * 64:
+            raise ValueError(f"selection of {words.numel() * 64} bits does not cover rows [{sel_bit0}, {int(sel_bit0) + N})")
+        sel_args = (nv.ptr(words), int(sel_bit0))
     if torch.is_tensor(radius):
         rad = radius.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
         assert rad.numel() == nq, "one radius per query"
     else:
         rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
-    count = getattr(nv.lib(), f"ac_knn_{metric}_range_count")
+    count_name = f"ac_knn_{metric}_range_count" + ("_sel" if sel is not None else "")
+    count = getattr(nv.lib(), count_name)
     fill = getattr(nv.lib(), f"ac_knn_{metric}_range_fill")
     chunk = range_query_chunk(N, D, nq, max_ws_bytes) if nq else 1
     ws = torch.empty(max(knn_range_workspace_bytes(N, D, min(chunk, nq)), 256), dtype=torch.uint8, device=dev)
@@ -434,8 +450,8 @@ def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=Fa
             q, r = Q[s:s + chunk], rad[s:s + chunk]
             c = q.shape[0]
             lims = torch.empty(c + 1, dtype=torch.int64, device=dev)
-            nv.check(count(nv.ptr(P), N, P.stride(0), D, nv.ptr(q), c, q.stride(0), nv.ptr(r), nv.ptr(lims), nv.ptr(ws), ws.numel(),
-                           nv.ptr(stats), nv.stream_ptr(dev)), f"ac_knn_{metric}_range_count")
+            nv.check(count(nv.ptr(P), N, P.stride(0), D, nv.ptr(q), c, q.stride(0), nv.ptr(r), *sel_args, nv.ptr(lims), nv.ptr(ws),
+                           ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)), count_name)
             total = int(lims[-1].item())                      # the protocol's one host read: sizes the outputs
             outD = torch.empty(total, dtype=torch.float32, device=dev)
             outI = torch.empty(total, dtype=torch.int64, device=dev)
@@ -449,6 +465,50 @@ def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=Fa
         return empty + (torch.empty(0, dtype=torch.float64, device=dev),) if exact_out else empty
     out = stitch_range_chunks([p[:3] for p in parts], dev)
     return out + (torch.cat([p[3] for p in parts]),) if exact_out else out
+
+
+def knn_range_ids_workspace_bytes(M, nq):
+    b = ctypes.c_size_t(0)
+    nv.check(nv.lib().ac_knn_range_ids_workspace(M, nq, ctypes.byref(b)), "ac_knn_range_ids_workspace")
+    return b.value
+
+
+def knn_range_ids(P, N, D, Q, radius, ids, metric="l2", row_offset=0, exact_out=False, stats=None):
+    """FILTERED range search over a short id list (`ac_knn_*_range_count_ids` / `_fill_ids`): the hits AMONG the listed rows.
+    ids = a RowSelector built by `from_ids`, or a SORTED, UNIQUE int64 cuda tensor of <= KNN_IDS_MAX row ids (ids outside [0, N)
+    are skipped).  Reads the listed rows only, any D and N; the workspace (a bitmap over list positions) does not depend on N, so
+    the queries go in one call.  Returns what `knn_range_search(..., sel=)` returns for those rows -- bit for bit where that route
+    covers the store.  One host read (the hit count).  stats[0] = the listed pairs inside the store (all decided exactly)."""
+    nv.require_gpu()
+    assert metric in ("l2", "ip")
+    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
+    assert P.stride(1) == 1 and Q.stride(1) == 1
+    ids = ids.ids if isinstance(ids, RowSelector) else ids
+    assert ids is not None and ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+    nq, dev, M = Q.shape[0], Q.device, ids.numel()
+    if torch.is_tensor(radius):
+        rad = radius.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert rad.numel() == nq, "one radius per query"
+    else:
+        rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+    if nq == 0:
+        empty = stitch_range_chunks([], dev)
+        return empty + (torch.empty(0, dtype=torch.float64, device=dev),) if exact_out else empty
+    ws = torch.empty(max(knn_range_ids_workspace_bytes(M, nq), 256), dtype=torch.uint8, device=dev)
+    lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+    head = (nv.ptr(P), N, P.stride(0), D, nv.ptr(ids) if M else None, M, nv.ptr(Q), nq, Q.stride(0))
+    with torch.cuda.device(dev):
+        nv.check(getattr(nv.lib(), f"ac_knn_{metric}_range_count_ids")(
+            *head, nv.ptr(rad), nv.ptr(lims), nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)),
+            f"ac_knn_{metric}_range_count_ids")
+        total = int(lims[-1].item())                          # the protocol's one host read: sizes the outputs
+        outD = torch.empty(total, dtype=torch.float32, device=dev)
+        outI = torch.empty(total, dtype=torch.int64, device=dev)
+        outE = torch.empty(total, dtype=torch.float64, device=dev) if exact_out else None
+        nv.check(getattr(nv.lib(), f"ac_knn_{metric}_range_fill_ids")(
+            *head, row_offset, nv.ptr(lims), total, nv.ptr(outD), nv.ptr(outE), nv.ptr(outI), nv.ptr(ws), ws.numel(), nv.ptr(stats),
+            nv.stream_ptr(dev)), f"ac_knn_{metric}_range_fill_ids")
+    return (lims, outD, outI, outE) if exact_out else (lims, outD, outI)
 
 
 class _HipFlatIndex:
@@ -703,21 +763,29 @@ class _HipFlatIndex:
         D, I = self.search_device(q, int(k)) if sel is None else self.search_device(q, int(k), sel)
         return D.cpu().numpy(), I.cpu().numpy()
 
-    def range_search_device(self, q, radius, max_ws_bytes=256 << 20):
+    def range_search_device(self, q, radius, sel=None, max_ws_bytes=256 << 20):
         """q: [nq, d] fp32 tensor (any device), radius: float or [nq] tensor -> (lims, D, I) CUDA tensors (`knn_range_search`).
-        Searches the fp32 rows: the fp16 plane is neither needed nor prepared."""
+        Searches the fp32 rows: the fp16 plane is neither needed nor prepared.
+        sel: a RowSelector, a bool mask [ntotal] or row ids (whatever `search(sel=)` accepts) -- the hits AMONG those rows.  The
+        routing is the top-k rule without the plane: a selector that carries <= KNN_IDS_MAX host ids takes the id-list route
+        (`knn_range_ids`), everything else the bitmap route on the fp32 rows; no bitmap is read back to choose."""
         self._materialize()
         q = q.detach().to(device=self.device, dtype=torch.float32)
         if q.dim() == 1:
             q = q.unsqueeze(0)
         if q.stride(-1) != 1:
             q = q.contiguous()
-        return knn_range_search(self._store, self._n, self.d, q, radius, metric=self.metric, max_ws_bytes=max_ws_bytes)
+        if sel is not None:
+            sel = self._as_selector(sel)
+            if sel.ids is not None and sel.ids.numel() <= KNN_IDS_MAX:
+                return knn_range_ids(self._store, self._n, self.d, q, radius, sel.ids, metric=self.metric)
+        return knn_range_search(self._store, self._n, self.d, q, radius, metric=self.metric, max_ws_bytes=max_ws_bytes, sel=sel)
 
-    def range_search(self, x, radius):
+    def range_search(self, x, radius, sel=None):
         """faiss signature: numpy in, (lims int64 [nq + 1], D float32, I int64) numpy out.  L2: squared distance < radius;
-        IP: inner product > radius.  Hits of a query by ascending row id."""
-        lims, D, I = self.range_search_device(self._as_rows(x), radius)
+        IP: inner product > radius.  Hits of a query by ascending row id.  sel (faiss: params=SearchParameters(sel=...)): a
+        RowSelector, a bool mask or row ids."""
+        lims, D, I = self.range_search_device(self._as_rows(x), radius, sel=sel)
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
     @property

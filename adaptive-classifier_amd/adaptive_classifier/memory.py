@@ -496,17 +496,31 @@ class PrototypeMemory:
                 results.append((self._label_of_row(int(idx)), float(score)))
         return results
 
-    def prototypes_within(self, query_embedding: torch.Tensor, radius: float) -> List[Tuple[str, float]]:
+    def prototypes_within(self, query_embedding: torch.Tensor, radius: float, among=None) -> List[Tuple[str, float]]:
         """[(label, squared distance)] of every prototype (or `load_rows()` row) whose squared L2 distance to the query is
         < radius (faiss range_search, strict), ascending by distance, ties to the lower row.  Duplicate detection before
-        `add_examples`, open-set rejection ("is any prototype closer than r?")."""
+        `add_examples`, open-set rejection ("is any prototype closer than r?").
+        among: an iterable of labels -- only their rows can be hits (FILTERED range search, the selector of
+        `get_nearest_prototypes(..., among=)`); unknown labels are ignored, an empty set gives [].  A memory loaded with
+        `sharded=` searches every rank's row shard (`ShardedSearch.range_search`) when the group has more than one rank."""
         with self._lock:
             if self._row_labels is None and self.updates_since_rebuild >= self.config.prototype_update_frequency:
                 self._rebuild_index()
-            if self.index.ntotal == 0:
+            sharded = getattr(self, "_sharded", None)
+            collective = sharded is not None and (sharded.world > 1 or sharded.force_collectives)
+            if self.index.ntotal == 0 and not collective:       # (a rank with an empty shard still enters the collectives)
                 return []
             self._flush_dirty()
-            _, D, I = self.index.range_search_device(query_embedding.detach().reshape(1, -1), float(radius))
+            sel = None
+            if among is not None:
+                sel, count = self._among_selector(among)
+                if count == 0:
+                    return []
+            q = query_embedding.detach().reshape(1, -1)
+            if collective:
+                _, D, I = sharded.range_search(q.to(device=self.index.device, dtype=torch.float32), float(radius), sel=sel)
+            else:
+                _, D, I = self.index.range_search_device(q, float(radius), sel=sel)
             d, ids = D.cpu().numpy(), I.cpu().numpy()
             order = np.lexsort((ids, d))
             return [(self._label_of_row(int(ids[i])), float(d[i])) for i in order]

@@ -22,6 +22,9 @@ No multi-GPU scaling curve has been measured by the builder (one GPU per gpurun 
 exercised on a world-size-1 nccl group (tests/test_sharded_gpu.py::test_rccl_branch_world1), the orchestration at world
 2 / 4 / 8 over gloo on CPU (tests/test_sharded_gloo.py) and at world 2 over gloo with the real kernels on one GPU.
 
+`range_search()` (radius queries, optionally filtered): every shard range-searches all queries; the per-query hit counts and then
+the packed (fp64 value, id) hits are all-gathered and stitched per query in rank order -- ascending row id, no merge.
+
 The local search and the merge are injected so that the orchestration (offsets, gather layout,
 merge semantics) can be exercised with world_size-2 `gloo` groups on CPU in tests, where the
 callables are the oracle; the product wires the HIP kernels (default).
@@ -49,8 +52,10 @@ def _unpack(both):
 
 class ShardedSearch:
     def __init__(self, local_rows, n_local, dim, row_offset, group=None, local_search=None, merge=None,
-                 force_collectives=False, equal_blocks=False, block_rows=None, metric="l2"):
-        """metric: "l2" (default) or "ip" -- which search and merge are wired when none is injected: squared L2 ascending
+                 force_collectives=False, equal_blocks=False, block_rows=None, metric="l2", local_range=None):
+        """local_range: the local RANGE search of `range_search`, injected by CPU tests -- (P, n, D, Q, radius, row_offset, sel,
+        sel_bit0) -> (lims, D fp32, global ids, exact fp64 values); None wires `index.knn_range_search` (either metric).
+        metric: "l2" (default) or "ip" -- which search and merge are wired when none is injected: squared L2 ascending
         (`knn_l2_topk_exact` + `topk_merge`) or inner product descending (`knn_ip_topk_exact` + `topk_merge_ip`); either
         search prepares the local shard's fp16 plane on first use where `batch_applies(..., auto=True)` holds; the exchange
         itself (exact fp64 values and ids on the wire) is the same.
@@ -96,6 +101,7 @@ class ShardedSearch:
             local_search = local_search or (_hip_search_ip if metric == "ip" else _hip_search)
             merge = merge or (ix.topk_merge_ip if metric == "ip" else ix.topk_merge)
         self._search, self._merge = local_search, merge
+        self._range = local_range
         self._ws = None
 
     @property
@@ -209,6 +215,62 @@ class ShardedSearch:
             return D_loc.to(torch.float32), I_loc
         both = self._all_gather(_pack(D_loc, I_loc))            # ONE message per peer: fp64 bits and ids side by side
         return self._merge(*_unpack(both))
+
+    def range_search(self, queries, radius, sel=None):
+        """RANGE search over the row shards: queries [b, D] (identical on all ranks), radius a float or a [b] tensor -> the global
+        (lims int64 [b + 1], D fp32, I int64) on EVERY rank -- what the unsharded range search returns: the hits of a query by
+        ascending global row id, D = the exact fp64 value rounded once to fp32.
+        sel: the global RowSelector (FILTERED range search): the shard reads its slice of the replicated bitmap in place
+        (sel_bit0 = row_offset).
+        Exchange: the per-query hit counts [b] (one all_gather), then ONE all_gather of the packed (fp64 bits | ids) hits, padded
+        to the largest rank's total.  The hits are stitched per query IN RANK ORDER on the device -- the shards are contiguous and
+        ascending, so that is ascending row id: no merge, no sort, no loop over queries."""
+        if self.block_rows is not None:
+            raise ValueError("the fixed-batch path (block_rows) has no range search: construct without block_rows")
+        lims, D_loc, I, E = self._local_range(queries, radius, sel)
+        if not self._collective:
+            return lims, D_loc, I
+        G, b, dev = self.world, lims.numel() - 1, lims.device
+        if b == 0:
+            return lims, D_loc, I
+        cnt = self._all_gather(lims[1:] - lims[:-1])                       # [G, b] hits of rank g for query q
+        tot = cnt.sum(1)                                                    # [G]
+        totals = tot.tolist()                                               # (the one host read: sizes the message and the result)
+        width, total = max(totals), sum(totals)
+        if width == 0:                                                      # (every rank sees the same counts)
+            return torch.zeros_like(lims), D_loc[:0], I[:0]
+        send = torch.zeros((width, 2), dtype=torch.int64, device=dev)
+        send[: E.numel()] = _pack(E.reshape(-1, 1), I.reshape(-1, 1))
+        both = self._all_gather(send)                                       # [G, width, 2]
+        # destination of every received hit: lims_out[q] + the hits of q on lower ranks + its place in its own rank's list
+        per_q = cnt.sum(0)                                                  # [b]
+        out_lims = torch.zeros(b + 1, dtype=torch.int64, device=dev)
+        out_lims[1:] = torch.cumsum(per_q, 0)
+        before = torch.cumsum(cnt, 0) - cnt                                 # [G, b] hits of q on ranks < g
+        start_g = torch.cumsum(cnt, 1) - cnt                                # [G, b] where q begins in rank g's list
+        # position j of rank g's list belongs to the query whose [start, start + cnt) holds it
+        j = torch.arange(width, device=dev).unsqueeze(0).expand(G, width)   # [G, width]
+        valid = j < tot.unsqueeze(1)
+        q_of = torch.searchsorted((start_g + cnt).contiguous(), j.contiguous(), right=True).clamp_(max=b - 1)
+        dest = out_lims[:-1][q_of] + torch.gather(before, 1, q_of) + (j - torch.gather(start_g, 1, q_of))
+        E_all, I_all = _unpack(both)                                        # [G, width, 1] each
+        outE = torch.empty(total, dtype=torch.float64, device=dev)
+        outI = torch.empty(total, dtype=torch.int64, device=dev)
+        outE[dest[valid]] = E_all.reshape(G, width)[valid]                  # (every slot of [0, total) is written exactly once)
+        outI[dest[valid]] = I_all.reshape(G, width)[valid]
+        return out_lims, outE.to(torch.float32), outI
+
+    def _local_range(self, queries, radius, sel):
+        """this rank's shard range-searched: (lims, D fp32, global ids, exact fp64 values).  The injected `local_range` (CPU
+        tests) or `index.knn_range_search` with row_offset = sel_bit0 = this shard's first row."""
+        if self._range is None:
+            from . import index as ix
+
+            def _hip_range(P, n, D, Q, radius, off, sel, sel_bit0):
+                return ix.knn_range_search(P, n, D, Q, radius, metric=self.metric, row_offset=off, exact_out=True, sel=sel,
+                                           sel_bit0=sel_bit0 if sel is not None else 0)
+            self._range = _hip_range
+        return self._range(self.rows, self.n_local, self.dim, queries, radius, self.row_offset, sel, self.row_offset)
 
     # ---- the fixed-batch path (block_rows given): fixed shapes, buffers allocated once, no host read-back ----------------
     def _buf(self, name, shape, dtype, device):

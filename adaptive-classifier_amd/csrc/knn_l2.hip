@@ -84,20 +84,7 @@ struct SweepParamsSel : SweepParams {
 template <bool SEL> struct sweep_params { typedef SweepParams type; };
 template <> struct sweep_params<true> { typedef SweepParamsSel type; };
 
-// The 16 selection bits of a wave's tile (rows row_base .. row_base + 15, bit i = row row_base + i): they sit in at most two
-// 64-bit words, fetched wave-uniformly through the SCALAR unit (constant address space, as knn_plane_sweep's norms: off the
-// vmcnt queue the prefetched rows / the DMA ring sit in).  Bits of rows >= N are never read as rows: the second word is touched
-// only if one of its rows exists, a tile past N reads nothing, and the callers test row < N besides.
-__device__ __forceinline__ uint32_t sweep_sel_bits(const uint64_t* sel, int64_t sel_bit0, int64_t N, int64_t row_base) {
-    if (row_base >= N) return 0u;
-    typedef const uint64_t __attribute__((address_space(4)))* cup;
-    const uint32_t rem = __builtin_amdgcn_readfirstlane((uint32_t)((sel_bit0 & 63) + row_base));     // (N < 2^31)
-    const cup w = (cup)(uintptr_t)(sel + (sel_bit0 >> 6) + (rem >> 6));
-    const int s = (int)(rem & 63u);
-    uint64_t bits = w[0] >> s;
-    if (s > 48 && row_base + (64 - s) < N) bits |= w[1] << (64 - s);
-    return (uint32_t)bits & 0xffffu;
-}
+// (sweep_sel_bits, the 16 selection bits of a wave's tile, lives in knn_stream.h: the range sweep fetches them the same way)
 // an unselected row's sweep value becomes +inf BEFORE the `acc < tau` test: it is never pushed, so lists, pruning and tau see
 // exactly the selected rows
 template <int NACC>

@@ -32,6 +32,15 @@
 //   knn_range_fill<IP, SMALL>  one wave per strip: hits by ascending row id at lims[q] + offset[q][strip] + rank; exact value per
 //                            hit (one wave per hit in the big-store form, one lane per hit in the small-store form).
 //
+// FILTERED range search (ac_knn_*_range_count_sel; acamd.h "FILTERED RANGE search"): a SEL flag on the sweep and on the small-store
+// kernel, nothing else.  The sweep's epilogue fetches the 16 selection bits of its tile (sweep_sel_bits, knn_stream.h: scalar
+// loads) and ANDs them into BOTH 16-bit pieces before the non-zero test: an unselected pair is neither certain-in nor ambiguous,
+// so it never reaches knn_range_resolve -- a sparse selection saves the exact decisions, and d_stats[0] shows it.  Resolve, scan
+// and fill are the unfiltered ones: they only see a bitmap with fewer bits.  Still one writer per piece, plain stores, no new atomic.
+// Id-list route (ac_knn_*_range_count_ids / _fill_ids): knn_range_ids_count / knn_range_ids_fill, one wave per (query, 64 list
+// positions), the listed rows only; membership over list positions, the same scan.  The exact value is summed in the order the
+// bitmap route uses for the same store, so both routes return the same bits.
+//
 // The bound (certain-in implies the fp32-ROUNDED exact value is on the right side of r):
 //   Let s be the real value the sweep approximates (L2: |p|^2 - 2 p.q, IP: -2 p.q) and v its fp32 MFMA-chain value.  knn_topk's
 //   certificate uses |v - s| <= gamma0 (|p| + |q|)^2, gamma0 = 1.01 n 2^-24, n = the chain's roundings per term (knn_sweep_gamma0); both
@@ -116,8 +125,24 @@ struct RangeParams {
     int64_t* outI;
 };
 
-template <int J, bool IP>
-__global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(RangeParams prm) {
+// FILTERED range search (the SEL instantiations take this struct; the plain ones keep RangeParams and with it their kernarg
+// segment, as SweepParams / SweepParamsSel in knn_l2.hip): row r can be a hit iff bit (sel_bit0 + r) of the bitmap is set
+struct RangeParamsSel : RangeParams {
+    const uint64_t* sel;
+    int64_t sel_bit0;
+};
+template <bool SEL> struct range_params_of { typedef RangeParams type; };
+template <> struct range_params_of<true> { typedef RangeParamsSel type; };
+
+// Id-list route: membership is a bitmap over LIST POSITIONS (word w of a query = positions 64 w .. 64 w + 63 of ids), a strip is
+// one word; bm_in / cnt / off / W = S = ceil(M / 64) of the base struct are laid out for that
+struct RangeParamsIds : RangeParams {
+    const int64_t* ids;   // [M] sorted, unique; an id outside [0, N) is skipped
+    int64_t M;
+};
+
+template <int J, bool IP, bool SEL = false>
+__global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(typename range_params_of<SEL>::type prm) {
     static_assert(J == 1 || J == 2, "query tile = 1 or 2 sub-tiles of 16");
     constexpr int TQ = 16 * J;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -182,6 +207,14 @@ __global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(RangeParams prm) 
 
     // per 16-row tile of this wave: classify 4 rows x J queries per lane, store the non-zero pieces
     auto epilogue = [&](f32x4 (&acc)[J], float nsq, int64_t row_base) {
+        // FILTERED: the tile's 16 selection bits, in both halves (certain-in | ambiguous).  A tile without a selected row stores
+        // nothing, so it is not classified either (wave-uniform: the bits come through the scalar unit).
+        uint32_t selmask = 0xffffffffu;
+        if constexpr (SEL) {
+            const uint32_t sb = sweep_sel_bits(prm.sel, prm.sel_bit0, prm.N, row_base);
+            if (sb == 0u) return;
+            selmask = sb | (sb << 16);
+        }
         // |p|^2 of the lane's four C/D rows: A = the lane's partial sum of squares, B = 1 (every column gets its row's sum)
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
         const f32x4 pn2 = Shape::mfma(nsq, 1.0f, zero4);
@@ -210,6 +243,8 @@ __global__ __launch_bounds__(kThreads, 2) void knn_range_sweep(RangeParams prm) 
             }
             bits |= __shfl_xor(bits, 16);
             bits |= __shfl_xor(bits, 32);
+            // an unselected pair leaves BOTH pieces before the non-zero test: it is neither a hit nor ever decided exactly
+            if constexpr (SEL) bits &= selmask;
             // lanes 0..15 hold the two 16-bit pieces of query column j; rows past N and columns past nq never set a bit
             if (lane < 16 && bits) {
                 const size_t at = (size_t)(qt * TQ + 16 * jj + j) * pieces + (size_t)(row_base >> 4);
@@ -263,20 +298,41 @@ __global__ __launch_bounds__(kPostWaves * 64) void knn_range_resolve(RangeParams
     }
 }
 
-// small stores: one wave per (query, word); every pair is decided by its exact value
-template <bool IP>
-__global__ __launch_bounds__(kPostWaves * 64) void knn_range_small(RangeParams prm) {
+// the pairs a kernel that decides EVERY candidate pair exactly reports in d_stats[0]: nq x candidates, saturated
+__device__ __forceinline__ int32_t exact_pairs(int64_t candidates, int nq) {
+    const int64_t pairs = candidates * (int64_t)nq;
+    return pairs > 2147483647LL ? 2147483647 : (int32_t)pairs;
+}
+
+// small stores: one wave per (query, word); every pair is decided by its exact value.  SEL: every SELECTED pair -- an unselected
+// row is not evaluated (its selection bit is read only for a row < N: no word behind (sel_bit0 + N - 1) / 64 is touched)
+template <bool IP, bool SEL = false>
+__global__ __launch_bounds__(kPostWaves * 64) void knn_range_small(typename range_params_of<SEL>::type prm) {
     const int lane = threadIdx.x & 63;
     const int64_t wid = (int64_t)blockIdx.x * kPostWaves + (threadIdx.x >> 6);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && prm.stats) {
-        const int64_t pairs = prm.N * (int64_t)prm.nq;
-        prm.stats[0] = pairs > 2147483647LL ? 2147483647 : (int32_t)pairs;
+    auto selected = [&](int64_t row) {
+        if constexpr (SEL) {
+            const int64_t b = prm.sel_bit0 + row;
+            return ((prm.sel[b >> 6] >> (b & 63)) & 1ull) != 0;
+        } else {
+            return true;
+        }
+    };
+    if constexpr (SEL) {
+        if (blockIdx.x == 0 && threadIdx.x < 64 && prm.stats) {        // wave 0 counts the selected rows: no atomic
+            int64_t nsel = 0;
+            for (int64_t r0 = 0; r0 < prm.N; r0 += 64)                  // (N <= kKnnSmallN)
+                nsel += __builtin_popcountll(__builtin_amdgcn_ballot_w64(r0 + lane < prm.N && selected(r0 + lane)));
+            if (lane == 0) prm.stats[0] = exact_pairs(nsel, prm.nq);
+        }
+    } else {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && prm.stats) prm.stats[0] = exact_pairs(prm.N, prm.nq);
     }
     if (wid >= (int64_t)prm.nq * prm.W) return;
     const int64_t q = wid / prm.W, w = wid - q * prm.W;
     const int64_t row = w * 64 + lane;
     bool hit = false;
-    if (row < prm.N) {
+    if (row < prm.N && selected(row)) {
         const double x = exact_lane<IP>(prm.P + (size_t)row * prm.ldP, prm.Q + (size_t)q * prm.ldQ, prm.D);
         hit = is_hit<IP>(x, prm.radius[q]);
     }
@@ -372,6 +428,94 @@ __global__ __launch_bounds__(kPostWaves * 64) void knn_range_fill(RangeParams pr
     }
 }
 
+// ---- the id-list route: M listed rows, membership over list positions ----
+// one wave per (query, word of 64 list positions): every listed pair with an id inside [0, N) is decided by its exact value, in
+// the summation order the bitmap route uses for the same store (LANE_ORDER = its small-store kernel's, else the wave order of
+// resolve / fill) -- the same bits, hence the same verdicts and the same D.  The word is written by the one wave that owns it.
+template <bool IP, bool LANE_ORDER>
+__global__ __launch_bounds__(kPostWaves * 64) void knn_range_ids_count(RangeParamsIds prm) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t)blockIdx.x * kPostWaves + (threadIdx.x >> 6);
+    if (blockIdx.x == 0 && threadIdx.x < 64 && prm.stats) {            // wave 0 counts the valid ids: no atomic
+        int64_t valid = 0;
+        for (int64_t m0 = 0; m0 < prm.M; m0 += 64) {                    // (M <= kKnnSmallN)
+            const int64_t id = m0 + lane < prm.M ? prm.ids[m0 + lane] : -1;
+            valid += __builtin_popcountll(__builtin_amdgcn_ballot_w64(id >= 0 && id < prm.N));
+        }
+        if (lane == 0) prm.stats[0] = exact_pairs(valid, prm.nq);
+    }
+    if (wid >= (int64_t)prm.nq * prm.W) return;                        // (wave-uniform)
+    const int64_t q = wid / prm.W, w = wid - q * prm.W;
+    const int64_t m = w * 64 + lane;
+    int64_t id = m < prm.M ? prm.ids[m] : -1;
+    if (id >= prm.N) id = -1;
+    const float r = prm.radius[q];
+    const float* qrow = prm.Q + (size_t)q * prm.ldQ;
+    unsigned long long word;
+    if constexpr (LANE_ORDER) {
+        bool hit = false;
+        if (id >= 0) hit = is_hit<IP>(exact_lane<IP>(prm.P + (size_t)id * prm.ldP, qrow, prm.D), r);
+        word = __builtin_amdgcn_ballot_w64(hit);
+    } else {
+        word = 0;
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(id >= 0);
+        const int nc4 = prm.Dp >> 2;
+        while (todo) {
+            const int b = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const int64_t row = (int64_t)shfl64((uint64_t)id, b);
+            const double x = exact_wave_global<IP>(prm.P + (size_t)row * prm.ldP, qrow, prm.D, nc4, lane);
+            if (is_hit<IP>(x, r)) word |= 1ull << b;                    // (every lane holds the sum: the word is wave-uniform)
+        }
+    }
+    if (lane == 0) {
+        prm.bm_in[wid] = word;
+        prm.cnt[wid] = __builtin_popcountll(word);
+    }
+}
+
+// one wave per (query, word): the hits by ascending list position = ascending row id (the list is sorted), with their exact values
+template <bool IP, bool LANE_ORDER>
+__global__ __launch_bounds__(kPostWaves * 64) void knn_range_ids_fill(RangeParamsIds prm) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wid = (int64_t)blockIdx.x * kPostWaves + (threadIdx.x >> 6);
+    const bool overflow = prm.lims[prm.nq] > prm.capacity;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && prm.stats) prm.stats[1] = overflow ? 1 : 0;
+    if (overflow || wid >= (int64_t)prm.nq * prm.W) return;
+    const int64_t q = wid / prm.W, w = wid - q * prm.W;
+    const uint64_t word = prm.bm_in[wid];
+    if (!word) return;                                                  // (wave-uniform)
+    const int64_t first = prm.lims[q] + prm.off[wid];
+    const float* qrow = prm.Q + (size_t)q * prm.ldQ;
+    const int64_t m = w * 64 + lane;
+    const int64_t id = m < prm.M ? prm.ids[m] : 0;                      // (a set bit is a valid id)
+    if constexpr (LANE_ORDER) {
+        if ((word >> lane) & 1ull) {
+            const int64_t pos = first + __builtin_popcountll(word & ((1ull << lane) - 1ull));
+            const double x = exact_lane<IP>(prm.P + (size_t)id * prm.ldP, qrow, prm.D);
+            prm.outD[pos] = (float)x;
+            if (prm.outD64) prm.outD64[pos] = x;
+            prm.outI[pos] = id + prm.row_offset;
+        }
+    } else {
+        const int nc4 = prm.Dp >> 2;
+        int64_t pos = first;
+        uint64_t iw = word;
+        while (iw) {
+            const int b = __builtin_ctzll(iw);
+            iw &= iw - 1;
+            const int64_t row = (int64_t)shfl64((uint64_t)id, b);
+            const double x = exact_wave_global<IP>(prm.P + (size_t)row * prm.ldP, qrow, prm.D, nc4, lane);
+            if (lane == 0) {                                            // pos < lims[nq] <= capacity
+                prm.outD[pos] = (float)x;
+                if (prm.outD64) prm.outD64[pos] = x;
+                prm.outI[pos] = row + prm.row_offset;
+            }
+            ++pos;
+        }
+    }
+}
+
 // ---- host side ----
 struct RangePlan {
     bool small;
@@ -430,8 +574,11 @@ RangeParams range_params(const RangePlan& pl, const float* d_P, int64_t N, int64
 
 unsigned post_blocks(int64_t waves) { return (unsigned)((waves + kPostWaves - 1) / kPostWaves); }
 
+// d_sel != NULL: the FILTERED search (ac_knn_*_range_count_sel) -- the same plan, workspace and launch sequence with the SEL
+// instantiations of the sweep / the small-store kernel; resolve, scan and fill do not know about the selection
 int range_count(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ, const float* d_radius,
-                int64_t* d_lims, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+                int64_t* d_lims, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_, const uint64_t* d_sel = nullptr,
+                int64_t sel_bit0 = 0) {
     hipStream_t stream = (hipStream_t)stream_;
     RangePlan pl;
     int rc = make_range_plan(N, D, nq, &pl);
@@ -448,26 +595,41 @@ int range_count(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const 
         AC_HIP_CHECK(hipMemsetAsync(d_lims, 0, ((size_t)nq + 1) * 8, stream));
         return AC_OK;
     }
-    RangeParams p = range_params(pl, d_P, N, ldP, D, d_Q, nq, ldQ, ws, d_stats);
+    RangeParamsSel p{};                               // (the plain kernels take its RangeParams base)
+    static_cast<RangeParams&>(p) = range_params(pl, d_P, N, ldP, D, d_Q, nq, ldQ, ws, d_stats);
     p.radius = d_radius;
+    p.sel = d_sel; p.sel_bit0 = sel_bit0;
     if (pl.small) {
-        void (*fn)(RangeParams) = ip ? knn_range_small<true> : knn_range_small<false>;
-        hipLaunchKernelGGL(fn, dim3(post_blocks((int64_t)nq * pl.W)), dim3(kPostWaves * 64), 0, stream, p);
+        if (d_sel) {
+            void (*fn)(RangeParamsSel) = ip ? knn_range_small<true, true> : knn_range_small<false, true>;
+            hipLaunchKernelGGL(fn, dim3(post_blocks((int64_t)nq * pl.W)), dim3(kPostWaves * 64), 0, stream, p);
+        } else {
+            void (*fn)(RangeParams) = ip ? knn_range_small<true> : knn_range_small<false>;
+            hipLaunchKernelGGL(fn, dim3(post_blocks((int64_t)nq * pl.W)), dim3(kPostWaves * 64), 0, stream, static_cast<RangeParams&>(p));
+        }
         AC_LAUNCH_CHECK();
     } else {
         // both bitmaps start at zero (they are adjacent): the sweep stores non-zero pieces only
         AC_HIP_CHECK(hipMemsetAsync(ws + pl.off_in, 0, pl.off_cnt - pl.off_in, stream));
-        void (*sweep_fn)(RangeParams);
-        if (pl.TQ == 32) sweep_fn = ip ? knn_range_sweep<2, true> : knn_range_sweep<2, false>;
-        else sweep_fn = ip ? knn_range_sweep<1, true> : knn_range_sweep<1, false>;
-        AC_HIP_CHECK(hipFuncSetAttribute((const void*)sweep_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
-        const int64_t G = ac::knn_residency_groups((const void*)sweep_fn, pl.sweep_lds, pl.nqt, pl.ntiles);
+        void (*sweep_fn)(RangeParams) = nullptr;
+        void (*sweep_sel_fn)(RangeParamsSel) = nullptr;      // FILTERED search: the SEL instantiation of the same sweep
+        if (d_sel) {
+            if (pl.TQ == 32) sweep_sel_fn = ip ? knn_range_sweep<2, true, true> : knn_range_sweep<2, false, true>;
+            else sweep_sel_fn = ip ? knn_range_sweep<1, true, true> : knn_range_sweep<1, false, true>;
+        } else {
+            if (pl.TQ == 32) sweep_fn = ip ? knn_range_sweep<2, true> : knn_range_sweep<2, false>;
+            else sweep_fn = ip ? knn_range_sweep<1, true> : knn_range_sweep<1, false>;
+        }
+        const void* kfn = d_sel ? (const void*)sweep_sel_fn : (const void*)sweep_fn;
+        AC_HIP_CHECK(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.sweep_lds));
+        const int64_t G = ac::knn_residency_groups(kfn, pl.sweep_lds, pl.nqt, pl.ntiles);
         p.G = (int)G;
         p.zeros = ac::knn_zeros_device();
-        hipLaunchKernelGGL(sweep_fn, dim3((unsigned)(G * pl.nqt)), dim3(kThreads), pl.sweep_lds, stream, p);
+        if (d_sel) hipLaunchKernelGGL(sweep_sel_fn, dim3((unsigned)(G * pl.nqt)), dim3(kThreads), pl.sweep_lds, stream, p);
+        else hipLaunchKernelGGL(sweep_fn, dim3((unsigned)(G * pl.nqt)), dim3(kThreads), pl.sweep_lds, stream, static_cast<RangeParams&>(p));
         AC_LAUNCH_CHECK();
         void (*res_fn)(RangeParams) = ip ? knn_range_resolve<true> : knn_range_resolve<false>;
-        hipLaunchKernelGGL(res_fn, dim3(post_blocks((int64_t)nq * pl.S)), dim3(kPostWaves * 64), 0, stream, p);
+        hipLaunchKernelGGL(res_fn, dim3(post_blocks((int64_t)nq * pl.S)), dim3(kPostWaves * 64), 0, stream, static_cast<RangeParams&>(p));
         AC_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(knn_range_scan, dim3(1), dim3(kScanThreads), 0, stream, (const int32_t*)p.cnt, p.off, d_lims, nq, pl.S);
@@ -501,7 +663,172 @@ int range_fill(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const f
     return AC_OK;
 }
 
+// FILTERED range search, bitmap route: the argument checks return before any HIP call
+int range_count_sel(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ, const float* d_radius,
+                    const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                    ac_stream_t stream) {
+    AC_REQUIRE(sel_bit0 >= 0, AC_EINVAL, "knn range sel: sel_bit0=%lld must be >= 0", (long long)sel_bit0);
+    AC_REQUIRE(d_sel != nullptr || N <= 0, AC_EINVAL, "knn range sel: d_sel is NULL");
+    AC_REQUIRE((((uintptr_t)d_sel) & 7) == 0, AC_EINVAL, "knn range sel: d_sel must be 8-byte aligned");
+    return range_count(ip, d_P, N, ldP, D, d_Q, nq, ldQ, d_radius, d_lims, d_ws, ws_bytes, d_stats, stream, N > 0 ? d_sel : nullptr,
+                       sel_bit0);
+}
+
+// ---- id-list route ----
+struct RangeIdsPlan {
+    bool lane_order;      // the summation order of the bitmap route's small-store kernel (else the wave order)
+    int Dp;
+    int64_t W;            // words (= strips) per query: max(ceil(M / 64), 1)
+    size_t off_in, off_cnt, off_off, total;
+};
+
+void range_ids_layout(int64_t M, int nq, RangeIdsPlan* pl) {
+    pl->W = M > 64 ? (M + 63) / 64 : 1;
+    const size_t n = (size_t)(nq > 0 ? nq : 1) * (size_t)pl->W;
+    ac::WsTake take;
+    pl->off_in = take(n * 8);
+    pl->off_cnt = take(n * 4);
+    pl->off_off = take(n * 8);
+    pl->total = take.off;
+}
+
+// argument checks (before any device work) and the plan; the layout depends on (M, nq) alone
+int make_range_ids_plan(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q, int nq,
+                        int64_t ldQ, void* d_ws, size_t ws_bytes, RangeIdsPlan* pl) {
+    AC_REQUIRE(M >= 0 && M <= ac::kKnnSmallN, AC_EINVAL, "knn range ids: M=%lld outside [0, %d]", (long long)M, ac::kKnnSmallN);
+    AC_REQUIRE(d_ids != nullptr || M == 0, AC_EINVAL, "knn range ids: d_ids is NULL");
+    AC_REQUIRE(N >= 0 && N < 2147483647LL, AC_EINVAL, "knn range ids: N=%lld out of range", (long long)N);
+    AC_REQUIRE(D >= 1 && nq >= 0, AC_EINVAL, "knn range ids: bad D=%d nq=%d", D, nq);
+    *pl = RangeIdsPlan{};
+    range_ids_layout(M, nq, pl);
+    pl->Dp = (D + 3) / 4 * 4;
+    if (nq == 0) return AC_OK;
+    AC_REQUIRE(d_Q != nullptr, AC_EINVAL, "knn range ids: null pointer");
+    AC_REQUIRE(ldQ >= D, AC_EINVAL, "knn range ids: ldQ=%lld < D=%d", (long long)ldQ, D);
+    AC_REQUIRE(ws_bytes >= pl->total && d_ws, AC_EWORKSPACE, "knn range ids: workspace %zu < required %zu", ws_bytes, pl->total);
+    if (N > 0 && M > 0) {
+        const int rc = ac::knn_check_store("knn range ids", d_P, ldP, pl->Dp);
+        if (rc != AC_OK) return rc;
+    }
+    // the order in which the bitmap route sums this store's exact values: its small-store kernel's iff that route takes it
+    // (a D beyond the sweep and N <= 8192); a store that route refuses is summed in the wave order
+    ac::KnnSweepShape sh;
+    pl->lane_order = ac::knn_sweep_shape(N, D, nq, 1, &sh) == AC_OK && sh.small;
+    return AC_OK;
+}
+
+RangeParamsIds range_ids_params(const RangeIdsPlan& pl, const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M,
+                                const float* d_Q, int nq, int64_t ldQ, char* ws, int32_t* d_stats) {
+    RangeParamsIds p{};
+    p.P = d_P; p.N = N; p.ldP = ldP; p.Q = d_Q; p.ldQ = ldQ; p.D = D; p.Dp = pl.Dp; p.nq = nq;
+    p.W = pl.W; p.S = pl.W;
+    p.bm_in = (uint64_t*)(ws + pl.off_in); p.cnt = (int32_t*)(ws + pl.off_cnt); p.off = (int64_t*)(ws + pl.off_off);
+    p.stats = d_stats;
+    p.ids = d_ids; p.M = M;
+    return p;
+}
+
+int range_count_ids(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q, int nq,
+                    int64_t ldQ, const float* d_radius, int64_t* d_lims, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                    ac_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    RangeIdsPlan pl;
+    const int rc = make_range_ids_plan(d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, d_ws, ws_bytes, &pl);
+    if (rc != AC_OK) return rc;
+    if (nq == 0) return AC_OK;
+    AC_REQUIRE(d_radius && d_lims, AC_EINVAL, "knn range ids: null pointer");
+    if (d_stats) AC_HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(int32_t), stream));
+    if (N == 0 || M == 0) {
+        AC_HIP_CHECK(hipMemsetAsync(d_lims, 0, ((size_t)nq + 1) * 8, stream));
+        return AC_OK;
+    }
+    RangeParamsIds p = range_ids_params(pl, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, (char*)d_ws, d_stats);
+    p.radius = d_radius;
+    void (*fn)(RangeParamsIds);
+    if (pl.lane_order) fn = ip ? knn_range_ids_count<true, true> : knn_range_ids_count<false, true>;
+    else fn = ip ? knn_range_ids_count<true, false> : knn_range_ids_count<false, false>;
+    hipLaunchKernelGGL(fn, dim3(post_blocks((int64_t)nq * pl.W)), dim3(kPostWaves * 64), 0, stream, p);
+    AC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(knn_range_scan, dim3(1), dim3(kScanThreads), 0, stream, (const int32_t*)p.cnt, p.off, d_lims, nq, pl.W);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
+}
+
+int range_fill_ids(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q, int nq,
+                   int64_t ldQ, int64_t row_offset, const int64_t* d_lims, int64_t capacity, float* d_outD, double* d_outD64,
+                   int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    RangeIdsPlan pl;
+    const int rc = make_range_ids_plan(d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, d_ws, ws_bytes, &pl);
+    if (rc != AC_OK) return rc;
+    if (nq == 0) return AC_OK;
+    AC_REQUIRE(d_lims && capacity >= 0 && (capacity == 0 || (d_outD && d_outI)), AC_EINVAL, "knn range ids fill: null pointer");
+    if (N == 0 || M == 0) {
+        if (d_stats) AC_HIP_CHECK(hipMemsetAsync(d_stats + 1, 0, sizeof(int32_t), stream));
+        return AC_OK;
+    }
+    RangeParamsIds p = range_ids_params(pl, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, (char*)d_ws, d_stats);
+    p.row_offset = row_offset; p.lims = const_cast<int64_t*>(d_lims); p.capacity = capacity;
+    p.outD = d_outD; p.outD64 = d_outD64; p.outI = d_outI;
+    void (*fn)(RangeParamsIds);
+    if (pl.lane_order) fn = ip ? knn_range_ids_fill<true, true> : knn_range_ids_fill<false, true>;
+    else fn = ip ? knn_range_ids_fill<true, false> : knn_range_ids_fill<false, false>;
+    hipLaunchKernelGGL(fn, dim3(post_blocks((int64_t)nq * pl.W)), dim3(kPostWaves * 64), 0, stream, p);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
+}
+
 }  // namespace
+
+extern "C" int ac_knn_l2_range_count_sel(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ,
+                                         const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims, void* d_ws,
+                                         size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
+    return range_count_sel(false, d_P, N, ldP, D, d_Q, nq, ldQ, d_radius, d_sel, sel_bit0, d_lims, d_ws, ws_bytes, d_stats, stream);
+}
+
+extern "C" int ac_knn_ip_range_count_sel(const float* d_P, int64_t N, int64_t ldP, int D, const float* d_Q, int nq, int64_t ldQ,
+                                         const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims, void* d_ws,
+                                         size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
+    return range_count_sel(true, d_P, N, ldP, D, d_Q, nq, ldQ, d_radius, d_sel, sel_bit0, d_lims, d_ws, ws_bytes, d_stats, stream);
+}
+
+extern "C" int ac_knn_range_ids_workspace(int64_t M, int nq, size_t* bytes) {
+    AC_REQUIRE(bytes != nullptr, AC_EINVAL, "knn range ids workspace: bytes is NULL");
+    AC_REQUIRE(M >= 0 && M <= ac::kKnnSmallN, AC_EINVAL, "knn range ids: M=%lld outside [0, %d]", (long long)M, ac::kKnnSmallN);
+    AC_REQUIRE(nq >= 0, AC_EINVAL, "knn range ids: bad nq=%d", nq);
+    RangeIdsPlan pl{};
+    range_ids_layout(M, nq, &pl);
+    *bytes = pl.total;
+    return AC_OK;
+}
+
+extern "C" int ac_knn_l2_range_count_ids(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M,
+                                         const float* d_Q, int nq, int64_t ldQ, const float* d_radius, int64_t* d_lims, void* d_ws,
+                                         size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
+    return range_count_ids(false, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, d_radius, d_lims, d_ws, ws_bytes, d_stats, stream);
+}
+
+extern "C" int ac_knn_l2_range_fill_ids(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q,
+                                        int nq, int64_t ldQ, int64_t row_offset, const int64_t* d_lims, int64_t capacity, float* d_outD,
+                                        double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                        ac_stream_t stream) {
+    return range_fill_ids(false, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, row_offset, d_lims, capacity, d_outD, d_outD64, d_outI, d_ws,
+                          ws_bytes, d_stats, stream);
+}
+
+extern "C" int ac_knn_ip_range_count_ids(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M,
+                                         const float* d_Q, int nq, int64_t ldQ, const float* d_radius, int64_t* d_lims, void* d_ws,
+                                         size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
+    return range_count_ids(true, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, d_radius, d_lims, d_ws, ws_bytes, d_stats, stream);
+}
+
+extern "C" int ac_knn_ip_range_fill_ids(const float* d_P, int64_t N, int64_t ldP, int D, const int64_t* d_ids, int64_t M, const float* d_Q,
+                                        int nq, int64_t ldQ, int64_t row_offset, const int64_t* d_lims, int64_t capacity, float* d_outD,
+                                        double* d_outD64, int64_t* d_outI, void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                        ac_stream_t stream) {
+    return range_fill_ids(true, d_P, N, ldP, D, d_ids, M, d_Q, nq, ldQ, row_offset, d_lims, capacity, d_outD, d_outD64, d_outI, d_ws,
+                          ws_bytes, d_stats, stream);
+}
 
 extern "C" int ac_knn_range_workspace(int64_t N, int D, int nq, size_t* bytes) {
     AC_REQUIRE(bytes != nullptr, AC_EINVAL, "knn range workspace: bytes is NULL");

@@ -4,6 +4,7 @@
 // the query tile sits in LDS pre-scaled by -2 in B-fragment order.  What a sweep does with a finished 16-row tile is its epilogue.
 // Both sweeps bound their error by the roundings of THIS chain (knn_sweep_gamma0, common.h): the bound is stated once because the
 // chain exists once.
+// The FILTERED forms of both sweeps fetch the 16 selection bits of a finished tile the same way (sweep_sel_bits).
 // The exact fp64 value of a (row, query) pair -- the bits every search returns -- closes the file: one accumulation step and the two
 // summation orders (a wave per pair, a lane per pair) that knn_exact.hip and knn_range.hip share.
 // Included by the .hip files of the kNN searches only.  The functions are device code; the constants (kWaves, kGroup, kLdsLimit,
@@ -165,6 +166,22 @@ __device__ __forceinline__ void stream_tiles(const float* P, int64_t N, int64_t 
     }
 #undef AC_PREFETCH
 #undef AC_COMPUTE
+}
+
+// ---- FILTERED sweeps (acamd.h "FILTERED search"): local row r is selected iff bit (sel_bit0 + r) of the bitmap is set ----
+// The 16 selection bits of a wave's tile (rows row_base .. row_base + 15, bit i = row row_base + i): they sit in at most two
+// 64-bit words, fetched wave-uniformly through the SCALAR unit (constant address space, as knn_plane_sweep's norms: off the
+// vmcnt queue the prefetched rows / the DMA ring sit in).  Bits of rows >= N are never read as rows: the second word is touched
+// only if one of its rows exists, a tile past N reads nothing, and the callers test row < N besides.
+__device__ __forceinline__ uint32_t sweep_sel_bits(const uint64_t* sel, int64_t sel_bit0, int64_t N, int64_t row_base) {
+    if (row_base >= N) return 0u;
+    typedef const uint64_t __attribute__((address_space(4)))* cup;
+    const uint32_t rem = __builtin_amdgcn_readfirstlane((uint32_t)((sel_bit0 & 63) + row_base));     // (N < 2^31)
+    const cup w = (cup)(uintptr_t)(sel + (sel_bit0 >> 6) + (rem >> 6));
+    const int s = (int)(rem & 63u);
+    uint64_t bits = w[0] >> s;
+    if (s > 48 && row_base + (64 - s) < N) bits |= w[1] << (64 - s);
+    return (uint32_t)bits & 0xffffu;
 }
 
 // ---- the exact fp64 value of a (row, query) pair ----

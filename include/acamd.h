@@ -324,7 +324,32 @@ int ac_knn_ip_range_fill(const float* d_P, int64_t N, int64_t ldP, int D,
  *       say about 1/32 of the rows; measured at 256 x 1M x 768, no query takes the fallback at 1/32 (nor at 1 %, whose 10 159
  *       selected rows still fit the candidate buffer) (profiles/knn_select/README.md).
  * AC_EINVAL for the batch forms: d_sel NULL, d_sel not 8-byte aligned, sel_bit0 < 0 -- checked first, before any device work.
- * Not covered: filtered range search.
+ *
+ * FILTERED RANGE search -- faiss IndexFlat.range_search(x, r, params=SearchParameters(sel=...)): row n is a hit iff it is
+ * selected AND the predicate of the range search holds.  Everything else is the unfiltered range search: hits by ascending row
+ * id, lims, D = the fp64 value rounded once, d_outD64, the special radii, N = 0, nq = 0.  Over the fp32 rows only (no
+ * prepared-store form).
+ *   ac_knn_l2_range_count_sel / ac_knn_ip_range_count_sel   the BITMAP route: the arguments of ac_knn_*_range_count plus
+ *       (d_sel, sel_bit0) after d_radius -- the selection layout above, no word behind word (sel_bit0 + N - 1) / 64 is read.
+ *       Same workspace (ac_knn_range_workspace), same supported (N, D), same protocol: ac_knn_*_range_fill then fills from that
+ *       workspace UNCHANGED -- after the count the membership bitmap simply holds fewer bits.  d_stats[0] = the (query, row)
+ *       pairs decided by exact arithmetic, which are SELECTED pairs only: an unselected pair is dropped in the sweep's epilogue
+ *       (both its certain-in and its ambiguous bit are masked before anything is stored) and never reaches the exact decision;
+ *       the small-store kernel does not evaluate an unselected row.  An all-ones selection returns the bits of the unfiltered
+ *       call: lims, I, D, D64 and d_stats[0].
+ *   ac_knn_range_ids_workspace / ac_knn_*_range_count_ids / ac_knn_*_range_fill_ids   the ID-LIST route for sparse selections:
+ *       d_ids = M sorted, unique int64 row ids, M <= 8192, ids outside [0, N) are skipped on the device (as ac_knn_*_topk_ids).
+ *       Reads the listed rows only; every listed pair is decided by its exact fp64 value.  Membership is a bitmap over LIST
+ *       POSITIONS: the workspace -- ac_knn_range_ids_workspace(M, nq): three arrays of nq * max(ceil(M / 64), 1) entries of 8, 4
+ *       and 8 bytes, each rounded up to 256 bytes -- and the work do not depend on N.  Any D and any N < 2^31; d_P / ldP as
+ *       ac_knn_l2_topk (16-byte aligned rows, zero padded to a multiple of 4 columns).  The exact value is summed in the order
+ *       the bitmap route uses for the same (N, D) -- a lane per pair where that route takes its small-store kernel, a wave per
+ *       pair otherwise (also where that route refuses the store) -- so where both routes cover a store they return the same
+ *       lims / I / D / D64 bit for bit.  Protocol and capacity rule as ac_knn_*_range_count / _fill (count -> read lims[nq] ->
+ *       fill with the same arguments, stream and untouched workspace); d_stats[0] = nq * (listed ids inside [0, N)), the pairs
+ *       decided (all exactly), d_stats[1] as for fill.
+ * AC_EINVAL, before any device work: d_sel NULL with N > 0, d_sel not 8-byte aligned, sel_bit0 < 0; M < 0, M > 8192, d_ids NULL
+ * with M > 0.
  */
 int ac_knn_l2_topk_sel(const float* d_P, int64_t N, int64_t ldP, int D,
                        const float* d_Q, int nq, int64_t ldQ, int k,
@@ -364,6 +389,43 @@ int ac_knn_ip_topk_ids(const float* d_P, int64_t N, int64_t ldP, int D,
                        int64_t row_offset,
                        float* d_outD, double* d_outD64, int64_t* d_outI,
                        ac_stream_t stream);
+int ac_knn_l2_range_count_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                              const float* d_Q, int nq, int64_t ldQ,
+                              const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims,
+                              void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                              ac_stream_t stream);
+int ac_knn_ip_range_count_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                              const float* d_Q, int nq, int64_t ldQ,
+                              const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims,
+                              void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                              ac_stream_t stream);
+int ac_knn_range_ids_workspace(int64_t M, int nq, size_t* bytes);
+int ac_knn_l2_range_count_ids(const float* d_P, int64_t N, int64_t ldP, int D,
+                              const int64_t* d_ids, int64_t M,
+                              const float* d_Q, int nq, int64_t ldQ,
+                              const float* d_radius, int64_t* d_lims,
+                              void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                              ac_stream_t stream);
+int ac_knn_l2_range_fill_ids(const float* d_P, int64_t N, int64_t ldP, int D,
+                             const int64_t* d_ids, int64_t M,
+                             const float* d_Q, int nq, int64_t ldQ,
+                             int64_t row_offset, const int64_t* d_lims, int64_t capacity,
+                             float* d_outD, double* d_outD64, int64_t* d_outI,
+                             void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                             ac_stream_t stream);
+int ac_knn_ip_range_count_ids(const float* d_P, int64_t N, int64_t ldP, int D,
+                              const int64_t* d_ids, int64_t M,
+                              const float* d_Q, int nq, int64_t ldQ,
+                              const float* d_radius, int64_t* d_lims,
+                              void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                              ac_stream_t stream);
+int ac_knn_ip_range_fill_ids(const float* d_P, int64_t N, int64_t ldP, int D,
+                             const int64_t* d_ids, int64_t M,
+                             const float* d_Q, int nq, int64_t ldQ,
+                             int64_t row_offset, const int64_t* d_lims, int64_t capacity,
+                             float* d_outD, double* d_outD64, int64_t* d_outI,
+                             void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                             ac_stream_t stream);
 int ac_knn_sel_pack(const uint8_t* d_mask, int64_t n, uint64_t* d_sel, ac_stream_t stream);
 int ac_knn_sel_classes(const int32_t* d_row_class, int64_t n, const uint8_t* d_class_on, int n_classes,
                        uint64_t* d_sel, ac_stream_t stream);

@@ -120,6 +120,15 @@ _SIGNATURES = {
                                           c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ac_knn_ip_range_count_sel": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int64,
                                           c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_range_batch_workspace": (c_int, [c_int64, c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ac_knn_l2_range_count_batch": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_ip_range_count_batch": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_l2_range_count_batch_sel": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                                c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ac_knn_ip_range_count_batch_sel": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                                c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "ac_knn_range_ids_workspace": (c_int, [c_int64, c_int, ctypes.POINTER(c_size_t)]),
     "ac_knn_l2_range_count_ids": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p,
                                           c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),

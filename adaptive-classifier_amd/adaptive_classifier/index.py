@@ -11,12 +11,12 @@ the lower id.  HipFlatIPIndex is the same store searched by inner product (`ac_k
 faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.
 Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `ac_knn_l2_topk_batch` /
 `ac_knn_ip_topk_batch`.  range_search() (faiss range_search: every row within a radius) is `ac_knn_*_range_count` / `_fill` over
-the fp32 rows.  search(x, k, sel=...) is the FILTERED search (faiss SearchParameters(sel=IDSelector...)): the k best among the
-rows a `RowSelector` names, through `ac_knn_*_topk_ids` (a short id list), `ac_knn_*_topk_batch_sel` (bitmap over the prepared
+the fp32 rows; an index that already holds a plane counts over it (`ac_knn_*_range_count_batch`), with the same bits.
+search(x, k, sel=...) is the FILTERED search (faiss SearchParameters(sel=IDSelector...)): the k best among the rows a `RowSelector` names, through `ac_knn_*_topk_ids` (a short id list), `ac_knn_*_topk_batch_sel` (bitmap over the prepared
 store: a selection known to hold >= 1 / SEL_BATCH_MAX_SPARSITY of the rows) or `ac_knn_*_topk_sel` (bitmap over the fp32 rows).
 range_search(x, r, sel=...) is the FILTERED range search (faiss range_search with SearchParameters(sel=...)): the hits among the
 selected rows, through `ac_knn_*_range_count_ids` / `_fill_ids` (a short id list) or `ac_knn_*_range_count_sel` + the unfiltered
-fill (bitmap over the fp32 rows; there is no prepared-store range search).
+fill (bitmap over the fp32 rows, or `ac_knn_*_range_count_batch_sel` over a plane the index already holds).
 """
 import ctypes
 
@@ -384,11 +384,29 @@ def knn_range_workspace_bytes(N, D, nq):
     return b.value
 
 
-def range_query_chunk(N, D, nq, max_ws_bytes):
+def knn_range_batch_workspace_bytes(N, D, nq):
+    """workspace of `ac_knn_*_range_count_batch[_sel]` (its prefix is the fp32 route's, which the fill reads)"""
+    b = ctypes.c_size_t(0)
+    nv.check(nv.lib().ac_knn_range_batch_workspace(N, D, nq, ctypes.byref(b)), "ac_knn_range_batch_workspace")
+    return b.value
+
+
+def range_batch_applies(N, D, nq):
+    """Library limits of the range count over a prepared store (N >= 65536, a D whose query tile fits): asked of the workspace
+    planner, a host-only call."""
+    if nq < 1:
+        return False
+    b = ctypes.c_size_t(0)
+    return nv.lib().ac_knn_range_batch_workspace(N, D, nq, ctypes.byref(b)) == 0
+
+
+def range_query_chunk(N, D, nq, max_ws_bytes, workspace_bytes=None):
     """Queries per call of a range search of nq queries: the largest count whose workspace (the membership bitmap grows as
-    nq * N / 8) stays within max_ws_bytes; at least 1.  Raises for an (N, D) the library does not cover."""
-    chunk = max(1, min(nq, max_ws_bytes // max(knn_range_workspace_bytes(N, D, 1), 1)))
-    while chunk > 1 and knn_range_workspace_bytes(N, D, chunk) > max_ws_bytes:
+    nq * N / 8) stays within max_ws_bytes; at least 1.  Raises for an (N, D) the library does not cover.
+    workspace_bytes: the planner that sizes a call, (N, D, nq) -> bytes; None = `knn_range_workspace_bytes` (the fp32 route)."""
+    ws_bytes = workspace_bytes or knn_range_workspace_bytes
+    chunk = max(1, min(nq, max_ws_bytes // max(ws_bytes(N, D, 1), 1)))
+    while chunk > 1 and ws_bytes(N, D, chunk) > max_ws_bytes:
         chunk = max(1, chunk // 2)
     return chunk
 
@@ -409,7 +427,7 @@ def stitch_range_chunks(parts, device=None):
 
 
 def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=False, max_ws_bytes=256 << 20, stats=None, sel=None,
-                     sel_bit0=0):
+                     sel_bit0=0, prepared=None):
     """Exact range search (`ac_knn_l2_range_count` / `_fill`, or the `ip` pair): every row of P[:N] with float32(exact squared
     distance) < radius (metric "l2"), or float32(exact inner product) > radius ("ip"); faiss range_search semantics, strict.
 
@@ -421,12 +439,19 @@ def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=Fa
     sel: the FILTERED range search (`ac_knn_*_range_count_sel`; the fill is the unfiltered one) -- a RowSelector or its int64
     words tensor; local row r can be a hit iff bit sel_bit0 + r is set (a row shard passes sel_bit0 = its first row and the
     replicated global bitmap).  Raises ValueError when the bitmap does not cover [sel_bit0, sel_bit0 + N).  An unselected pair
-    is never decided exactly (stats[0] counts selected pairs only); an all-ones selection returns the unfiltered bits."""
+    is never decided exactly (stats[0] counts selected pairs only); an all-ones selection returns the unfiltered bits.
+    prepared: optional (planes, norms) from `prepare_store`, current for P[:N].  Where `range_batch_applies`, the COUNT then reads
+    the store's fp16 plane (`ac_knn_*_range_count_batch[_sel]`: half the bytes; stats[2] = 2 reports it) -- the same bits at any
+    radius, since every pair the plane cannot decide is decided from the fp32 rows as before.  The fill and the host read per chunk
+    are unchanged; chunks are sized by the batch workspace."""
     nv.require_gpu()
     assert metric in ("l2", "ip")
     assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
     assert P.stride(1) == 1 and Q.stride(1) == 1
     nq, dev = Q.shape[0], Q.device
+    batch = prepared is not None and range_batch_applies(N, D, nq)
+    store_args = (nv.ptr(prepared[0]), nv.ptr(prepared[1])) if batch else ()
+    ws_bytes = knn_range_batch_workspace_bytes if batch else knn_range_workspace_bytes
     sel_args = ()
     if sel is not None:
         words = sel.words if isinstance(sel, RowSelector) else sel
@@ -439,19 +464,19 @@ def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=Fa
         assert rad.numel() == nq, "one radius per query"
     else:
         rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
-    count_name = f"ac_knn_{metric}_range_count" + ("_sel" if sel is not None else "")
+    count_name = f"ac_knn_{metric}_range_count" + ("_batch" if batch else "") + ("_sel" if sel is not None else "")
     count = getattr(nv.lib(), count_name)
     fill = getattr(nv.lib(), f"ac_knn_{metric}_range_fill")
-    chunk = range_query_chunk(N, D, nq, max_ws_bytes) if nq else 1
-    ws = torch.empty(max(knn_range_workspace_bytes(N, D, min(chunk, nq)), 256), dtype=torch.uint8, device=dev)
+    chunk = range_query_chunk(N, D, nq, max_ws_bytes, ws_bytes) if nq else 1
+    ws = torch.empty(max(ws_bytes(N, D, min(chunk, nq)), 256), dtype=torch.uint8, device=dev)
     parts = []
     with torch.cuda.device(dev):
         for s in range(0, nq, chunk):
             q, r = Q[s:s + chunk], rad[s:s + chunk]
             c = q.shape[0]
             lims = torch.empty(c + 1, dtype=torch.int64, device=dev)
-            nv.check(count(nv.ptr(P), N, P.stride(0), D, nv.ptr(q), c, q.stride(0), nv.ptr(r), *sel_args, nv.ptr(lims), nv.ptr(ws),
-                           ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)), count_name)
+            nv.check(count(nv.ptr(P), N, P.stride(0), D, *store_args, nv.ptr(q), c, q.stride(0), nv.ptr(r), *sel_args, nv.ptr(lims),
+                           nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)), count_name)
             total = int(lims[-1].item())                      # the protocol's one host read: sizes the outputs
             outD = torch.empty(total, dtype=torch.float32, device=dev)
             outI = torch.empty(total, dtype=torch.int64, device=dev)
@@ -540,6 +565,7 @@ class _HipFlatIndex:
         self._stats = None
         self._prepared = None        # (planes, norms) of the resident rows for the batched search; dropped when rows change
         self._searches_since_change = 0
+        self._range_stats = None     # d_stats of the last range_search_device() that took the bitmap route
 
     def _rows_changed(self):
         """the resident rows changed in a way the prepared plane cannot follow (compaction, adoption of another matrix, reset)"""
@@ -765,10 +791,12 @@ class _HipFlatIndex:
 
     def range_search_device(self, q, radius, sel=None, max_ws_bytes=256 << 20):
         """q: [nq, d] fp32 tensor (any device), radius: float or [nq] tensor -> (lims, D, I) CUDA tensors (`knn_range_search`).
-        Searches the fp32 rows: the fp16 plane is neither needed nor prepared.
-        sel: a RowSelector, a bool mask [ntotal] or row ids (whatever `search(sel=)` accepts) -- the hits AMONG those rows.  The
-        routing is the top-k rule without the plane: a selector that carries <= KNN_IDS_MAX host ids takes the id-list route
-        (`knn_range_ids`), everything else the bitmap route on the fp32 rows; no bitmap is read back to choose."""
+        A range search NEVER prepares the fp16 plane; when one already exists (a top-k search or `prepare_store` built it and it
+        has followed the rows since) and the store has >= PLANE_MIN_ROWS rows, the count reads it (`prepared=`: half the bytes,
+        the same bits) -- `range_stats[2] == 2` then.  Otherwise the fp32 rows are searched.
+        sel: a RowSelector, a bool mask [ntotal] or row ids (whatever `search(sel=)` accepts) -- the hits AMONG those rows.  A
+        selector that carries <= KNN_IDS_MAX host ids takes the id-list route (`knn_range_ids`) first, everything else the bitmap
+        route; no bitmap is read back to choose."""
         self._materialize()
         q = q.detach().to(device=self.device, dtype=torch.float32)
         if q.dim() == 1:
@@ -779,7 +807,11 @@ class _HipFlatIndex:
             sel = self._as_selector(sel)
             if sel.ids is not None and sel.ids.numel() <= KNN_IDS_MAX:
                 return knn_range_ids(self._store, self._n, self.d, q, radius, sel.ids, metric=self.metric)
-        return knn_range_search(self._store, self._n, self.d, q, radius, metric=self.metric, max_ws_bytes=max_ws_bytes, sel=sel)
+        prepared = self._prepared if self._prepared is not None and self._n >= PLANE_MIN_ROWS else None
+        if self._range_stats is None and q.is_cuda:
+            self._range_stats = torch.zeros(4, dtype=torch.int32, device=q.device)
+        return knn_range_search(self._store, self._n, self.d, q, radius, metric=self.metric, max_ws_bytes=max_ws_bytes, sel=sel,
+                                stats=self._range_stats, prepared=prepared)
 
     def range_search(self, x, radius, sel=None):
         """faiss signature: numpy in, (lims int64 [nq + 1], D float32, I int64) numpy out.  L2: squared distance < radius;
@@ -787,6 +819,11 @@ class _HipFlatIndex:
         RowSelector, a bool mask or row ids."""
         lims, D, I = self.range_search_device(self._as_rows(x), radius, sel=sel)
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    @property
+    def range_stats(self):
+        """d_stats of the last bitmap-route range search as a list: [0] pairs decided exactly, [2] == 2 iff the count read the plane"""
+        return [0, 0, 0, 0] if self._range_stats is None else self._range_stats.tolist()
 
     @property
     def exact_fallbacks(self):

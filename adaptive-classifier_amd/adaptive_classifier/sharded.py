@@ -262,13 +262,15 @@ class ShardedSearch:
 
     def _local_range(self, queries, radius, sel):
         """this rank's shard range-searched: (lims, D fp32, global ids, exact fp64 values).  The injected `local_range` (CPU
-        tests) or `index.knn_range_search` with row_offset = sel_bit0 = this shard's first row."""
+        tests) or `index.knn_range_search` with row_offset = sel_bit0 = this shard's first row.  A range search never prepares
+        the shard's fp16 plane; one that a top-k search already built (>= PLANE_MIN_ROWS local rows) is counted over."""
         if self._range is None:
             from . import index as ix
 
             def _hip_range(P, n, D, Q, radius, off, sel, sel_bit0):
+                prepared = self._prepared if self._prepared is not None and n >= ix.PLANE_MIN_ROWS else None
                 return ix.knn_range_search(P, n, D, Q, radius, metric=self.metric, row_offset=off, exact_out=True, sel=sel,
-                                           sel_bit0=sel_bit0 if sel is not None else 0)
+                                           sel_bit0=sel_bit0 if sel is not None else 0, prepared=prepared)
             self._range = _hip_range
         return self._range(self.rows, self.n_local, self.dim, queries, radius, self.row_offset, sel, self.row_offset)
 

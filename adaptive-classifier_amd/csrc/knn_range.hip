@@ -1,6 +1,8 @@
 // Exact range search (radius queries) over the flat store: faiss IndexFlatL2.range_search / IndexFlatIP.range_search.
 //   ac_knn_{l2,ip}_range_count   membership of every (query, row) pair as a bitmap, per-query totals -> lims[nq + 1]
 //   ac_knn_{l2,ip}_range_fill    the bitmap expanded by ascending row id to I, the exact value of every hit to D (and D64)
+//   ac_knn_{l2,ip}_range_count_batch[_sel]   the count over a PREPARED store's fp16 plane (knn_plane_range, further down): the
+//                                same bitmaps, resolve, scan and fill; only the sweep and its thresholds differ
 // Contract (include/acamd.h): row n is a hit of query q iff float32(d64) < r_q (L2) / float32(v64) > r_q (IP), d64 / v64 the fp64
 // value ac_knn_*_topk rounds and returns.  Nothing here depends on the order in which atomics land: every bitmap piece is written
 // by exactly one wave with plain vector stores; the only atomic is an integer sum into d_stats[0].
@@ -516,6 +518,278 @@ __global__ __launch_bounds__(kPostWaves * 64) void knn_range_ids_fill(RangeParam
     }
 }
 
+// --------------------------------------------------------------------------------------
+// Range search over the PREPARED store's fp16 plane (ac_knn_*_range_count_batch): the count phase reads 2 B per store element.
+//   knn_plane_range_thresholds<IP>   one wave per query: |q|^2 in fp64, E_q = gamma (|p|max + |q|)^2, the two thresholds of the
+//                                    query rounded to fp32 to the safe side, the "can this query hit at all" flag.
+//   knn_plane_range<TQ, IP, SEL>     the load path and k-loop of knn_plane_sweep (knn_l2.hip -- a COPY: that kernel is left as it
+//                                    is, folding the two into one header is a follow-up) with a range epilogue: no lists, no
+//                                    pruning, no tau, no barrier and no LDS traffic after the k-loop.
+// After the sweep the launch sequence is the fp32 route's: knn_range_resolve decides every ambiguous pair from the fp32 rows by the
+// same fp64 value, knn_range_scan makes lims, and the unchanged knn_range_fill expands the same bitmap.
+//
+// The bound.  The sweep value is knn_plane_sweep's: L2 v = fmaf(acc, f_q, |p|^2) with |p|^2 from the prepared norms, IP v = f_q acc
+// (f_q = -2 2^(e_p + e_q), acc = h_p . h_q in the fp32 accumulator of v_mfma_f32_32x32x16_f16).  include/acamd.h derives
+//   |v - s| <= gamma_b (|p|max + |q|)^2,  gamma_b = knn_batch_gamma(D) = 1.01 (2^-11 + (Kp + 18 + sqrt Kp) 2^-24)
+// for s = |p|^2 - 2 p.q (L2) and s = -2 p.q (IP), |p|max = the store maximum kept at d_norms[round_up(N, 256)] -- the bound the
+// top-k certificate over the plane relies on.  It is a bound PER QUERY: the absolute 2^-25 sqrt(Kp) term of the fp16 rounding does
+// not shrink with a row's own norm, so no per-row form is used.  E_q = 1.02 gamma_b (|p|max~ + |q|~)^2 + 1e-30: the 2 % cover the
+// fp32 rounding of the stored maximum (2^-24 relative), the fp64 |q| and the (D + 3) 2^-53 (|p| + |q|)^2 of the exact fp64 value
+// (the argument at the top of this file, with gamma_b >= 2^-11 in place of gamma0).  With E_q a constant of the query both
+// thresholds are constants too, computed once in fp64 and rounded to fp32 so that the fp32 compare implies the fp64 one:
+//     L2  in : v <= fl_down((r- - |q|^2) - E)      out: v >= fl_up((r - |q|^2) + E)
+//     IP  in : v <= fl_down(-2 r+ - E)             out: v >= fl_up(-2 r + E)
+// Everything else is ambiguous: a NaN or infinite v, a NaN threshold (E or |q| not finite), an infinite threshold (no finite v is
+// beyond it).  Queries that cannot hit (NaN radius, L2 r <= 0, IP r = +inf) are switched off.  A STALE plane voids the bound.
+//
+// Bitmap writes.  A wave's tile is 32 consecutive rows: it owns the 32-BIT piece (query, row / 32) of bm_in and of bm_amb -- half a
+// word.  In the C/D layout of the 32x32 MFMA a lane holds 16 verdicts of its query column (rows plane_acc_row(r, lane)), the two
+// lane halves hold complementary rows: one __shfl_xor(.., 32) of a packed word joins them, lanes 0..31 store the non-zero pieces with
+// one plain 4-byte store each.  Exactly one writer per piece, no atomic; the bitmaps are zeroed by the memset before the sweep.
+// Rows past N -- zero plane rows whose IP value 0 beats every negative product, and the clamped reloads behind the last tile -- are
+// masked explicitly in both metrics; SEL ANDs the tile's 32 selection bits into both pieces and skips a tile without a selected row.
+// --------------------------------------------------------------------------------------
+struct PlaneRangeParams {
+    const uint16_t* Pp;       // store plane, tile-major (knn_batch.hip knn_plane_kernel)
+    const float* pnorm;       // [round_up(N, 256)] |p|^2, +inf past N
+    const uint16_t* Qp;       // query plane [Kp/8][q_rows][8]
+    int64_t q_rows;           // round_up(nq, 256)
+    const float* qfac;        // [q_rows] -2 2^(e_p + e_q)
+    const float* thr_in;      // [q_rows] certain-in  iff v <= thr_in
+    const float* thr_out;     // [q_rows] certain-out iff v >= thr_out
+    const int32_t* live;      // [q_rows] 0 = the query cannot hit (or is padding)
+    int64_t N;
+    int64_t ntiles;           // ceil(N / 256)
+    int64_t W;                // 64-bit words per query of each bitmap
+    uint64_t* bm_in;          // [nq][W]
+    uint64_t* bm_amb;         // [nq][W]
+    int32_t* stats;           // first launch of a call: stats[2] = 2 (the plane sweep ran); else NULL
+    int Kp;                   // multiple of 64
+    int q0, nq;               // this launch's query tile starts at q0; nq = queries of the whole call
+    int G;
+};
+struct PlaneRangeParamsSel : PlaneRangeParams {
+    const uint64_t* sel;
+    int64_t sel_bit0;
+};
+template <bool SEL> struct plane_range_params_of { typedef PlaneRangeParams type; };
+template <> struct plane_range_params_of<true> { typedef PlaneRangeParamsSel type; };
+
+// (knn_l2.hip plane_sel_bits) the 32 selection bits of a wave's rows row_base .. row_base + 31 (bit i = row row_base + i): two
+// 64-bit words at most, through the scalar unit, the second one only if one of its rows exists.  row_base < N.
+__device__ __forceinline__ uint32_t plane_range_sel_bits(const uint64_t* sel, int64_t sel_bit0, int64_t N, int row_base) {
+    typedef const uint64_t __attribute__((address_space(4)))* cup;
+    const uint32_t rem = __builtin_amdgcn_readfirstlane((uint32_t)(sel_bit0 & 63) + (uint32_t)row_base);     // (N < 2^31)
+    const cup w = (cup)(uintptr_t)(sel + (sel_bit0 >> 6) + (rem >> 6));
+    const int s = (int)(rem & 63u);
+    uint64_t bits = w[0] >> s;
+    if (s > 32 && row_base + (64 - s) < N) bits |= w[1] << (64 - s);
+    return (uint32_t)bits;
+}
+
+__device__ __forceinline__ float f32_round_down(double x) {        // the largest fp32 <= x (NaN stays NaN)
+    float t = (float)x;
+    if ((double)t > x) t = nextafterf(t, -INFINITY);
+    return t;
+}
+__device__ __forceinline__ float f32_round_up(double x) {          // the smallest fp32 >= x
+    float t = (float)x;
+    if ((double)t < x) t = nextafterf(t, INFINITY);
+    return t;
+}
+
+// one wave per row of the padded query plane (q_rows rows): rows past nq are switched off
+template <bool IP>
+__global__ __launch_bounds__(kPostWaves * 64) void knn_plane_range_thresholds(const float* Q, int64_t ldQ, int D, int nq, int64_t q_rows,
+                                                                              const float* radius, const float* maxnorm, double gamma,
+                                                                              float* thr_in, float* thr_out, int32_t* live) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * kPostWaves + (threadIdx.x >> 6);
+    if (row >= q_rows) return;                            // (wave-uniform)
+    double a = 0;
+    float r = NAN;
+    if (row < nq) {
+        const float* src = Q + (size_t)row * ldQ;
+        for (int c = lane; c < D; c += 64) a = fma((double)src[c], (double)src[c], a);
+        r = radius[row];
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a += __shfl_xor(a, o);
+    if (lane == 0) {
+        const double t = sqrt((double)maxnorm[0]) + sqrt(a);
+        const double E = gamma * t * t + 1e-30;
+        double cin, cout;
+        if (IP) {
+            cin = -2.0 * (double)nextafterf(r, INFINITY) - E;
+            cout = -2.0 * (double)r + E;
+        } else {
+            cin = ((double)nextafterf(r, -INFINITY) - a) - E;
+            cout = ((double)r - a) + E;
+        }
+        thr_in[row] = f32_round_down(cin);
+        thr_out[row] = f32_round_up(cout);
+        live[row] = (IP ? (r < INFINITY) : (r > 0.f)) ? 1 : 0;          // false for NaN and for the padding rows
+    }
+}
+
+typedef _Float16 rf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t ru32x4 __attribute__((ext_vector_type(4)));
+typedef float rf32x16 __attribute__((ext_vector_type(16)));
+
+template <int TQ, bool IP, bool SEL = false>
+__global__ __launch_bounds__(kThreads, 2) void knn_plane_range(typename plane_range_params_of<SEL>::type prm) {
+    constexpr int NJ = TQ / 32;                       // 32-column sub-tiles of the query tile
+    constexpr int NB = 4, GK = 4;                     // register buffers x k-steps per buffer (16 loads in flight)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i32 = lane & 31, kg = lane >> 5;
+    const int g = xcd_remap(blockIdx.x, prm.G);
+    if (blockIdx.x == 0 && tid == 0 && prm.stats) prm.stats[2] = 2;       // (after the count's memset of d_stats, same stream)
+    const int nk = prm.Kp >> 4;                       // 16-k MFMA steps per row
+    const int ngrp = nk / GK;                         // (Kp % 64 == 0)
+    // ---- LDS: the query fragments [nk][NJ][64] x 16 B, nothing else ----
+    ru32x4* Qs = reinterpret_cast<ru32x4*>(smem);
+    for (int t = tid; t < nk * NJ * 64; t += kThreads) {
+        const int l = t & 63, jj = (t >> 6) % NJ, s = (t >> 6) / NJ;
+        const int64_t qrow = prm.q0 + 32 * jj + (l & 31);          // (< q_rows: the plane is padded to 256 queries with zeros)
+        Qs[t] = *reinterpret_cast<const ru32x4*>(prm.Qp + ((int64_t)(2 * s + (l >> 5)) * prm.q_rows + qrow) * 8);
+    }
+    // this lane's query columns: factor, thresholds, live (the per-query arrays are q_rows long)
+    float qf[NJ], tin[NJ], tout[NJ];
+    bool live[NJ];
+#pragma unroll
+    for (int jj = 0; jj < NJ; ++jj) {
+        const int qrow = prm.q0 + 32 * jj + i32;
+        qf[jj] = prm.qfac[qrow]; tin[jj] = prm.thr_in[qrow]; tout[jj] = prm.thr_out[qrow];
+        live[jj] = qrow < prm.nq && prm.live[qrow] != 0;
+    }
+    __syncthreads();
+
+    const int64_t my_tiles = (prm.ntiles > g) ? (prm.ntiles - 1 - g) / prm.G + 1 : 0;
+    const int64_t total = my_tiles * ngrp;            // groups of GK k-steps this wave consumes
+    const size_t tile_bytes = (size_t)prm.Kp * 512;   // 256 rows x Kp x 2 B
+    const uint32_t lane_off = (uint32_t)(kg * 256 + 32 * wave + i32) * 16u;    // byte offset of this lane's piece inside a k-slot pair
+    int64_t pf_tile = 0;                              // prefetch state: next group to load
+    int pf_grp = 0;
+    auto tile_base = [&](int64_t it) -> const char* {
+        int64_t T = it * prm.G + g;
+        if (T > prm.ntiles - 1) T = prm.ntiles - 1;    // past the end: the last tile again (never consumed)
+        return reinterpret_cast<const char*>(prm.Pp) + (size_t)T * tile_bytes;
+    };
+    const char* pf_base = tile_base(0);
+    ru32x4 buf[NB][GK];
+#define AC_PR_PREFETCH(B)                                                                                     \
+    do {                                                                                                      \
+        const char* src_ = pf_base + (size_t)pf_grp * (GK * 8192) + lane_off;                                 \
+        _Pragma("unroll") for (int u = 0; u < GK; ++u)                                                        \
+            buf[B][u] = __builtin_nontemporal_load(reinterpret_cast<const ru32x4*>(src_ + u * 8192));          \
+        if (++pf_grp == ngrp) { pf_grp = 0; ++pf_tile; pf_base = tile_base(pf_tile); }                        \
+    } while (0)
+
+    rf32x16 acc[NJ];
+    int64_t cur_tile = 0;
+    int cur_grp = 0;
+    const size_t pieces = (size_t)prm.W * 2;          // 32-bit pieces per query
+    uint32_t* in32 = reinterpret_cast<uint32_t*>(prm.bm_in);
+    uint32_t* amb32 = reinterpret_cast<uint32_t*>(prm.bm_amb);
+
+    // per 32-row tile of this wave: classify 16 rows x NJ queries per lane, store the non-zero pieces
+    auto epilogue = [&]() {
+        const int row0 = __builtin_amdgcn_readfirstlane((int)((cur_tile * prm.G + g) * 256) + 32 * wave);     // (N < 2^31)
+        if (row0 >= prm.N) return;                                             // (wave-uniform) a tile of padding rows
+        const int64_t left = prm.N - row0;
+        uint32_t rowmask = left >= 32 ? 0xffffffffu : (1u << (int)left) - 1u;   // rows past N never set a bit, in either metric
+        if constexpr (SEL) {
+            rowmask &= plane_range_sel_bits(prm.sel, prm.sel_bit0, prm.N, row0);
+            if (rowmask == 0u) return;                                         // no selected row: nothing to classify or store
+        }
+        typedef const float __attribute__((address_space(4)))* cfp;
+        const cfp pn = (cfp)(uintptr_t)(prm.pnorm + row0);                     // (L2) |p|^2 of the wave's rows through the scalar unit
+        uint32_t in_b[NJ], amb_b[NJ];
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) { in_b[jj] = 0u; amb_b[jj] = 0u; }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rr = (r & 3) + 8 * (r >> 2);                             // this lane's row: rr + 4 kg (the MFMA's C/D layout)
+            float pnr = 0.f;
+            if constexpr (!IP) {
+                const float lo = pn[rr], hi = pn[rr + 4];
+                pnr = kg ? hi : lo;
+            }
+            const uint32_t bit = (1u << rr) << (4 * kg);
+#pragma unroll
+            for (int jj = 0; jj < NJ; ++jj) {
+                const float v = IP ? acc[jj][r] * qf[jj] : fmaf(acc[jj][r], qf[jj], pnr);      // knn_plane_sweep's value
+                const bool fin = fabsf(v) < INFINITY;                          // false for NaN too: the bound is void, decide exactly
+                const bool in = fin && v <= tin[jj];
+                const bool out = fin && v >= tout[jj];
+                if (in) in_b[jj] |= bit;
+                if (!in && !out) amb_b[jj] |= bit;
+            }
+        }
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            // lane half 0 holds rows {0-3, 8-11, ..} (mask 0x0f0f0f0f), half 1 the others: `in` stays in place, `amb` moves into
+            // the free nibbles, ONE shuffle exchanges both
+            const uint32_t packed = kg ? (in_b[jj] | (amb_b[jj] >> 4)) : (in_b[jj] | (amb_b[jj] << 4));
+            const uint32_t other = __shfl_xor(packed, 32);
+            uint32_t in_w = in_b[jj] | (other & 0xf0f0f0f0u);                   // (meaningful in lanes 0..31, which store)
+            uint32_t amb_w = amb_b[jj] | ((other & 0x0f0f0f0fu) << 4);
+            in_w &= rowmask; amb_w &= rowmask;
+            if (kg == 0 && live[jj] && (in_w | amb_w)) {
+                const size_t at = (size_t)(prm.q0 + 32 * jj + i32) * pieces + (size_t)(row0 >> 5);
+                if (in_w) in32[at] = in_w;
+                if (amb_w) amb32[at] = amb_w;
+            }
+        }
+    };
+
+#define AC_PR_COMPUTE(B)                                                                                      \
+    do {                                                                                                      \
+        if (cur_grp == 0) {                                                                                   \
+            _Pragma("unroll") for (int jj = 0; jj < NJ; ++jj)                                                 \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;                              \
+        }                                                                                                     \
+        const ru32x4* qsrc_ = Qs + (size_t)cur_grp * (GK * NJ * 64) + lane;                                    \
+        ru32x4 bq_[NJ];                                                                                        \
+        _Pragma("unroll") for (int jj = 0; jj < NJ; ++jj) bq_[jj] = qsrc_[jj * 64];                           \
+        _Pragma("unroll") for (int u = 0; u < GK; ++u) {                                                      \
+            const rf16x8 a_ = __builtin_bit_cast(rf16x8, buf[B][u]);                                          \
+            rf16x8 b_[NJ];                                                                                    \
+            _Pragma("unroll") for (int jj = 0; jj < NJ; ++jj) b_[jj] = __builtin_bit_cast(rf16x8, bq_[jj]);   \
+            if (u + 1 < GK) { /* LDS reads one step ahead */                                                  \
+                _Pragma("unroll") for (int jj = 0; jj < NJ; ++jj) bq_[jj] = qsrc_[((u + 1) * NJ + jj) * 64];  \
+            }                                                                                                 \
+            _Pragma("unroll") for (int jj = 0; jj < NJ; ++jj)                                                 \
+                acc[jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_, b_[jj], acc[jj], 0, 0, 0);               \
+            __builtin_amdgcn_sched_barrier(0); /* keep the per-load consume order */                          \
+        }                                                                                                     \
+        if (++cur_grp == ngrp) { epilogue(); cur_grp = 0; ++cur_tile; }                                       \
+    } while (0)
+
+    // Loads are issued unconditionally (past the end they re-read the last tile) so that every path has the same number of
+    // loads in flight (knn_plane_sweep: a load inside a branch makes hipcc wait on the buffer it has just issued).
+    if (total > 0) {
+        AC_PR_PREFETCH(0);
+        AC_PR_PREFETCH(1);
+        AC_PR_PREFETCH(2);
+        for (int64_t gg = 0; gg < total; gg += NB) {      // (ngrp may be odd: the tile boundary falls anywhere in this body)
+            AC_PR_PREFETCH(3);
+            AC_PR_COMPUTE(0);
+            AC_PR_PREFETCH(0);
+            if (gg + 1 < total) AC_PR_COMPUTE(1);
+            AC_PR_PREFETCH(1);
+            if (gg + 2 < total) AC_PR_COMPUTE(2);
+            AC_PR_PREFETCH(2);
+            if (gg + 3 < total) AC_PR_COMPUTE(3);
+        }
+    }
+#undef AC_PR_PREFETCH
+#undef AC_PR_COMPUTE
+}
+
 // ---- host side ----
 struct RangePlan {
     bool small;
@@ -674,6 +948,126 @@ int range_count_sel(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, co
                        sel_bit0);
 }
 
+// ---- the count over the PREPARED store's fp16 plane (ac_knn_*_range_count_batch[_sel]) ----
+constexpr int64_t kPlaneRangeMinRows = 65536;         // the limit of ac_knn_*_topk_batch
+
+struct PlaneRangePlan {
+    RangePlan rp;             // the fp32 route's plan: the workspace PREFIX (bm_in, bm_amb, cnt, off) is exactly its layout
+    int TQ, nqt, Kp;
+    int64_t ntiles, q_rows;   // 256-row tiles of the plane; rows of the padded query plane
+    size_t lds;
+    size_t off_qp, off_qfac, off_thr, off_tin, off_tout, off_live, total;
+};
+
+// host only (the workspace planner runs without a device); the grid is chosen at launch
+int make_plane_range_plan(int64_t N, int D, int nq, PlaneRangePlan* pl) {
+    *pl = PlaneRangePlan{};
+    const int rc = make_range_plan(N, D, nq, &pl->rp);                 // validates (N, D, nq); refuses a D the range search does not take
+    if (rc != AC_OK) return rc;
+    AC_REQUIRE(N >= kPlaneRangeMinRows && N < 2147483647LL - 512 && !pl->rp.small, AC_EUNSUPPORTED,
+               "knn range batch: N=%lld outside [%lld, 2^31 - 512): use ac_knn_*_range_count", (long long)N, (long long)kPlaneRangeMinRows);
+    pl->Kp = (D + 63) / 64 * 64;
+    auto lds_for = [&](int TQ) { return (size_t)(pl->Kp / 16) * (TQ / 32) * 1024; };
+    pl->TQ = (nq > 32 && lds_for(64) <= (size_t)kLdsLimit) ? 64 : 32;
+    AC_REQUIRE(lds_for(pl->TQ) <= (size_t)kLdsLimit, AC_EUNSUPPORTED, "knn range batch: D=%d: a 32-query tile of the plane exceeds LDS", D);
+    pl->lds = lds_for(pl->TQ);
+    pl->nqt = nq > 0 ? (nq + pl->TQ - 1) / pl->TQ : 1;
+    pl->ntiles = (N + 255) / 256;
+    pl->q_rows = ((int64_t)(nq > 0 ? nq : 1) + 255) / 256 * 256;
+    ac::WsTake take;
+    take.off = ac::align_up(pl->rp.total, 256);
+    pl->off_qp = take(ac::knn_planes_bytes(nq > 0 ? nq : 1, D));
+    pl->off_qfac = take((size_t)pl->q_rows * 4);
+    pl->off_thr = take((size_t)pl->q_rows * 4);                        // knn_prepare_queries' top-k threshold: written, not read
+    pl->off_tin = take((size_t)pl->q_rows * 4);
+    pl->off_tout = take((size_t)pl->q_rows * 4);
+    pl->off_live = take((size_t)pl->q_rows * 4);
+    pl->total = take.off;
+    return AC_OK;
+}
+
+// has_sel: the FILTERED form.  Every argument check returns before any HIP call.
+int range_count_batch(bool ip, const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+                      const float* d_Q, int nq, int64_t ldQ, const float* d_radius, bool has_sel, const uint64_t* d_sel, int64_t sel_bit0,
+                      int64_t* d_lims, void* d_ws, size_t ws_bytes, int32_t* d_stats, ac_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (has_sel) {
+        AC_REQUIRE(sel_bit0 >= 0, AC_EINVAL, "knn range batch sel: sel_bit0=%lld must be >= 0", (long long)sel_bit0);
+        AC_REQUIRE(d_sel != nullptr || N <= 0, AC_EINVAL, "knn range batch sel: d_sel is NULL");
+        AC_REQUIRE((((uintptr_t)d_sel) & 7) == 0, AC_EINVAL, "knn range batch sel: d_sel must be 8-byte aligned");
+    }
+    PlaneRangePlan pl;
+    int rc = make_plane_range_plan(N, D, nq, &pl);
+    if (rc != AC_OK) return rc;
+    if (nq == 0) return AC_OK;
+    AC_REQUIRE(d_planes != nullptr, AC_EINVAL, "knn range batch: d_planes is NULL");
+    AC_REQUIRE(d_norms != nullptr, AC_EINVAL, "knn range batch: d_norms is NULL");
+    AC_REQUIRE(d_P != nullptr, AC_EINVAL, "knn range batch: d_P is NULL");
+    AC_REQUIRE(d_Q && d_radius && d_lims, AC_EINVAL, "knn range batch: null pointer");
+    AC_REQUIRE((((uintptr_t)d_planes) & 15) == 0 && (((uintptr_t)d_norms) & 15) == 0, AC_EINVAL,
+               "knn range batch: d_planes / d_norms must be 16-byte aligned");
+    AC_REQUIRE(ldQ >= D && ldP >= pl.rp.Dp && (ldP % 4) == 0 && (((uintptr_t)d_P) & 15) == 0, AC_EINVAL,
+               "knn range batch: bad leading dimension / alignment (ldP=%lld, ldQ=%lld, d_P)", (long long)ldP, (long long)ldQ);
+    AC_REQUIRE(d_ws && ws_bytes >= pl.total, AC_EWORKSPACE, "knn range batch: workspace %zu < required %zu", ws_bytes, pl.total);
+    AC_REQUIRE((int64_t)nq * pl.rp.S < 2147483647LL * kPostWaves, AC_EUNSUPPORTED, "knn range batch: nq=%d x %lld strips exceeds one launch",
+               nq, (long long)pl.rp.S);
+    char* ws = (char*)d_ws;
+    if (d_stats) AC_HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(int32_t), stream));
+    const int64_t np = (N + 255) / 256 * 256;
+    const float* d_maxnorm = d_norms + np;                             // the store maximum |p|^2 (it only ever grows)
+    const double gamma_b = ac::knn_batch_gamma(D);
+    // 1. the queries' fp16 plane and epilogue factors: the kernel, scaling and rounding of the top-k search over the plane, hence
+    //    its bound; then the two thresholds of every query
+    rc = ac::knn_prepare_queries(nullptr, 1, d_Q, ldQ, D, nq, reinterpret_cast<const uint32_t*>(d_maxnorm), gamma_b,
+                                 (uint16_t*)(ws + pl.off_qp), (float*)(ws + pl.off_thr), (float*)(ws + pl.off_qfac), stream);
+    if (rc != AC_OK) return rc;
+    void (*thr_fn)(const float*, int64_t, int, int, int64_t, const float*, const float*, double, float*, float*, int32_t*) =
+        ip ? knn_plane_range_thresholds<true> : knn_plane_range_thresholds<false>;
+    hipLaunchKernelGGL(thr_fn, dim3(post_blocks(pl.q_rows)), dim3(kPostWaves * 64), 0, stream, d_Q, ldQ, D, nq, pl.q_rows, d_radius, d_maxnorm,
+                       1.02 * gamma_b, (float*)(ws + pl.off_tin), (float*)(ws + pl.off_tout), (int32_t*)(ws + pl.off_live));
+    AC_LAUNCH_CHECK();
+    // 2. both bitmaps start at zero (they are adjacent): the sweep stores non-zero pieces only
+    AC_HIP_CHECK(hipMemsetAsync(ws + pl.rp.off_in, 0, pl.rp.off_cnt - pl.rp.off_in, stream));
+    // 3. one pass over the plane per query tile: one 8-wave workgroup per CU, one residency round
+    PlaneRangeParamsSel sp{};                          // (the plain kernels take its PlaneRangeParams base)
+    sp.Pp = d_planes; sp.pnorm = d_norms; sp.Qp = (const uint16_t*)(ws + pl.off_qp); sp.q_rows = pl.q_rows;
+    sp.qfac = (const float*)(ws + pl.off_qfac); sp.thr_in = (const float*)(ws + pl.off_tin); sp.thr_out = (const float*)(ws + pl.off_tout);
+    sp.live = (const int32_t*)(ws + pl.off_live); sp.N = N; sp.ntiles = pl.ntiles; sp.W = pl.rp.W;
+    sp.bm_in = (uint64_t*)(ws + pl.rp.off_in); sp.bm_amb = (uint64_t*)(ws + pl.rp.off_amb);
+    sp.Kp = pl.Kp; sp.nq = nq;
+    int64_t G = ac::dev_info().cus;
+    if (G > pl.ntiles) G = pl.ntiles;
+    sp.G = (int)G;
+    sp.sel = d_sel; sp.sel_bit0 = sel_bit0;
+    for (int qt = 0; qt < pl.nqt; ++qt) {
+        sp.q0 = qt * pl.TQ;
+        sp.stats = qt == 0 ? d_stats : nullptr;
+        if (has_sel) {
+            void (*fn)(PlaneRangeParamsSel);
+            if (pl.TQ == 64) fn = ip ? knn_plane_range<64, true, true> : knn_plane_range<64, false, true>;
+            else fn = ip ? knn_plane_range<32, true, true> : knn_plane_range<32, false, true>;
+            AC_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+            hipLaunchKernelGGL(fn, dim3(sp.G), dim3(kThreads), pl.lds, stream, sp);
+        } else {
+            void (*fn)(PlaneRangeParams);
+            if (pl.TQ == 64) fn = ip ? knn_plane_range<64, true> : knn_plane_range<64, false>;
+            else fn = ip ? knn_plane_range<32, true> : knn_plane_range<32, false>;
+            AC_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+            hipLaunchKernelGGL(fn, dim3(sp.G), dim3(kThreads), pl.lds, stream, static_cast<PlaneRangeParams&>(sp));
+        }
+        AC_LAUNCH_CHECK();
+    }
+    // 4. the fp32 route's tail, unchanged: the ambiguous pairs decided from the fp32 rows, the strip counts scanned into lims
+    RangeParams p = range_params(pl.rp, d_P, N, ldP, D, d_Q, nq, ldQ, ws, d_stats);
+    p.radius = d_radius;
+    void (*res_fn)(RangeParams) = ip ? knn_range_resolve<true> : knn_range_resolve<false>;
+    hipLaunchKernelGGL(res_fn, dim3(post_blocks((int64_t)nq * pl.rp.S)), dim3(kPostWaves * 64), 0, stream, p);
+    AC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(knn_range_scan, dim3(1), dim3(kScanThreads), 0, stream, (const int32_t*)p.cnt, p.off, d_lims, nq, pl.rp.S);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
+}
+
 // ---- id-list route ----
 struct RangeIdsPlan {
     bool lane_order;      // the summation order of the bitmap route's small-store kernel (else the wave order)
@@ -790,6 +1184,45 @@ extern "C" int ac_knn_ip_range_count_sel(const float* d_P, int64_t N, int64_t ld
                                          const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims, void* d_ws,
                                          size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
     return range_count_sel(true, d_P, N, ldP, D, d_Q, nq, ldQ, d_radius, d_sel, sel_bit0, d_lims, d_ws, ws_bytes, d_stats, stream);
+}
+
+extern "C" int ac_knn_range_batch_workspace(int64_t N, int D, int nq, size_t* bytes) {
+    AC_REQUIRE(bytes != nullptr, AC_EINVAL, "knn range batch workspace: bytes is NULL");
+    PlaneRangePlan pl;
+    const int rc = make_plane_range_plan(N, D, nq, &pl);
+    if (rc != AC_OK) return rc;
+    *bytes = pl.total;
+    return AC_OK;
+}
+
+extern "C" int ac_knn_l2_range_count_batch(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+                                           const float* d_Q, int nq, int64_t ldQ, const float* d_radius, int64_t* d_lims, void* d_ws,
+                                           size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
+    return range_count_batch(false, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, d_radius, false, nullptr, 0, d_lims, d_ws, ws_bytes,
+                             d_stats, stream);
+}
+
+extern "C" int ac_knn_ip_range_count_batch(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes, const float* d_norms,
+                                           const float* d_Q, int nq, int64_t ldQ, const float* d_radius, int64_t* d_lims, void* d_ws,
+                                           size_t ws_bytes, int32_t* d_stats, ac_stream_t stream) {
+    return range_count_batch(true, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, d_radius, false, nullptr, 0, d_lims, d_ws, ws_bytes,
+                             d_stats, stream);
+}
+
+extern "C" int ac_knn_l2_range_count_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
+                                               const float* d_norms, const float* d_Q, int nq, int64_t ldQ, const float* d_radius,
+                                               const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims, void* d_ws, size_t ws_bytes,
+                                               int32_t* d_stats, ac_stream_t stream) {
+    return range_count_batch(false, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, d_radius, true, d_sel, sel_bit0, d_lims, d_ws, ws_bytes,
+                             d_stats, stream);
+}
+
+extern "C" int ac_knn_ip_range_count_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D, const uint16_t* d_planes,
+                                               const float* d_norms, const float* d_Q, int nq, int64_t ldQ, const float* d_radius,
+                                               const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims, void* d_ws, size_t ws_bytes,
+                                               int32_t* d_stats, ac_stream_t stream) {
+    return range_count_batch(true, d_P, N, ldP, D, d_planes, d_norms, d_Q, nq, ldQ, d_radius, true, d_sel, sel_bit0, d_lims, d_ws, ws_bytes,
+                             d_stats, stream);
 }
 
 extern "C" int ac_knn_range_ids_workspace(int64_t M, int nq, size_t* bytes) {

@@ -327,8 +327,8 @@ int ac_knn_ip_range_fill(const float* d_P, int64_t N, int64_t ldP, int D,
  *
  * FILTERED RANGE search -- faiss IndexFlat.range_search(x, r, params=SearchParameters(sel=...)): row n is a hit iff it is
  * selected AND the predicate of the range search holds.  Everything else is the unfiltered range search: hits by ascending row
- * id, lims, D = the fp64 value rounded once, d_outD64, the special radii, N = 0, nq = 0.  Over the fp32 rows only (no
- * prepared-store form).
+ * id, lims, D = the fp64 value rounded once, d_outD64, the special radii, N = 0, nq = 0.  These entry points read the fp32
+ * rows; the form over a prepared store is ac_knn_*_range_count_batch_sel ("RANGE search over a PREPARED store" below).
  *   ac_knn_l2_range_count_sel / ac_knn_ip_range_count_sel   the BITMAP route: the arguments of ac_knn_*_range_count plus
  *       (d_sel, sel_bit0) after d_radius -- the selection layout above, no word behind word (sel_bit0 + N - 1) / 64 is read.
  *       Same workspace (ac_knn_range_workspace), same supported (N, D), same protocol: ac_knn_*_range_fill then fills from that
@@ -426,6 +426,64 @@ int ac_knn_ip_range_fill_ids(const float* d_P, int64_t N, int64_t ldP, int D,
                              float* d_outD, double* d_outD64, int64_t* d_outI,
                              void* d_ws, size_t ws_bytes, int32_t* d_stats,
                              ac_stream_t stream);
+/*
+ * RANGE search over a PREPARED store (ac_knn_prepare_store / ac_knn_update_store, unchanged: the plane and norms the top-k search
+ * uses): the COUNT phase reads the fp16 plane, 2 B per store element instead of 4 B.  The result contract is
+ * ac_knn_*_range_count[_sel]'s, word for word: lims, and after the fill I, D and D64, are bit for bit what the fp32 route returns,
+ * at ANY radius -- both routes decide every pair that is not certain by the same exact fp64 value from the fp32 rows.
+ *   ac_knn_range_batch_workspace   bytes of d_ws (both metrics).  Its first ac_knn_range_workspace(N, D, nq) bytes have exactly the
+ *       layout of the fp32 route (membership bitmaps, strip counts, strip offsets); the query plane, factors and thresholds follow.
+ *   ac_knn_*_range_count_batch     the arguments of ac_knn_*_range_count with (d_planes, d_norms) after D, as in
+ *       ac_knn_*_topk_batch.  Then the UNCHANGED ac_knn_*_range_fill fills from the same d_ws, on the same stream, with the same
+ *       (N, D, nq) -- it needs only the prefix.
+ *   ac_knn_*_range_count_batch_sel the FILTERED form: (d_sel, sel_bit0) after d_radius, as in ac_knn_*_range_count_sel; an
+ *       all-ones selection returns the bits of the unfiltered call, d_stats included.
+ * Limits: N >= 65536 and N < 2^31 - 512, an (N, D) ac_knn_range_workspace accepts and whose 32-query tile of the query plane
+ * (round_up(D, 64) * 64 bytes) fits in LDS; AC_EUNSUPPORTED otherwise -- the caller then uses ac_knn_*_range_count.  Any nq (one
+ * pass over the plane per 64 queries); nq = 0 returns AC_OK and writes nothing.
+ * d_stats (optional int32[4]): [0] = the (query, row) pairs decided by exact arithmetic (with a selection: selected pairs only),
+ * [2] = 2: the plane sweep ran (the fill leaves [2] alone), [1] = [3] = 0.
+ * AC_EINVAL, before any device work, names the argument: d_planes / d_norms / d_P NULL with nq > 0, d_planes / d_norms not 16-byte
+ * aligned, the alignment and ldP / ldQ rules of ac_knn_l2_topk_batch, the d_sel rules of ac_knn_*_range_count_sel; AC_EWORKSPACE
+ * with the required size.
+ * The store MUST match the rows (ac_knn_prepare_store after the last change, or ac_knn_update_store for every change): the
+ * certain-in / certain-out verdicts rest on the plane's error bound, and a stale plane voids it.
+ * Mechanism (csrc/knn_range.hip, profiles/knn_range_batch/README.md): knn_plane_range, the load path of knn_plane_sweep with a range
+ * epilogue.  Sweep value v as in ac_knn_*_topk_batch (L2 v = |p|^2 + f_q acc, IP v = f_q acc) with the bound derived there,
+ * |v - s| <= gamma (|p|max + |q|)^2, gamma = 1.01 (2^-11 + (K + 18 + sqrt K) 2^-24), |p|max from d_norms[round_up(N, 256)].  It
+ * depends on the query only, so E_q = 1.02 gamma (|p|max + |q|)^2 (the 2 % as in the fp32 route: the fp64 |q|, the fp32 |p|max, the
+ * fp64 error of the exact value) gives two constants per query, computed in fp64 and rounded to fp32 to the safe side:
+ *   L2: certain-in iff v <= (r- - |q|^2) - E_q, certain-out iff v >= (r - |q|^2) + E_q   (r-, r+ the fp32 neighbours of r)
+ *   IP: certain-in iff v <= -2 r+ - E_q,        certain-out iff v >= -2 r + E_q
+ * and every other pair -- a NaN or infinite v or threshold included -- goes to the exact decision.  Queries that cannot hit (NaN
+ * radius, L2 r <= 0, IP r = +inf) are switched off; rows past N are masked explicitly in both metrics.  The band of undecided
+ * values is ~40x wider than the fp32 sweep's (2^-11 against ~D 2^-24 / 16): more pairs reach the exact decision.
+ */
+int ac_knn_range_batch_workspace(int64_t N, int D, int nq, size_t* bytes);
+int ac_knn_l2_range_count_batch(const float* d_P, int64_t N, int64_t ldP, int D,
+                                const uint16_t* d_planes, const float* d_norms,
+                                const float* d_Q, int nq, int64_t ldQ,
+                                const float* d_radius, int64_t* d_lims,
+                                void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                ac_stream_t stream);
+int ac_knn_ip_range_count_batch(const float* d_P, int64_t N, int64_t ldP, int D,
+                                const uint16_t* d_planes, const float* d_norms,
+                                const float* d_Q, int nq, int64_t ldQ,
+                                const float* d_radius, int64_t* d_lims,
+                                void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                ac_stream_t stream);
+int ac_knn_l2_range_count_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                                    const uint16_t* d_planes, const float* d_norms,
+                                    const float* d_Q, int nq, int64_t ldQ,
+                                    const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims,
+                                    void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                    ac_stream_t stream);
+int ac_knn_ip_range_count_batch_sel(const float* d_P, int64_t N, int64_t ldP, int D,
+                                    const uint16_t* d_planes, const float* d_norms,
+                                    const float* d_Q, int nq, int64_t ldQ,
+                                    const float* d_radius, const uint64_t* d_sel, int64_t sel_bit0, int64_t* d_lims,
+                                    void* d_ws, size_t ws_bytes, int32_t* d_stats,
+                                    ac_stream_t stream);
 int ac_knn_sel_pack(const uint8_t* d_mask, int64_t n, uint64_t* d_sel, ac_stream_t stream);
 int ac_knn_sel_classes(const int32_t* d_row_class, int64_t n, const uint8_t* d_class_on, int n_classes,
                        uint64_t* d_sel, ac_stream_t stream);

@@ -26,6 +26,7 @@ class NativeError(RuntimeError):
 AC_GEMM_F32, AC_GEMM_BF16X3, AC_GEMM_F16X2 = 0, 1, 2     # include/acamd.h: ac_gemm_set_arith
 AC_BERT_LAYERED = 1     # include/acamd.h: ac_bert_encode_cls_opts never takes the one-launch path
 AC_BERT_PATH_PACKED, AC_BERT_PATH_PADDED, AC_BERT_PATH_PADDED_MASK = 0, 1, 2     # ac_bert_encode_cls_unpad's *path
+AC_POOL_DEFAULT, AC_POOL_CLS, AC_POOL_MEAN = 0, 1, 2     # ac_bert_config.pool_opt / ac_modernbert_config.pool_opt (0 = CLS)
 
 
 def build(force=False):
@@ -44,7 +45,8 @@ class ac_bert_config(ctypes.Structure):
     _fields_ = [("hidden", c_int), ("layers", c_int), ("heads", c_int), ("intermediate", c_int),
                 ("vocab", c_int), ("max_pos", c_int), ("type_vocab", c_int), ("ln_eps", c_float),
                 # per-call options, 0 = process default, else value + 1 (include/acamd.h)
-                ("gemm_arith_opt", c_int), ("ln_fusion_opt", c_int), ("one_launch_opt", c_int)]
+                ("gemm_arith_opt", c_int), ("ln_fusion_opt", c_int), ("one_launch_opt", c_int),
+                ("pool_opt", c_int)]             # AC_POOL_*: what the encode calls write per sequence (ac_version() >= 9)
 
 
 class ac_prune_job(ctypes.Structure):
@@ -55,7 +57,8 @@ class ac_prune_job(ctypes.Structure):
 class ac_modernbert_config(ctypes.Structure):
     _fields_ = [("hidden", c_int), ("layers", c_int), ("heads", c_int), ("intermediate", c_int), ("vocab", c_int),
                 ("max_pos", c_int), ("global_every", c_int), ("local_window", c_int), ("norm_eps", c_float),
-                ("gemm_arith_opt", c_int)]       # per-call option, 0 = process default, else AC_GEMM_* + 1
+                ("gemm_arith_opt", c_int),       # per-call option, 0 = process default, else AC_GEMM_* + 1
+                ("pool_opt", c_int)]             # per-call option, AC_POOL_* (ac_version() >= 9)
 
 
 class ac_modernbert_weights(ctypes.Structure):

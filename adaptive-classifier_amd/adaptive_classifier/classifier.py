@@ -84,6 +84,13 @@ class AdaptiveClassifier:
         if use_onnx is True:
             logger.warning("use_onnx=True ignored: ONNX Runtime is a CPU optimisation outside this build's scope")
         self.model_name = model_name
+        # config["pooling"]: "cls" (default, the reference's embedding) | "mean" (the attention-masked mean of the sentence-embedding
+        # checkpoints: MiniLM family, e5, ModernBERT with classifier_pooling="mean").  PER OBJECT like gemm_arith: it travels with
+        # every encoder call this classifier makes (encode_cls(pooling=...) -> ac_bert_config.pool_opt); save() records it, so that
+        # prototypes built from mean-pooled rows are never searched with CLS rows.
+        from .encoder import pooling_mode
+        self._pooling = (config or {}).get("pooling") or "cls"
+        pooling_mode(self._pooling)                                              # ValueError on an unknown name
         if encoder is None:
             from transformers import AutoModel, AutoTokenizer
             from .encoder import make_encoder
@@ -93,6 +100,10 @@ class AdaptiveClassifier:
             if tokenizer is None:
                 tokenizer = AutoTokenizer.from_pretrained(model_name, trust_remote_code=trust_remote_code)
         self.model = encoder
+        if self._pooling != "cls" and "pooling" not in self._encoder_options():
+            raise ValueError(f"config['pooling'] = {self._pooling!r} needs an encoder whose encode_cls takes `pooling` "
+                             f"(HipBertEncoder / HipModernBertEncoder); {type(encoder).__name__}.encode_cls does not, and its "
+                             "embeddings would silently be something else")
         # config["gemm_arith"]: "f32" | "bf16x3" | "f16x2" (opt-in, include/acamd.h) | absent = the process-wide default.
         # PER OBJECT: it travels with every encoder call this classifier makes (encode_cls(arith=...) -> ac_bert_config.
         # gemm_arith_opt); no process-wide switch is touched, other classifiers -- even on the same encoder -- keep theirs.
@@ -339,7 +350,7 @@ class AdaptiveClassifier:
             try:
                 params = inspect.signature(self.model.encode_cls).parameters
                 anykw = any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
-                opts = {name for name in ("verify", "force_layered", "arith") if anykw or name in params}
+                opts = {name for name in ("verify", "force_layered", "arith", "pooling") if anykw or name in params}
             except (TypeError, ValueError):
                 opts = set()
             cached = self._enc_opts = (self.model, opts)
@@ -358,6 +369,13 @@ class AdaptiveClassifier:
             kw["force_layered"] = force_layered
         if "arith" in opts and getattr(self, "_gemm_arith", None) is not None:
             kw["arith"] = self._gemm_arith
+        pooling = getattr(self, "_pooling", "cls")
+        if pooling != "cls":
+            if "pooling" not in opts:              # (the encoder object was swapped after construction)
+                raise ValueError(f"config['pooling'] = {pooling!r}: {type(self.model).__name__}.encode_cls takes no `pooling`")
+            kw["pooling"] = pooling
+        elif "pooling" in opts:
+            kw["pooling"] = "cls"                  # explicit: an encoder whose own default is "mean" must not leak into this classifier
         return self.model.encode_cls(input_ids, token_type_ids, attention_mask, **kw)
 
     def _embed_device(self, texts: List[str], verify: bool = True, force_layered: bool = False) -> torch.Tensor:
@@ -1176,6 +1194,10 @@ class AdaptiveClassifier:
                "label_to_id": self.label_to_id, "id_to_label": {str(k): v for k, v in self.id_to_label.items()},
                "train_steps": self.train_steps, "training_history": self.training_history,
                "config": self.config.to_dict(), "library_name": "adaptive-classifier"}
+        if getattr(self, "_pooling", "cls") != "cls":
+            # (only when it is not the default: directories of default classifiers keep their bytes; the reference's ModelConfig
+            #  reads its keys with .get and ignores this one)
+            cfg["config"]["pooling"] = self._pooling
         (d / "config.json").write_text(json.dumps(cfg, indent=2, sort_keys=True))
         keep = (lambda exs: exs) if all_examples else \
             (lambda exs: select_representative_examples(exs, k=self.config.num_representative_examples))

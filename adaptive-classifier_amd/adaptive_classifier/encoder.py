@@ -5,7 +5,9 @@ Replaces `self.model(**inputs).last_hidden_state[:, 0, :]` + `F.normalize`
 checkpoints (bert-base-uncased, bert-large, e5-large-v2, bert-tiny, distilbert-base-*, roberta-*, xlm-roberta-* /
 multilingual-e5-*) with one native call,
 `ac_bert_encode_cls`, that writes unit-norm CLS vectors straight into a device buffer usable as the
-kNN query block (no device->host copy, cf. classifier.py:1282).
+kNN query block (no device->host copy, cf. classifier.py:1282).  `pooling="mean"` (per encoder or per call) returns the
+attention-masked mean of the token states instead -- the embedding the MiniLM family, e5 and ModernBERT with
+classifier_pooling="mean" were trained with -- through the same native calls (`ac_bert_config.pool_opt`).
 
 Weights are taken from a transformers `BertModel` (pretrained or randomly initialised); Q/K/V
 projections are fused into one [3H, H] matrix.  `HipModernBertEncoder` covers ModernBERT
@@ -52,11 +54,23 @@ def arith_mode(value):
     return int(value)
 
 
+POOLINGS = {"cls": nv.AC_POOL_CLS, "mean": nv.AC_POOL_MEAN}
+
+
+def pooling_mode(value):
+    """"cls" | "mean" -> AC_POOL_*; anything else: ValueError."""
+    if not isinstance(value, str) or value not in POOLINGS:
+        raise ValueError(f"pooling must be one of {sorted(POOLINGS)}, got {value!r}")
+    return POOLINGS[value]
+
+
 class HipBertEncoder:
-    def __init__(self, hf_bert, device=None, unpad=True):
+    def __init__(self, hf_bert, device=None, unpad=True, pooling="cls"):
         """unpad: leave the padding tokens out of the forward (ac_bert_pack + ac_bert_encode_cls_packed) whenever the
         attention mask is right-padded -- same CLS vectors from sum(len) token rows instead of b * S."""
+        pooling_mode(pooling)                 # (ValueError on an unknown name, before anything touches the device)
         nv.require_gpu()
+        self.pooling = pooling                # "cls" | "mean": what encode_cls() returns when the call names none
         self.unpad = bool(unpad)
         self.last_tokens = 0                  # token rows the last encode_cls call actually ran (roofline accounting)
         self.last_one_launch = False          # the last native call ran as the one persistent launch (bert_small.hip)
@@ -215,25 +229,28 @@ class HipBertEncoder:
         self.ln_fusion = False
         return self
 
-    def _call_cfg(self, arith=None):
-        """ac_bert_config of one native call: the architecture + this call's options (0 = process default, else value + 1)."""
+    def _call_cfg(self, arith=None, pooling=None):
+        """ac_bert_config of one native call: the architecture + this call's options (0 = process default, else value + 1;
+        pool_opt: AC_POOL_*, 0 for "cls" -- the struct a call without the option always passed)."""
         a = arith_mode(arith)
         if a is None:
             a = self.arith
+        pool = pooling_mode(self.pooling if pooling is None else pooling)
         c = self.ccfg
         return nv.ac_bert_config(c.hidden, c.layers, c.heads, c.intermediate, c.vocab, c.max_pos, c.type_vocab, c.ln_eps,
                                  0 if a is None else a + 1,
-                                 0 if self.ln_fusion is None else (2 if self.ln_fusion else 1), 0)
+                                 0 if self.ln_fusion is None else (2 if self.ln_fusion else 1), 0,
+                                 nv.AC_POOL_MEAN if pool == nv.AC_POOL_MEAN else nv.AC_POOL_DEFAULT)
 
-    def _call_cfg_shared(self, arith=None):
-        """_call_cfg for encode_cls's own use: one struct per (arithmetic, fusion) state, never handed out, never modified."""
+    def _call_cfg_shared(self, arith=None, pooling=None):
+        """_call_cfg for encode_cls's own use: one struct per (arithmetic, fusion, pooling) state, never handed out, never modified."""
         a = arith_mode(arith)
         if a is None:
             a = self.arith
-        key = (a, self.ln_fusion)
+        key = (a, self.ln_fusion, self.pooling if pooling is None else pooling)
         cached = self.__dict__.get("_cfg_cache")
         if cached is None or cached[0] != key:
-            cached = self._cfg_cache = (key, self._call_cfg(arith))
+            cached = self._cfg_cache = (key, self._call_cfg(arith, pooling))
         return cached[1]
 
     # -- the nn.Module-ish surface classifier.py touches (:1253-1255,1278-1279,1215) ----------
@@ -268,8 +285,13 @@ class HipBertEncoder:
         return got
 
     def encode_cls(self, input_ids, token_type_ids=None, attention_mask=None, out=None, verify=True, force_layered=False,
-                   verify_small=None, arith=None):
-        """int64 [b, S] ids (+ optional type ids / mask) -> unit-norm CLS embeddings [b, H] on device.
+                   verify_small=None, arith=None, pooling=None):
+        """int64 [b, S] ids (+ optional type ids / mask) -> unit-norm embeddings [b, H] on device.
+        pooling: "cls" = F.normalize(last_hidden_state[:, 0, :]), the reference's embedding; "mean" = the attention-masked mean of
+        the sentence-embedding checkpoints, F.normalize(sum over the tokens with mask != 0 of last_hidden_state / count) (no mask:
+        every token; a row without any admitted token comes back exactly zero); None = this encoder's `pooling` ("cls" unless
+        set).  A per-call option inside ac_bert_config like `arith`.  Under "mean" the last layer runs on every token row (the
+        CLS-only tail saves nothing there) and <= 32 token rows go layer by layer: the one persistent launch ends in the CLS row.
         arith: this call's GEMM arithmetic ("f32" | "bf16x3" | "f16x2"; None = this encoder's `arith`, else the process default) --
         a per-call option inside ac_bert_config, no process-wide state is touched.
 
@@ -302,7 +324,9 @@ class HipBertEncoder:
             # layer by layer (bert-large: no one-launch kernel; a one-launch abort retried layered) reads them below without
             # having cleared them, and torch.empty memory is garbage -- a spurious "gave up" would switch the fusion off
             self._ws[:256].zero_()
-        cfg = self._call_cfg_shared(arith)
+        cfg = self._call_cfg_shared(arith, pooling)
+        if cfg.pool_opt == nv.AC_POOL_MEAN:
+            force_layered = True              # (what the native call does with <= 32 rows anyway: no pooled one-launch form)
         with torch.cuda.device(self.device):
             # the fused-LayerNorm verdict of this call starts clean (sticky over the chunks below; include/acamd.h); a call
             # that runs as the one persistent launch has no such epilogue (and is the latency path: no extra launch)
@@ -314,7 +338,7 @@ class HipBertEncoder:
                     "CU-masked?); LayerNorm fusion is now off for this encoder and the batch is encoded again")
                 self.ln_gave_up += 1
                 self.disable_ln_fusion()
-                cfg = self._call_cfg_shared(arith)
+                cfg = self._call_cfg_shared(arith, pooling)
                 self._run_chunks(ids, tt, mk, b, S, cb, out, verify, force_layered, cfg, clear=True)
             if verify and layered and self.f16x2_active(arith) and not bool(torch.isfinite(out).all()):
                 # an activation beyond fp16's range at scale 2^6 turned its rows into NaN (never into a wrong number)
@@ -329,9 +353,11 @@ class HipBertEncoder:
                 # an encoder-level or process-level f16x2 becomes an encoder-level bf16x3
                 if arith_mode(arith) is None:
                     self.arith = nv.AC_GEMM_BF16X3
-                cfg = self._call_cfg_shared(nv.AC_GEMM_BF16X3)
+                cfg = self._call_cfg_shared(nv.AC_GEMM_BF16X3, pooling)
                 self._run_chunks(ids, tt, mk, b, S, cb, out, verify, force_layered, cfg)
         return out
+
+    encode = encode_cls       # the general name (same function, same docstring): the embedding need not be the CLS row, see `pooling`
 
     # one call for packing + forward, no stream synchronisation (include/acamd.h ac_bert_encode_cls_unpad); AC_BERT_UNPAD_ONE_CALL=0
     # keeps the separate ac_bert_pack -> read-back -> ac_bert_encode_cls_packed form (A/B runs, the equivalence test)
@@ -429,24 +455,29 @@ class HipBertEncoder:
                                                    ctypes.byref(aborted), nv.stream_ptr(self.device)), "ac_bert_ln_fusion_status")
         return bool(aborted.value)
 
-    def flops(self, b, S, executed=True, tokens=None, sum_len_sq=None):
+    def flops(self, b, S, executed=True, tokens=None, sum_len_sq=None, pooling=None):
         """FLOPs of one forward (dense projections + attention), for roofline reports.
         executed=True counts what the kernels run (the last layer's output projection / FFN and its
-        attention only touch the b CLS rows); executed=False is the full BertModel.forward count.
-        tokens / sum_len_sq: the padding-free path's row count and sum of squared sequence lengths (attention)."""
+        attention only touch the b CLS rows -- under pooling="mean" the last layer is a full token layer like the others);
+        executed=False is the full BertModel.forward count.
+        tokens / sum_len_sq: the padding-free path's row count and sum of squared sequence lengths (attention).
+        pooling: as encode_cls (None = this encoder's)."""
         c = self.ccfg
         H, I, L = c.hidden, c.intermediate, c.layers
         T = b * S
+        mean = pooling_mode(self.pooling if pooling is None else pooling) == nv.AC_POOL_MEAN
         if tokens is not None and executed:
             per_tok = 2.0 * (4.0 * H * H + 2.0 * H * I)
             ssq = float(sum_len_sq if sum_len_sq is not None else tokens * tokens / max(b, 1))
             attn_layer = 4.0 * c.heads * ssq * (H // c.heads)
+            if mean:
+                return (per_tok * tokens + attn_layer) * L
             qkv_last = (2.0 * tokens * 2.0 * H * H + 2.0 * b * H * H) if tokens >= 4 * b else 2.0 * tokens * 3.0 * H * H
             last = qkv_last + 2.0 * b * (H * H + 2.0 * H * I) + 4.0 * c.heads * tokens * (H // c.heads)
             return per_tok * tokens * (L - 1) + attn_layer * (L - 1) + last
         per_tok = 2.0 * (4.0 * H * H + 2.0 * H * I)
         attn_layer = 4.0 * b * c.heads * S * S * (H // c.heads)
-        if not executed:
+        if not executed or mean:
             return per_tok * T * L + attn_layer * L
         # (last layer: K and V of every token, Q of the b CLS rows only when the batch has >= 4 token rows per sequence)
         qkv_last = (2.0 * T * 2.0 * H * H + 2.0 * b * H * H) if T >= 4 * b else 2.0 * T * 3.0 * H * H
@@ -475,8 +506,10 @@ def _split_planes_f16(t, device):
 class HipModernBertEncoder:
     """ModernBERT (transformers modeling_modernbert.py) behind the same surface as HipBertEncoder."""
 
-    def __init__(self, hf_model, device=None, unpad=True):
+    def __init__(self, hf_model, device=None, unpad=True, pooling="cls"):
+        pooling_mode(pooling)                 # (ValueError on an unknown name, before anything touches the device)
         nv.require_gpu()
+        self.pooling = pooling              # "cls" | "mean" (classifier_pooling="mean"): what encode_cls() returns when the call names none
         self.unpad = bool(unpad)            # leave the padding tokens of ragged batches out of the forward
         self.last_tokens = 0
         cfg = hf_model.config
@@ -499,7 +532,7 @@ class HipModernBertEncoder:
         self.config = _Cfg(H, getattr(cfg, "_name_or_path", ""))
         self.training = False
         self.ccfg = nv.ac_modernbert_config(H, L, A, I, cfg.vocab_size, cfg.max_position_embeddings, every,
-                                            int(cfg.sliding_window), float(cfg.norm_eps), 0)
+                                            int(cfg.sliding_window), float(cfg.norm_eps), 0, 0)
         self.arith = None               # this encoder's GEMM arithmetic (None = the process default); per call: encode_cls(arith=)
         sd = {k: v.detach() for k, v in hf_model.state_dict().items()}
         self._keep, self._arrays = [], {}
@@ -592,24 +625,30 @@ class HipModernBertEncoder:
                  "ac_modernbert_workspace")
         return need.value
 
-    def _call_cfg(self, arith=None):
-        """ac_modernbert_config of one native call: the architecture + this call's arithmetic (0 = process default, else value + 1)."""
+    def _call_cfg(self, arith=None, pooling=None):
+        """ac_modernbert_config of one native call: the architecture + this call's arithmetic (0 = process default, else value + 1)
+        and pooling (AC_POOL_*, 0 for "cls")."""
         a = arith_mode(arith)
         if a is None:
             a = self.arith
+        pool = pooling_mode(self.pooling if pooling is None else pooling)
         c = self.ccfg
         return nv.ac_modernbert_config(c.hidden, c.layers, c.heads, c.intermediate, c.vocab, c.max_pos, c.global_every,
-                                       c.local_window, c.norm_eps, 0 if a is None else a + 1)
+                                       c.local_window, c.norm_eps, 0 if a is None else a + 1,
+                                       nv.AC_POOL_MEAN if pool == nv.AC_POOL_MEAN else nv.AC_POOL_DEFAULT)
 
     def encode_cls(self, input_ids, token_type_ids=None, attention_mask=None, out=None, verify=True, force_layered=False,
-                   verify_small=None, arith=None):
-        """int64 [b, S] ids (+ optional mask; token types do not exist in ModernBERT) -> unit-norm CLS [b, H].
+                   verify_small=None, arith=None, pooling=None):
+        """int64 [b, S] ids (+ optional mask; token types do not exist in ModernBERT) -> unit-norm embeddings [b, H].
+        pooling: "cls" = F.normalize(final_norm(x)[:, 0, :]); "mean" = classifier_pooling="mean", the attention-masked mean of
+        final_norm(x) over the tokens (the norm per token first, then the mean), L2-normalised; None = this encoder's `pooling`.
+        Under "mean" the last layer runs on every token row.
         arith: this call's GEMM arithmetic ("f32" | "bf16x3" | "f16x2"; None = this encoder's `arith`, else the process default),
         a per-call option inside ac_modernbert_config as for HipBertEncoder; "f16x2" runs as bf16x3 here (no fp16 weight planes
         are built for this family).
         (verify / force_layered: interface parity with HipBertEncoder; this encoder has neither a one-launch path nor
         LayerNorm-fused GEMM epilogues, i.e. no kernel that can give up.)"""
-        ccfg = self._call_cfg(arith)
+        ccfg = self._call_cfg(arith, pooling)
         ids = input_ids.to(device=self.device, dtype=torch.int64).contiguous()
         b, S = ids.shape
         mk = None if attention_mask is None else attention_mask.to(device=self.device, dtype=torch.int64).contiguous()
@@ -647,6 +686,8 @@ class HipModernBertEncoder:
                     nv.ptr(self._ws), self._ws.numel(), nv.stream_ptr(self.device)), "ac_modernbert_encode_cls")
         return out
 
+    encode = encode_cls       # the general name (same function, same docstring)
+
     def flops(self, b, S, executed=True):
         c = self.ccfg
         H, I, L = c.hidden, c.intermediate, c.layers
@@ -656,10 +697,10 @@ class HipModernBertEncoder:
         return 2.0 * b * S * L * (4.0 * H * H + 3.0 * H * I) + attn
 
 
-def make_encoder(hf_model, device=None):
+def make_encoder(hf_model, device=None, pooling="cls"):
     """The native encoder for a transformers model: BERT / DistilBERT -> HipBertEncoder, ModernBERT ->
-    HipModernBertEncoder; anything else raises (there is no eager fallback)."""
+    HipModernBertEncoder; anything else raises (there is no eager fallback).  pooling: the encoder's default ("cls" | "mean")."""
     mtype = getattr(hf_model.config, "model_type", "bert")
     if mtype == "modernbert":
-        return HipModernBertEncoder(hf_model, device=device)
-    return HipBertEncoder(hf_model, device=device)
+        return HipModernBertEncoder(hf_model, device=device, pooling=pooling)
+    return HipBertEncoder(hf_model, device=device, pooling=pooling)

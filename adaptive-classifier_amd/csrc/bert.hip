@@ -10,6 +10,9 @@
 // wave-per-token kernels (embedding gather+LayerNorm, LayerNorm, CLS gather+L2 normalise) and a
 // fused fp32 attention kernel (one wave per (sequence, head, 64-query tile); K/V tiles staged
 // through LDS, online softmax, scores never touch HBM).
+//
+// pool_opt = AC_POOL_MEAN (include/acamd.h): the attention-masked mean of the sentence-embedding checkpoints instead of the CLS
+// row -- the last layer runs on every token row like the layers before it, pool_mean_normalize_kernel reduces the result.
 #include "common.h"
 #include "attention_core.h"
 
@@ -229,6 +232,119 @@ __global__ __launch_bounds__(256) void cls_normalize_kernel(const float* x, int 
     for (int c = lane; c < H; c += 64) s = fmaf(src[c], src[c], s);
     const float nrm = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
     for (int c = lane; c < H; c += 64) out[(int64_t)i * ldo + c] = src[c] / nrm;
+    for (int c = H + lane; c < ldo; c += 64) out[(int64_t)i * ldo + c] = 0.f;
+}
+
+// AC_POOL_MEAN: the attention-masked mean over the token rows of the residual stream -> F.normalize(p=2, dim=1, eps=1e-12)
+//   out[i] = normalize(sum over the admitted tokens t of x[t] / max(count, 1));  columns [H, ldo) zeroed
+// admitted: rows [cu[i], cu[i + 1]) (packed layout), all S rows of sequence i (padded, mask == nullptr), the rows with
+// mask[i, t] != 0 (padded with a mask: holes and left padding too).  A sequence without any gives an exactly zero row.
+// One 256-thread workgroup per sequence: wave w sums the tokens w, w + 4, ... in position order (16-byte row loads, kMaxVec
+// vectors per lane), the four partial sums are added in the order 0, 1, 2, 3 through LDS, wave 0 divides, takes the norm and
+// writes -- an order fixed by the shape alone: the same call twice gives the same bits.
+// NORM (ModernBERT): every admitted row goes through the final LayerNorm first, the expressions of layernorm_store on the row
+// already in registers -- the mean of the normed rows, not the norm of the mean.
+// Dynamic LDS: 3 * H floats (the partial sums of waves 1 .. 3).
+template <bool NORM>
+__global__ __launch_bounds__(256) void pool_mean_normalize_kernel(const float* __restrict__ x, const int64_t* __restrict__ mask,
+                                                                  const int32_t* __restrict__ cu, int S, int H,
+                                                                  const float* __restrict__ g, const float* __restrict__ be, float eps,
+                                                                  float* __restrict__ out, int64_t ldo) {
+    extern __shared__ __attribute__((aligned(16))) float pool_part[];
+    __shared__ int pool_count[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, i = blockIdx.x;
+    const int nv = H >> 2;
+    const int64_t row0 = cu ? (int64_t)cu[i] : (int64_t)i * S;
+    const int n = cu ? cu[i + 1] - cu[i] : S;
+    const int64_t* mk = (!cu && mask) ? mask + (int64_t)i * S : nullptr;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc[kMaxVec];
+#pragma unroll
+    for (int e = 0; e < kMaxVec; ++e) acc[e] = zero4;
+    int count = 0;
+    for (int t = wv; t < n; t += 4) {
+        if (mk && mk[t] == 0) continue;                              // (wave-uniform)
+        const float* src = x + (row0 + t) * (int64_t)H;
+        f32x4 r[kMaxVec];
+#pragma unroll
+        for (int e = 0; e < kMaxVec; ++e) {
+            const int c4 = lane + 64 * e;
+            r[e] = c4 < nv ? *reinterpret_cast<const f32x4*>(src + 4 * c4) : zero4;
+        }
+        if constexpr (NORM) {
+            float s = 0.f;
+#pragma unroll
+            for (int e = 0; e < kMaxVec; ++e)
+                if (lane + 64 * e < nv) s += (r[e].x + r[e].y) + (r[e].z + r[e].w);
+            const float mean = wave_sum(s) / (float)H;
+            float q = 0.f;
+#pragma unroll
+            for (int e = 0; e < kMaxVec; ++e)
+                if (lane + 64 * e < nv) {
+                    const float d0 = r[e].x - mean, d1 = r[e].y - mean, d2 = r[e].z - mean, d3 = r[e].w - mean;
+                    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+                }
+            const float var = wave_sum(q) / (float)H;
+            const float rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+            for (int e = 0; e < kMaxVec; ++e) {
+                const int c4 = lane + 64 * e;
+                if (c4 < nv) {
+                    const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * c4);
+                    const f32x4 bb = *reinterpret_cast<const f32x4*>(be + 4 * c4);
+                    f32x4 y;
+                    y.x = (r[e].x - mean) * rstd * gg.x + bb.x;
+                    y.y = (r[e].y - mean) * rstd * gg.y + bb.y;
+                    y.z = (r[e].z - mean) * rstd * gg.z + bb.z;
+                    y.w = (r[e].w - mean) * rstd * gg.w + bb.w;
+                    r[e] = y;
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < kMaxVec; ++e) { acc[e].x += r[e].x; acc[e].y += r[e].y; acc[e].z += r[e].z; acc[e].w += r[e].w; }
+        ++count;
+    }
+    if (wv > 0) {
+#pragma unroll
+        for (int e = 0; e < kMaxVec; ++e) {
+            const int c4 = lane + 64 * e;
+            if (c4 < nv) *reinterpret_cast<f32x4*>(pool_part + (size_t)(wv - 1) * H + 4 * c4) = acc[e];
+        }
+        if (lane == 0) pool_count[wv] = count;
+    }
+    __syncthreads();
+    if (wv > 0) return;
+    for (int w = 1; w < 4; ++w) {                                    // the partial sums in the order 0, 1, 2, 3
+#pragma unroll
+        for (int e = 0; e < kMaxVec; ++e) {
+            const int c4 = lane + 64 * e;
+            if (c4 < nv) {
+                const f32x4 p = *reinterpret_cast<const f32x4*>(pool_part + (size_t)(w - 1) * H + 4 * c4);
+                acc[e].x += p.x; acc[e].y += p.y; acc[e].z += p.z; acc[e].w += p.w;
+            }
+        }
+        count += pool_count[w];
+    }
+    const float den = (float)(count > 1 ? count : 1);
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < kMaxVec; ++e)
+        if (lane + 64 * e < nv) {
+            f32x4 y = acc[e];
+            y.x = y.x / den; y.y = y.y / den; y.z = y.z / den; y.w = y.w / den;
+            acc[e] = y;
+            ss = fmaf(y.x, y.x, ss); ss = fmaf(y.y, y.y, ss); ss = fmaf(y.z, y.z, ss); ss = fmaf(y.w, y.w, ss);
+        }
+    const float nrm = fmaxf(sqrtf(wave_sum(ss)), 1e-12f);
+#pragma unroll
+    for (int e = 0; e < kMaxVec; ++e) {
+        const int c4 = lane + 64 * e;
+        if (c4 < nv) {
+            float* dst = out + (int64_t)i * ldo + 4 * c4;
+            dst[0] = acc[e].x / nrm; dst[1] = acc[e].y / nrm; dst[2] = acc[e].z / nrm; dst[3] = acc[e].w / nrm;   // (ldo need not be a multiple of 4)
+        }
+    }
     for (int c = H + lane; c < ldo; c += 64) out[(int64_t)i * ldo + c] = 0.f;
 }
 
@@ -645,6 +761,8 @@ int check_cfg(const ac_bert_config* c) {
                    c->one_launch_opt >= 0 && c->one_launch_opt <= 2, AC_EINVAL,
                "bert: per-call options out of range (gemm_arith_opt %d, ln_fusion_opt %d, one_launch_opt %d)", c->gemm_arith_opt,
                c->ln_fusion_opt, c->one_launch_opt);
+    AC_REQUIRE(c->pool_opt >= AC_POOL_DEFAULT && c->pool_opt <= AC_POOL_MEAN, AC_EINVAL,
+               "bert: pool_opt %d out of range (0 = default = AC_POOL_CLS, AC_POOL_CLS, AC_POOL_MEAN)", c->pool_opt);
     return AC_OK;
 }
 
@@ -667,6 +785,9 @@ static bool tail_fused() {
     const char* e = getenv("AC_BERT_TAIL_FUSED");
     return !(e && atoi(e) == 0);
 }
+// AC_POOL_MEAN: the last layer is a token layer like the others (every row feeds the mean); else it runs on the b CLS rows
+inline bool pools_mean(int pool_opt) { return pool_opt == AC_POOL_MEAN; }
+inline int token_layers(const ac_bert_config& c) { return pools_mean(c.pool_opt) ? c.layers : c.layers - 1; }
 // What of a forward is decided by the token-row count alone: operand planes between the GEMMs, fp16x2 planes
 struct EncodePlan { bool wplanes, pl, f16; };
 EncodePlan encode_plan(const ac_bert_config& c, const ac_bert_weights* w, int T) {
@@ -674,7 +795,7 @@ EncodePlan encode_plan(const ac_bert_config& c, const ac_bert_weights* w, int T)
     EncodePlan p;
     p.wplanes = w->qkv_w3 && w->ao_w3 && w->ff1_w3 && w->ff2_w3;
     p.pl = p.wplanes && ac::linear_takes_planes(T, H, H) && ac::linear_takes_planes(T, H, I) && (H % 8) == 0;
-    p.f16 = p.pl && ac::gemm_arith() == AC_GEMM_F16X2 && w->qkv_wh && w->ao_wh && w->ff1_wh && w->ff2_wh && c.layers > 1 &&
+    p.f16 = p.pl && ac::gemm_arith() == AC_GEMM_F16X2 && w->qkv_wh && w->ao_wh && w->ff1_wh && w->ff2_wh && token_layers(c) > 0 &&
             ac::linear_f16x2_takes(T, 3 * H, H) && ac::linear_f16x2_takes(T, H, H) && ac::linear_f16x2_takes(T, I, H) &&
             ac::linear_f16x2_takes(T, H, I);
     return p;
@@ -722,7 +843,8 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
     // AC_GEMM_F16X2 (opt-in): the same flow on fp16x2 planes when the fp16 weight planes are there and all four token-row GEMMs
     // take the ring-staged kernel; the CLS-only tail of the last layer (fp32 activations, b rows) stays bf16x3
     const bool f16 = pn.f16;
-    const bool fuse_ln = pl && c.layers > 1 && ac::pipe_ln_applies(T, H, H) && ac::pipe_ln_applies(T, H, I);
+    const bool pool = pools_mean(c.pool_opt);
+    const bool fuse_ln = pl && token_layers(c) > 0 && ac::pipe_ln_applies(T, H, H) && ac::pipe_ln_applies(T, H, I);
     unsigned* ln_abort = (unsigned*)base;
     if (!(pre & kPreCtl)) {
         hipLaunchKernelGGL(ln_verdict_roll_kernel, dim3(1), dim3(1), 0, stream, ln_abort);
@@ -741,7 +863,7 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
     // Self-attention inside the QKV GEMM's epilogue (gemm_pipe.hip EPI_QKV_ATTN): sequences laid out row after row (packed, or
     // unpacked without a mask = every sequence S real tokens), head dim 64, longest sequence <= 64, layers 0 .. L-2 on planes
     const int32_t* cu_at = cu;
-    const bool fuse_attn = pl && c.layers > 1 && dh == 64 && (cu || !d_mask) && ac::qkv_attn_applies(T, H, c.heads, Smax);
+    const bool fuse_attn = pl && token_layers(c) > 0 && dh == 64 && (cu || !d_mask) && ac::qkv_attn_applies(T, H, c.heads, Smax);
     if (fuse_attn && !cu) {
         int32_t* cuw = (int32_t*)(base + ws.cu);
         hipLaunchKernelGGL(iota_cu_kernel, dim3((b + 256) / 256), dim3(256), 0, stream, cuw, b, S);
@@ -765,9 +887,10 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
         const uint16_t* ao_w3 = wplanes ? w->ao_w3[l] : nullptr;
         const uint16_t* ff1_w3 = wplanes ? w->ff1_w3[l] : nullptr;
         const uint16_t* ff2_w3 = wplanes ? w->ff2_w3[l] : nullptr;
-        const bool last = (l == c.layers - 1);
+        const bool last = (l == c.layers - 1) && !pool;
         // After the last layer's attention only the CLS row of each sequence is consumed, so the
-        // output projection, both LayerNorms and the FFN run on b rows instead of b*S.
+        // output projection, both LayerNorms and the FFN run on b rows instead of b*S (AC_POOL_MEAN consumes every row: no
+        // layer is `last`, the loop ends with T rows in x).
         const int Ml = last ? b : T;
         const bool lp = pl && !last;                   // this layer's post-attention GEMMs run on planes
         const float* resid = x;                        // residual = layer input
@@ -889,6 +1012,12 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
         launch_ln(f16, lblocks, stream, y, Ml, H, w->ln2_g[l], w->ln2_b[l], c.ln_eps, x, lp ? xp : nullptr, (int64_t)H);
         AC_LAUNCH_CHECK();
     }
+    if (pool) {                                        // x holds the T token rows of the last layer's output
+        hipLaunchKernelGGL(pool_mean_normalize_kernel<false>, dim3(b), dim3(256), 3 * (size_t)H * sizeof(float), stream, x, d_mask, cu, S, H,
+                           (const float*)nullptr, (const float*)nullptr, 0.f, d_out, ldo);
+        AC_LAUNCH_CHECK();
+        return AC_OK;
+    }
     // after the CLS-only last layer x holds b compact rows (sequence stride 1)
     hipLaunchKernelGGL(cls_normalize_kernel, dim3((b + 3) / 4), dim3(256), 0, stream, x, b, 1, H, d_out, ldo);
     AC_LAUNCH_CHECK();
@@ -908,7 +1037,9 @@ extern "C" int ac_bert_encode_cls_opts(const ac_bert_config* cfg, const ac_bert_
     const ac::CallScope scope(cfg->gemm_arith_opt, cfg->ln_fusion_opt, cfg->one_launch_opt);
     AC_REQUIRE(w && d_ids && d_out && b > 0 && S >= 1 && S <= cfg->max_pos && ldo >= cfg->hidden, AC_EINVAL,
                "bert_encode_cls: bad arguments (b=%d S=%d max_pos=%d)", b, S, cfg->max_pos);
-    if (b * S <= 32 && !(opts & AC_BERT_LAYERED)) {   // a handful of token rows (single-query predict): every layer in ONE persistent launch
+    // a handful of token rows (single-query predict): every layer in ONE persistent launch (which ends in the CLS row: a
+    // mean-pooled call of this size goes layer by layer)
+    if (b * S <= 32 && !(opts & AC_BERT_LAYERED) && !pools_mean(cfg->pool_opt)) {
         const BertWs ws = bert_ws(*cfg, b, S);
         AC_REQUIRE(d_ws && ws_bytes >= ws.total, AC_EWORKSPACE, "bert_encode_cls: workspace %zu < %zu", ws_bytes, ws.total);
         rc = ac::bert_small_encode(*cfg, *w, d_ids, d_type_ids, d_mask, b, S, d_out, ldo, (char*)d_ws + ws.small, (hipStream_t)stream_);
@@ -1107,6 +1238,8 @@ int check_mb(const ac_modernbert_config* c) {
     AC_REQUIRE(c->hidden == c->heads * DH, AC_EUNSUPPORTED, "modernbert: head dim %d unsupported (only %d)",
                c->hidden / c->heads, DH);
     AC_REQUIRE(c->gemm_arith_opt >= 0 && c->gemm_arith_opt <= 3, AC_EINVAL, "modernbert: gemm_arith_opt %d out of range", c->gemm_arith_opt);
+    AC_REQUIRE(c->pool_opt >= AC_POOL_DEFAULT && c->pool_opt <= AC_POOL_MEAN, AC_EINVAL,
+               "modernbert: pool_opt %d out of range (0 = default = AC_POOL_CLS, AC_POOL_CLS, AC_POOL_MEAN)", c->pool_opt);
     return AC_OK;
 }
 
@@ -1159,6 +1292,7 @@ int modernbert_encode_impl(const ac_modernbert_config* cfg, const ac_modernbert_
                        w->emb_norm_b ? w->emb_norm_b : zb, c.norm_eps, x, pl ? xnp : nullptr, tok_src);
     AC_LAUNCH_CHECK();
     const float scale = 1.0f / sqrtf((float)DH);
+    const bool pool = pools_mean(c.pool_opt);
     for (int l = 0; l < c.layers; ++l) {
         const float* a_in = x;             // attention input rows (fp32) -- x itself for layer 0
         if (l > 0) {
@@ -1175,9 +1309,10 @@ int modernbert_encode_impl(const ac_modernbert_config* cfg, const ac_modernbert_
         const float* rc_ = global ? w->rope_cos_global : w->rope_cos_local;
         const float* rs_ = global ? w->rope_sin_global : w->rope_sin_local;
         const int win = global ? -1 : c.local_window;
-        const bool last = (l == c.layers - 1);
+        const bool last = (l == c.layers - 1) && !pool;
         // After the last layer's attention only the CLS row of each sequence is consumed (classifier.py:1272):
-        // the CLS-query attention, the output projection, the MLP and the final norm run on b rows, not b*S.
+        // the CLS-query attention, the output projection, the MLP and the final norm run on b rows, not b*S
+        // (AC_POOL_MEAN consumes every row: no layer is `last`).
         const int Ml = last ? b : T;
         const bool lp = last ? (wplanes && ac::linear_takes_planes(b, H, H) && ac::linear_takes_planes(b, H, I) && (H % 8) == 0) : pl;
         const float* resid = x;
@@ -1221,6 +1356,12 @@ int modernbert_encode_impl(const ac_modernbert_config* cfg, const ac_modernbert_
         rc = ac::linear_f32(g, I, w->wo2[l], I, opt(w->wo2_b, l), y, H, x, H, Ml, H, I, 0, nullptr, 1.f, stream, 0.f, 0,
                             wplanes ? w->wo23[l] : nullptr, lp ? gp : nullptr);
         if (rc) return rc;
+    }
+    if (pool) {                            // x holds T token rows: final LayerNorm per admitted token, masked mean, L2-normalise
+        hipLaunchKernelGGL(pool_mean_normalize_kernel<true>, dim3(b), dim3(256), 3 * (size_t)H * sizeof(float), stream, x, d_mask, cu, S, H,
+                           w->final_norm_g, w->final_norm_b ? w->final_norm_b : zb, c.norm_eps, d_out, ldo);
+        AC_LAUNCH_CHECK();
+        return AC_OK;
     }
     // after the CLS-only last layer x holds b compact rows: final LayerNorm, then L2-normalise
     hipLaunchKernelGGL(ln_kernel_t<false>, dim3((b + 3) / 4), dim3(256), 0, stream, x, b, H, w->final_norm_g,

@@ -882,7 +882,23 @@ typedef struct {
     int ln_fusion_opt;    /* 1 = LayerNorms as separate launches, 2 = fused into the GEMM epilogues where the launch allows it
                            * (3 = fused with a starved exchange: tests of the give-up path only) */
     int one_launch_opt;   /* 1 = never the one persistent launch for <= 32 token rows (like AC_BERT_LAYERED), 2 = allowed */
+    /* What every ac_bert_encode_cls* entry writes per sequence (ac_version() >= 9; a per-call option like the three above):
+     *   0 / AC_POOL_CLS   the CLS row, F.normalize(last_hidden_state[:, 0, :]) -- the reference's embedding, the default.  The last
+     *                     layer runs on the b CLS rows only.
+     *   AC_POOL_MEAN      the attention-masked mean of the sentence-embedding checkpoints (MiniLM family, e5, ModernBERT with
+     *                     classifier_pooling="mean"): F.normalize(sum over the admitted tokens of last_hidden_state / max(count, 1)).
+     *                     Admitted = the rows [cu[i], cu[i + 1]) of a packed call, all S rows without a mask, the rows whose
+     *                     d_mask[i, t] != 0 with one (holes and left padding included); a sequence without any gives an exactly
+     *                     zero row.  The last layer is an ordinary token layer -- the kernels layers 0 .. L-2 run at that row count
+     *                     (planes, fused LayerNorm, fused attention, the exchange) -- and pool_mean_normalize_kernel reduces the
+     *                     fp32 residual stream in a fixed order (bit-equal from call to call).  The one persistent launch of
+     *                     <= 32 token rows has no pooled form: such a call runs layer by layer, used_one_launch = 0.
+     * Anything else: AC_EINVAL.  The workspace is the same size under every value. */
+    int pool_opt;
 } ac_bert_config;
+#define AC_POOL_DEFAULT 0
+#define AC_POOL_CLS     1
+#define AC_POOL_MEAN    2
 
 /* Device pointers to the weights, nn.Linear [out,in] layout, fp32.
  * Per-layer arrays have `layers` entries (host arrays of device pointers). */
@@ -1001,7 +1017,9 @@ int ac_bert_encode_cls(const ac_bert_config* cfg, const ac_bert_weights* w,
 /* ac_bert_encode_cls with per-call options and a report of the path taken.
  *   opts & AC_BERT_LAYERED   never take the one-launch path of bert_small.hip (<= 32 token rows), whatever
  *                            ac_set_persistent_kernels says: the layer-by-layer kernels run.
- *   used_one_launch          (nullable, host) 1 if this call ran as the one persistent launch.
+ *   used_one_launch          (nullable, host) 1 if this call ran as the one persistent launch.  Never under
+ *                            pool_opt = AC_POOL_MEAN: the one-launch kernel ends in the CLS row and has no pooled form, a
+ *                            mean-pooled call of <= 32 token rows runs layer by layer.
  * The one-launch kernel is launched without the cooperative-launch residency check (it saves ~30 us per single query);
  * if the device is shared with another compute process one of its grid barriers can give up after a bounded spin, in
  * which case the output rows are NaN.  ac_bert_one_launch_status reads that verdict for the LAST one-launch call that
@@ -1090,6 +1108,8 @@ typedef struct {
     float norm_eps;       /* 1e-5 */
     int gemm_arith_opt;   /* per-call GEMM arithmetic as in ac_bert_config: 0 = process default, else AC_GEMM_* + 1 (AC_GEMM_F16X2
                            * runs as bf16x3 here: this encoder builds no fp16 weight planes) */
+    int pool_opt;         /* AC_POOL_* as in ac_bert_config (ac_version() >= 9).  AC_POOL_MEAN pools final_norm(x) per token -- the norm
+                           * first, then the masked mean (classifier_pooling="mean") -- and the last layer runs on every token row */
 } ac_modernbert_config;
 
 typedef struct {

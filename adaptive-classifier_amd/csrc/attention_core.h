@@ -48,7 +48,7 @@ __device__ __forceinline__ void rope_rotate(f32x4 (&x)[8], const float* cs, cons
 // window >= 0 (sliding-window layers, masking_utils.py:141-151): key k is visible to query q iff |q - k| <= window.
 // FP32_OUT = false: the caller always passes ctx_planes (the fp32-row store path is not compiled: in a kernel whose operands sit
 // in LDS its generic destination pointer would become flat stores).
-template <bool ROPE, int DHT, bool FP32_OUT = true>
+template <bool ROPE, int DHT, bool FP32_OUT = true, bool K_AHEAD = true>
 __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_, const float* vb, int64_t ld, int S, int qt, int lane,
                                                float scale, const int64_t* mask_row, const float* rope_cos, const float* rope_sin,
                                                int window, float* ctx_rows, int H, uint16_t* ctx_planes, int64_t rows, int64_t row0,
@@ -77,7 +77,11 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
     float m = -INFINITY, l = 0.f;
 
     // K fragment of a tile (keys past S are clamped; they are masked below).  The next tile's fragment is
-    // requested right after the QK^T MFMAs have consumed this one, so its latency hides under softmax + PV.
+    // requested right after the QK^T MFMAs have consumed this one, so its latency hides under softmax + PV; after the
+    // last tile nothing is requested.  K_AHEAD = false (operands in LDS, the GEMM epilogue): each tile's fragment is read at the
+    // top of its own iteration instead -- 32 registers less across softmax + PV in a kernel that sits at its register limit (any
+    // branch in here made hipcc spill there), the same loads in front of the same MFMAs for the single-tile sequences (<= 32
+    // tokens) that route mostly serves, and no read for a tile that does not exist.  Loads only: the arithmetic is the same.
     f32x4 Kf[NKB];
     auto load_k = [&](int k0) {
         int kr = k0 + j; if (kr > S - 1) kr = S - 1;
@@ -93,13 +97,17 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
         const int last = qt * 32 + 31 + window;
         if (last + 1 < kend) kend = last + 1;
     }
-    load_k(kbeg);
+    if constexpr (K_AHEAD) load_k(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += 32) {
+        if constexpr (!K_AHEAD) load_k(k0);
         // key validity as a 32-bit mask shared by the wave
         const int kj = k0 + j;
         const bool kv = kj < S && (!mask_row || mask_row[kj] != 0);
         const unsigned vmask = (unsigned)(__ballot(kv && h == 0) & 0xffffffffull);
-        if (vmask == 0u) { load_k(k0 + 32); continue; }              // wave-uniform
+        if (vmask == 0u) {                                           // wave-uniform
+            if constexpr (K_AHEAD) if (k0 + 32 < kend) load_k(k0 + 32);
+            continue;
+        }
         f32x16 st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = 0.f;
@@ -108,7 +116,7 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4)
                 st = __builtin_amdgcn_mfma_f32_32x32x2f32(Kf[kb][s4], Qf[kb][s4], st, 0, 0, 0);
-        load_k(k0 + 32);                                             // clamped past the end: harmless re-read
+        if constexpr (K_AHEAD) if (k0 + 32 < kend) load_k(k0 + 32);  // (wave-uniform; there is no tile at or past kend to fetch for)
         // online softmax for query `j` (this lane + partner lane hold its 32 keys)
         float cmax = -INFINITY;
 #pragma unroll
@@ -135,13 +143,47 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
         m = m_new;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { o0[r] *= corr; o1[r] *= corr; }
-        // O^T += V^T P^T
+        // O^T += V^T P^T -- the LIVE steps only.  MFMA step r multiplies keys crow32(r, 0) and crow32(r, 1) = crow32(r, 0) + 4 of the
+        // tile.  A key past S, masked out, or (window) outside [qt 32 - window, qt 32 + 31 + window] -- visible to none of the tile's
+        // queries -- has p == +0 exactly in EVERY lane (its score was set to -inf above, and 2^-inf = +0; `none` lanes hold +0 as
+        // well), so a step whose two keys are both such adds v * 0 + v' * 0 to each accumulator.  For finite V that is +-0, and
+        // x + (+-0) == x bit for bit for every x but -0 (where -0 + +0 = +0).  The accumulators are never -0 at this point short of
+        // an fp32 underflow: they start +0, a round-to-nearest sum is -0 only when every term is, o * corr keeps +0 (corr >= 0),
+        // and a non-zero o turns into -0 only when corr underflows to 0, i.e. when this tile's maximum exceeds the running one by
+        // more than ~87 (e^-87 < 2^-126) -- and then the tile's maximum key itself, p = 1 in a live step, lands on that element.
+        // So the live steps run in the order and with the rounding they had, and the dead ones (about a third of them at lengths of
+        // 8 .. 32, each 2 x 64 matrix-pipe cycles on the fp32 MFMA) are left out together with their V loads.  The decision is
+        // wave-uniform: vmask is a ballot, qt / k0 / window are scalars.  (One visible difference, in the safe direction: a
+        // non-finite V row of a key nobody may see no longer reaches the output through 0 * inf.)
+        // The V loads of a batch of PVC steps are issued before the batch's first MFMA: a step's branch would otherwise put each
+        // load's latency in front of its own MFMA, where the unconditional form had a dozen loads in flight.
+        unsigned live = vmask;
+        if (window >= 0) {
+            const int lo = qt * 32 - window - k0, hi = qt * 32 + 31 + window - k0;       // visible to some query: tile keys lo .. hi
+            if (lo > 0) live &= lo < 32 ? 0xffffffffu << lo : 0u;
+            if (hi < 31) live &= hi >= 0 ? 0xffffffffu >> (31 - hi) : 0u;
+        }
+        live = (unsigned)__builtin_amdgcn_readfirstlane((int)(live | (live >> 4)));        // bit crow32(r, 0): step r has a live key
+        constexpr int PVC = 8;                                       // steps per batch of V loads (registers: 2 PVC values in flight)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            int vr = k0 + crow32(r, h); if (vr > S - 1) vr = S - 1;
-            const float* vp = vb + (int64_t)vr * ld + j;
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[0], p[r], o0, 0, 0, 0);
-            if constexpr (DHT == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vp[32], p[r], o1, 0, 0, 0);
+        for (int rb = 0; rb < 16; rb += PVC) {
+            float v0[PVC], v1[PVC];
+#pragma unroll
+            for (int u = 0; u < PVC; ++u) {
+                const int r = rb + u;
+                if (!((live >> crow32(r, 0)) & 1u)) continue;
+                int vr = k0 + crow32(r, h); if (vr > S - 1) vr = S - 1;
+                const float* vp = vb + (int64_t)vr * ld + j;
+                v0[u] = vp[0];
+                if constexpr (DHT == 64) v1[u] = vp[32];
+            }
+#pragma unroll
+            for (int u = 0; u < PVC; ++u) {
+                const int r = rb + u;
+                if (!((live >> crow32(r, 0)) & 1u)) continue;
+                o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0[u], p[r], o0, 0, 0, 0);
+                if constexpr (DHT == 64) o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1[u], p[r], o1, 0, 0, 0);
+            }
         }
     }
     if (qvalid) {

@@ -369,7 +369,7 @@ __device__ __forceinline__ void qkv_attention_epilogue(f32x16 (&acc)[TM][TN], co
                 const float* qb = T + (r0 - seq_lo) * kAtLd;
                 const int S = r1 - r0;
                 for (int qt = 0; qt * 32 < S; ++qt)
-                    acattn::attention_tile<false, 64, false>(qb, qb + 64, qb + 128, kAtLd, S, qt, lane, at.scale, nullptr, nullptr, nullptr, -1,
+                    acattn::attention_tile<false, 64, false, false>(qb, qb + 64, qb + 128, kAtLd, S, qt, lane, at.scale, nullptr, nullptr, nullptr, -1,
                                                              nullptr, H, at.ctx_planes, prm.M, r0, head * 64, AR == 2);
             } else {
                 spill_rows(r0, tile_end, lo_r);                         // it continues in the next tile: the boundary launch serves it
@@ -517,7 +517,34 @@ __global__ __launch_bounds__(64 * WMW * WNW, (PipeGeom<TM, TN, WMW, WNW, NS, AR>
     __builtin_amdgcn_sched_barrier(0);
     stamp<(EPI == EPI_QKV_ATTN ? 16 : 4)>(prm, wave, 1);
 
-    if constexpr (PIPE != 0) {
+    // A wave whose rows all lie at or past M (the ragged last row tile: at 5141 rows six of the eight waves of a 256-row tile) has
+    // nothing to multiply: its DMA rows are clamped to row M - 1, so its MFMAs would run on real data at full power for accumulators
+    // that no store ever reads.  It keeps its place in the ring protocol -- the same PPW DMA instructions per stage (the other waves'
+    // operands), the same counted waits, every barrier -- and leaves out the fragment reads and the MFMAs; its accumulators stay
+    // zero, so the epilogues see finite values (bias [+ residual of the clamped row]) in the rows their stores mask.  Wave-uniform
+    // (wm comes from readfirstlane); the live loops below are the code they were.
+    const bool dead_wave = m0 + 32 * TM * wm >= prm.M;
+    if (__builtin_expect(dead_wave, 0)) {
+        if constexpr (PIPE != 0) {
+            for (int s = 0; s < nk; ++s) {
+                wait_vm<(NS - 3) * PPW>();
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                issue();
+            }
+        } else {
+            for (int s = 0; s < nk; ++s) {
+                if (s > 0) {
+                    wait_vm<(NS - 2) * PPW>();
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                issue();
+            }
+        }
+    } else if constexpr (PIPE != 0) {
         Frags F0, F1;
         read_frags(F0, 0);
         int slot = 1 % NS;                                              // ring slot of stage s + 1

@@ -6,32 +6,41 @@ Protocol kept (reference call sites in /root/reference/src/adaptive_classifier/m
 
 Rows live in one resident, row-major fp32 device matrix with a 16-byte aligned, zero padded
 leading dimension (growth by doubling, so `add` is amortised O(1) like faiss's vector).
-search() is one call into the C ABI (`ac_knn_l2_topk`): exact squared L2, ascending, ties to
-the lower id.  HipFlatIPIndex is the same store searched by inner product (`ac_knn_ip_topk`,
-faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.
-Both metrics search a prepared store (one fp16 plane, `prepare_store`) through `ac_knn_l2_topk_batch` /
-`ac_knn_ip_topk_batch`.  range_search() (faiss range_search: every row within a radius) is `ac_knn_*_range_count` / `_fill` over
-the fp32 rows; an index that already holds a plane counts over it (`ac_knn_*_range_count_batch`), with the same bits.
-search(x, k, sel=...) is the FILTERED search (faiss SearchParameters(sel=IDSelector...)): the k best among the rows a `RowSelector` names, through `ac_knn_*_topk_ids` (a short id list), `ac_knn_*_topk_batch_sel` (bitmap over the prepared
-store: a selection known to hold >= 1 / SEL_BATCH_MAX_SPARSITY of the rows) or `ac_knn_*_topk_sel` (bitmap over the fp32 rows).
-range_search(x, r, sel=...) is the FILTERED range search (faiss range_search with SearchParameters(sel=...)): the hits among the
-selected rows, through `ac_knn_*_range_count_ids` / `_fill_ids` (a short id list) or `ac_knn_*_range_count_sel` + the unfiltered
-fill (bitmap over the fp32 rows, or `ac_knn_*_range_count_batch_sel` over a plane the index already holds).
+search() is exact squared L2, ascending, ties to the lower id; HipFlatIPIndex is the same store searched by inner product
+(faiss.IndexFlatIP: descending, ties to the lower id); the reference itself never builds one.  search(x, k, sel=...) is the FILTERED
+search (faiss SearchParameters(sel=IDSelector...)): the k best among the rows a `RowSelector` names; range_search() is faiss
+range_search (every row within a radius), filtered by `sel=` likewise.  Both metrics share one prepared store (one fp16 plane +
+norms, `prepare_store`).  Every search is one of three routes, chosen by `plan_topk` / `plan_range` (below) from what the host
+knows -- no bitmap is ever read back to choose:
+
+  route  | taken by                                            | top-k entry (`ac_knn_{l2,ip}_`)  | range entries (count; fill)
+  -------+-----------------------------------------------------+----------------------------------+------------------------------------
+  ids    | a selector carrying <= KNN_IDS_MAX host ids         | topk_ids                         | range_count_ids; range_fill_ids
+  plane  | `batch_applies(auto=True)` (a selection: KNOWN to   | topk_batch, topk_batch_sel       | range_count_batch[_sel]; range_fill
+         | hold >= 1 / SEL_BATCH_MAX_SPARSITY of the rows)     |                                  |   (a plane that exists, from
+         | and a plane exists or may be prepared now           |                                  |   PLANE_MIN_ROWS rows on)
+  rows   | everything else, an unknown count included          | topk_x, topk_sel                 | range_count[_sel]; range_fill
+
+Who prepares a plane that does not exist (from BATCH_MIN_QUERIES queries on: every top-k search that takes the plane route):
+  HipFlatL2Index.search, unfiltered       | small batches too, once the rows have served one search since they last changed
+  HipFlatIPIndex.search; any search(sel=) | never from small batches: they only use a plane that exists
+  ShardedSearch, unfiltered               | always (sized for the shard's rows; the indexes size it for the store's capacity)
+  any range search; the functional API    | never (`knn_*_topk(prepared=)` / `knn_range_search(prepared=)` use the CALLER's plane
+                                          | wherever the library takes it, and fall back to the fp32 entry elsewhere)
 """
 import ctypes
 
 import numpy as np
 import torch
 
+from collections import namedtuple
+
 from . import _native as nv
 
-
-def knn_workspace_bytes(N, D, nq, k):
-    b = ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_l2_topk_workspace(N, D, nq, k, ctypes.byref(b)), "ac_knn_l2_topk_workspace")
-    return b.value
-
-
+# ---- the route planner: pure host code (integers in, a decision out; no tensor, no native call) -----------------------------------
+# Every caller -- the flat indexes, the row-sharded search, the functional wrappers -- states the facts and keeps only what is its
+# own: who owns the plane, the workspace, the stats tensor, the row offset.  The constants are read when a route is planned.
+#
 # Where the prepared-store paths apply (library limits: N >= 65536, k <= 100) and pay.
 #   >= 64 queries: the GEMM-form proposal sweep (knn_batch_sweep); its fixed cost (sample stages, thresholds, query plane, a deeper
 #      merge: ~0.3 ms) beats the fp32 sweep from ~20 M query-row pairs on (measured, round 3, fp32 sweep vs batched: 256 x 100k 0.56
@@ -40,20 +49,105 @@ def knn_workspace_bytes(N, D, nq, k):
 #      the bytes of the fp32 sweep; pays once the sweep, not the launch chain, is what a search costs (PLANE_MIN_ROWS)
 BATCH_MIN_QUERIES, BATCH_MIN_ROWS, BATCH_MAX_K, BATCH_MIN_PAIRS = 64, 65536, 100, 2.0e7
 PLANE_MIN_ROWS = 1 << 18
+KNN_IDS_MAX = 8192       # rows the id-list route covers (include/acamd.h: ac_knn_*_topk_ids)
+# The filtered search takes the prepared store only for a selection KNOWN to hold at least 1 / 32 of the rows: the thresholds of
+# the prepared-store sweeps come from selected rows only -- stage A samples >= 128 k' rows, a two-phase round sees 256 tiles of 256
+# rows -- and at density 1 / 32 both still see >= 4 k' selected rows, the planner's own margin.  Sparser, the thresholds may stay
+# +inf; a store with more selected rows than the candidate buffer holds then overflows it and every query is redone in fp64 (exact,
+# but slower than the fp32 route).  Measured at 256 x 1M x 768 (profiles/knn_select/README.md): no query takes the fallback at
+# 1/32 -- nor at 1 %, where the 10 159 selected rows still fit the buffer; the fraction stays at the planner's margin.
+SEL_BATCH_MAX_SPARSITY = 32
+
+# When a top-k search that would take the plane, has fewer than BATCH_MIN_QUERIES queries and finds no plane may prepare one (two
+# passes over the rows, 2 B per element; from BATCH_MIN_QUERIES queries on preparing pays within the call: every policy prepares):
+PREPARE_SECOND_SEARCH = "second search"            # once the rows have served a search since they last changed (L2 index, unfiltered)
+PREPARE_NEVER_SMALL = "never from small batches"   # small batches only use a plane that exists (IP index; every filtered search)
+PREPARE_ALWAYS = "always"                          # wherever batch_applies(auto=True) holds (the unfiltered sharded search)
+
+# What the host knows of a row selection: ids = the length of its host id list (None: it has none), count = its known number of
+# selected rows (None: unknown -- it is never read back to choose a route), total = the rows it covers (None: the searched rows; a
+# row shard passes the GLOBAL count over the GLOBAL rows).
+Selection = namedtuple("Selection", "ids count total")
+# kind: "ids" (the id-list entries), "plane" (the prepared-store entries) or "rows" (the fp32 rows); prepare: build the plane first
+Route = namedtuple("Route", "kind prepare")
 
 
-def store_buffers(rows, D, device):
-    """Empty (plane int16, norms fp32) buffers of a prepared store of up to `rows` rows (`ac_knn_store_bytes`)."""
-    pb, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_store_bytes(rows, D, ctypes.byref(pb), ctypes.byref(nb)), "ac_knn_store_bytes")
-    return (torch.empty(pb.value // 2, dtype=torch.int16, device=device), torch.empty(nb.value // 4, dtype=torch.float32, device=device))
+def batch_applies(N, nq, k, auto=False):
+    """Library limits of ac_knn_l2_topk_batch / ac_knn_ip_topk_batch (any number of queries: below 64 they run the fp16-plane
+    sweep); auto=True adds the size heuristic the index uses to pick a path."""
+    ok = nq >= 1 and N >= BATCH_MIN_ROWS and k <= BATCH_MAX_K
+    if not ok or not auto:
+        return ok
+    return float(N) * nq >= BATCH_MIN_PAIRS if nq >= BATCH_MIN_QUERIES else N >= PLANE_MIN_ROWS
+
+
+def sel_batch_applies(N, nq, k, count, total=None):
+    """the routing rule of the filtered search: the prepared-store route for a selection whose size is known on the host and
+    dense enough (count * SEL_BATCH_MAX_SPARSITY >= total rows; total defaults to N -- a row shard passes the global figures)
+    where `batch_applies(N, nq, k, auto=True)` holds"""
+    total = N if total is None else total
+    return count is not None and int(count) * SEL_BATCH_MAX_SPARSITY >= int(total) and batch_applies(N, nq, k, auto=True)
+
+
+def _takes_id_list(sel):
+    return sel is not None and sel.ids is not None and sel.ids <= KNN_IDS_MAX
+
+
+def plan_topk(n, nq, k, sel=None, have_plane=False, searches=0, policy=PREPARE_NEVER_SMALL, auto=True):
+    """Route of a top-k search of nq queries over n (local) rows.  sel: None or the `Selection` facts; have_plane: a prepared plane
+    exists; searches: searches served since the rows last changed; policy: one of PREPARE_*.
+    auto=False is the functional API (`knn_l2_topk(..., prepared=)` and its kin): the caller's plane wherever the library takes it
+    (`batch_applies` without the size heuristic, at any density of the selection), and nothing is ever prepared."""
+    if _takes_id_list(sel):
+        return Route("ids", False)
+    if not auto:
+        return Route("plane" if have_plane and batch_applies(n, nq, k) else "rows", False)
+    pays = batch_applies(n, nq, k, auto=True) if sel is None else sel_batch_applies(n, nq, k, sel.count, sel.total)
+    if not pays:
+        return Route("rows", False)
+    if have_plane:
+        return Route("plane", False)
+    prepare = nq >= BATCH_MIN_QUERIES or policy == PREPARE_ALWAYS or (policy == PREPARE_SECOND_SEARCH and searches >= 1)
+    return Route("plane" if prepare else "rows", prepare)
+
+
+def plan_range(n, have_plane, batch_ok, sel=None, auto=True):
+    """Route of a range search over n (local) rows: "ids", "plane" (the COUNT reads the plane) or "rows".  A range search never
+    prepares.  batch_ok: whether `range_batch_applies` holds -- the library's verdict on (N, D, nq); a caller that only hands
+    the plane on to `knn_range_search`, which asks the library, passes True.  auto=True adds the rule of the index and the sharded
+    search: a plane is used from PLANE_MIN_ROWS rows on."""
+    if _takes_id_list(sel):
+        return "ids"
+    return "plane" if have_plane and batch_ok and (not auto or n >= PLANE_MIN_ROWS) else "rows"
+
+
+# ---- the native calls ----------------------------------------------------------------------------------------------------------------
+
+def _planned_bytes(entry, *shape, outs=1):
+    """a host-only planner of the library, entry(*shape, &bytes ...): the byte count(s) it reports"""
+    b = [ctypes.c_size_t(0) for _ in range(outs)]
+    nv.check(getattr(nv.lib(), entry)(*shape, *map(ctypes.byref, b)), entry)
+    return b[0].value if outs == 1 else tuple(x.value for x in b)
+
+
+def knn_workspace_bytes(N, D, nq, k):
+    return _planned_bytes("ac_knn_l2_topk_workspace", N, D, nq, k)
+
+
+def knn_batch_workspace_bytes(N, D, nq, k):
+    return _planned_bytes("ac_knn_l2_topk_batch_workspace", N, D, nq, k)
 
 
 def store_buffers_sizes(rows, D):
     """(plane elements, norm elements) a prepared store of `rows` rows occupies"""
-    pb, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_store_bytes(rows, D, ctypes.byref(pb), ctypes.byref(nb)), "ac_knn_store_bytes")
-    return pb.value // 2, nb.value // 4
+    pb, nb = _planned_bytes("ac_knn_store_bytes", rows, D, outs=2)
+    return pb // 2, nb // 4
+
+
+def store_buffers(rows, D, device):
+    """Empty (plane int16, norms fp32) buffers of a prepared store of up to `rows` rows (`ac_knn_store_bytes`)."""
+    pe, ne = store_buffers_sizes(rows, D)
+    return torch.empty(pe, dtype=torch.int16, device=device), torch.empty(ne, dtype=torch.float32, device=device)
 
 
 def update_store(P, n_old, n_new, D, prepared, row0, nrows):
@@ -73,23 +167,70 @@ def prepare_store(P, N, D, capacity=None):
     operand plane + |p|^2 per row.  Costs two passes over the rows and 2 B per element.  After rows change: `update_store`
     (appended / overwritten rows) or prepare anew.  capacity: size the buffers for that many rows (stores that grow)."""
     nv.require_gpu()
-    pb, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_store_bytes(max(N, capacity or 0), D, ctypes.byref(pb), ctypes.byref(nb)), "ac_knn_store_bytes")
-    planes = torch.empty(pb.value // 2, dtype=torch.int16, device=P.device)
-    norms = torch.empty(nb.value // 4, dtype=torch.float32, device=P.device)
+    planes, norms = store_buffers(max(N, capacity or 0), D, P.device)
     with torch.cuda.device(P.device):
         nv.check(nv.lib().ac_knn_prepare_store(nv.ptr(P), N, P.stride(0), D, nv.ptr(planes), nv.ptr(norms),
                                                nv.stream_ptr(P.device)), "ac_knn_prepare_store")
     return planes, norms
 
 
-def batch_applies(N, nq, k, auto=False):
-    """Library limits of ac_knn_l2_topk_batch / ac_knn_ip_topk_batch (any number of queries: below 64 they run the fp16-plane
-    sweep); auto=True adds the size heuristic the index uses to pick a path."""
-    ok = nq >= 1 and N >= BATCH_MIN_ROWS and k <= BATCH_MAX_K
-    if not ok or not auto:
-        return ok
-    return float(N) * nq >= BATCH_MIN_PAIRS if nq >= BATCH_MIN_QUERIES else N >= PLANE_MIN_ROWS
+def _check_rows_queries(P, Q, metric):
+    """what every kNN entry asks of its rows and queries (and fails loudly without a GPU)"""
+    nv.require_gpu()
+    assert metric in ("l2", "ip")
+    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
+    assert P.stride(1) == 1 and Q.stride(1) == 1
+
+
+def _sel_args(sel, sel_bit0, N):
+    """(d_sel, sel_bit0) of a RowSelector / its words tensor; ValueError unless it covers rows [sel_bit0, sel_bit0 + N)"""
+    words = sel.words if isinstance(sel, RowSelector) else sel
+    assert words.dtype == torch.int64 and words.is_cuda and words.is_contiguous()
+    if int(sel_bit0) + N > words.numel() * 64:
+        raise ValueError(f"selection of {words.numel() * 64} bits does not cover rows [{sel_bit0}, {int(sel_bit0) + N})")
+    return nv.ptr(words), int(sel_bit0)
+
+
+def _ids_args(ids):
+    """(d_ids, M) of a `from_ids` RowSelector / a sorted, unique int64 cuda tensor"""
+    ids = ids.ids if isinstance(ids, RowSelector) else ids
+    assert ids is not None and ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
+    return nv.ptr(ids) if ids.numel() else None, ids.numel()
+
+
+def _knn_topk(metric, kind, P, N, D, Q, k, row_offset, out, exact_out, workspace=None, stats=None, prepared=None, sel=None, sel_bit0=0,
+              ids=None):
+    """THE top-k call: ac_knn_{metric}_topk_{x, batch, sel, batch_sel, ids}, by the route `kind` and whether a bitmap is given.
+    The argument list is  rows [store] [id list] queries k row_offset [bitmap]  outD outD64 outI  [workspace stats]  stream."""
+    _check_rows_queries(P, Q, metric)
+    nq, dev = Q.shape[0], Q.device
+    head = (nv.ptr(P), N, P.stride(0), D)
+    if kind == "plane":
+        head += (nv.ptr(prepared[0]), nv.ptr(prepared[1]))
+    elif kind == "ids":
+        head += _ids_args(ids)
+    head += (nv.ptr(Q), nq, Q.stride(0), k, row_offset)
+    if sel is not None:
+        head += _sel_args(sel, sel_bit0, N)
+    if out is None:
+        out = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev))
+    outD, outI = out
+    tail = (nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI))
+    if kind == "ids":
+        entry = f"ac_knn_{metric}_topk_ids"                  # reads the listed rows only: no workspace, no stats
+    else:
+        form = ("batch", "batch_sel") if kind == "plane" else ("x", "sel")
+        entry = f"ac_knn_{metric}_topk_{form[sel is not None]}"
+        # (the planners of the two metrics report the same bytes; which one is asked is kept as it was, call for call)
+        need = _planned_bytes("ac_knn_l2_topk_workspace" if kind == "rows" else
+                              f"ac_knn_{metric if sel is None else 'l2'}_topk_batch_workspace", N, D, nq, k)
+        if workspace is None or workspace.numel() < need:
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        tail += (nv.ptr(workspace), workspace.numel(), nv.ptr(stats))
+    with torch.cuda.device(dev):
+        rc = getattr(nv.lib(), entry)(*head, *tail, nv.stream_ptr(dev))
+    nv.check(rc, entry)
+    return outD, outI
 
 
 def knn_l2_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=None, exact_out=None, prepared=None):
@@ -99,35 +240,11 @@ def knn_l2_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=Non
     exact_out: optional float64 [nq,k] cuda tensor that receives the exact fp64 distances (shard merges).
     prepared: optional (planes, norms) from `prepare_store`: the search then proposes from the store's fp16 plane
               (`ac_knn_l2_topk_batch`: one bandwidth-bound pass for < 64 queries, the GEMM-form sweep on the matrix pipe from 64
-              on) -- same exact result, half the bytes / several times the throughput.
+              on) -- same exact result, half the bytes / several times the throughput.  Outside `batch_applies(N, nq, k)` the
+              fp32 entry (`ac_knn_l2_topk_x`) is called as without it.
     """
-    if prepared is not None and batch_applies(N, Q.shape[0], k):
-        return _knn_topk_batch("ac_knn_l2_topk_batch", P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out)
-    return _knn_topk_x("ac_knn_l2_topk_x", P, N, D, Q, k, row_offset, out, workspace, stats, exact_out)
-
-
-def _knn_topk_x(entry, P, N, D, Q, k, row_offset, out, workspace, stats, exact_out):
-    """the fp32-sweep search of either metric: `entry` = ac_knn_l2_topk_x or ac_knn_ip_topk_x (same arguments, same workspace)"""
-    nv.require_gpu()
-    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
-    assert P.stride(1) == 1 and Q.stride(1) == 1
-    nq = Q.shape[0]
-    dev = Q.device
-    if out is None:
-        outD = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    else:
-        outD, outI = out
-    need = knn_workspace_bytes(N, D, nq, k)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = getattr(nv.lib(), entry)(
-            nv.ptr(P), N, P.stride(0), D, nv.ptr(Q), nq, Q.stride(0), k, row_offset,
-            nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(),
-            nv.ptr(stats), nv.stream_ptr(dev))
-    nv.check(rc, entry)
-    return outD, outI
+    kind = plan_topk(N, Q.shape[0], k, have_plane=prepared is not None, auto=False).kind
+    return _knn_topk("l2", kind, P, N, D, Q, k, row_offset, out, exact_out, workspace, stats, prepared)
 
 
 def knn_ip_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=None, exact_out=None, prepared=None):
@@ -135,71 +252,24 @@ def knn_ip_topk(P, N, D, Q, k, row_offset=0, out=None, workspace=None, stats=Non
     descending, ties to the lower id; rows need not be normalised.  Arguments and workspace as `knn_l2_topk`, `prepared`
     included: the SAME (planes, norms) of `prepare_store` serve both metrics (`ac_knn_ip_topk_batch`, same exact result).
     Returns (values fp32 [nq,k], ids int64 [nq,k]); k > N pads with (-FLT_MAX, -1)."""
-    if prepared is not None and batch_applies(N, Q.shape[0], k):
-        return _knn_topk_batch("ac_knn_ip_topk_batch", P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out)
-    return _knn_topk_x("ac_knn_ip_topk_x", P, N, D, Q, k, row_offset, out, workspace, stats, exact_out)
+    kind = plan_topk(N, Q.shape[0], k, have_plane=prepared is not None, auto=False).kind
+    return _knn_topk("ip", kind, P, N, D, Q, k, row_offset, out, exact_out, workspace, stats, prepared)
 
 
-def knn_ip_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, prepared=None):
-    """(exact fp64 inner products [nq,k] descending, ids [nq,k]): what a row shard contributes to a sharded IP search."""
+def _topk_exact(search, P, N, D, Q, k, row_offset, workspace, stats, prepared):
     ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
-    _, I = knn_ip_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex, prepared=prepared)
+    _, I = search(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex, prepared=prepared)
     return ex, I
-
-
-def _knn_topk_batch(entry, P, N, D, Q, k, prepared, row_offset, out, workspace, stats, exact_out):
-    """the prepared-store search of either metric: `entry` = ac_knn_l2_topk_batch or ac_knn_ip_topk_batch (same arguments; the
-    workspace planners return the same value)"""
-    nv.require_gpu()
-    planes, norms = prepared
-    nq, dev = Q.shape[0], Q.device
-    if out is None:
-        outD = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    else:
-        outD, outI = out
-    b = ctypes.c_size_t(0)
-    nv.check(getattr(nv.lib(), entry + "_workspace")(N, D, nq, k, ctypes.byref(b)), entry + "_workspace")
-    if workspace is None or workspace.numel() < b.value:
-        workspace = torch.empty(b.value, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = getattr(nv.lib(), entry)(
-            nv.ptr(P), N, P.stride(0), D, nv.ptr(planes), nv.ptr(norms), nv.ptr(Q), nq, Q.stride(0), k, row_offset,
-            nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(), nv.ptr(stats),
-            nv.stream_ptr(dev))
-    nv.check(rc, entry)
-    return outD, outI
-
-
-def knn_batch_workspace_bytes(N, D, nq, k):
-    b = ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_l2_topk_batch_workspace(N, D, nq, k, ctypes.byref(b)), "ac_knn_l2_topk_batch_workspace")
-    return b.value
 
 
 def knn_l2_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, prepared=None):
     """(exact fp64 dist [nq,k], ids [nq,k]): what a row shard contributes to a sharded search."""
-    ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
-    _, I = knn_l2_topk(P, N, D, Q, k, row_offset=row_offset, workspace=workspace, stats=stats, exact_out=ex, prepared=prepared)
-    return ex, I
+    return _topk_exact(knn_l2_topk, P, N, D, Q, k, row_offset, workspace, stats, prepared)
 
 
-KNN_IDS_MAX = 8192       # rows the id-list route covers (include/acamd.h: ac_knn_*_topk_ids)
-# The filtered search takes the prepared store only for a selection KNOWN to hold at least 1 / 32 of the rows: the thresholds of
-# the prepared-store sweeps come from selected rows only -- stage A samples >= 128 k' rows, a two-phase round sees 256 tiles of 256
-# rows -- and at density 1 / 32 both still see >= 4 k' selected rows, the planner's own margin.  Sparser, the thresholds may stay
-# +inf; a store with more selected rows than the candidate buffer holds then overflows it and every query is redone in fp64 (exact,
-# but slower than the fp32 route).  Measured at 256 x 1M x 768 (profiles/knn_select/README.md): no query takes the fallback at
-# 1/32 -- nor at 1 %, where the 10 159 selected rows still fit the buffer; the fraction stays at the planner's margin.
-SEL_BATCH_MAX_SPARSITY = 32
-
-
-def sel_batch_applies(N, nq, k, count, total=None):
-    """the routing rule of the filtered search: the prepared-store route for a selection whose size is known on the host and
-    dense enough (count * SEL_BATCH_MAX_SPARSITY >= total rows; total defaults to N -- a row shard passes the global figures)
-    where `batch_applies(N, nq, k, auto=True)` holds"""
-    total = N if total is None else total
-    return count is not None and int(count) * SEL_BATCH_MAX_SPARSITY >= int(total) and batch_applies(N, nq, k, auto=True)
+def knn_ip_topk_exact(P, N, D, Q, k, row_offset=0, workspace=None, stats=None, prepared=None):
+    """(exact fp64 inner products [nq,k] descending, ids [nq,k]): what a row shard contributes to a sharded IP search."""
+    return _topk_exact(knn_ip_topk, P, N, D, Q, k, row_offset, workspace, stats, prepared)
 
 
 def _sel_words(n):
@@ -315,6 +385,15 @@ class RowSelector:
         return self.known_count
 
 
+def selection_facts(sel, id_list=True):
+    """the planner's `Selection` of a RowSelector (None stays None), from what the host already holds -- `count()` is never
+    called.  id_list=False: the caller has no id-list route (a row shard: the ids are global)."""
+    if sel is None:
+        return None
+    ids = getattr(sel, "ids", None) if id_list else None
+    return Selection(None if ids is None else ids.numel(), getattr(sel, "known_count", None), getattr(sel, "n", None))
+
+
 def knn_topk_sel(P, N, D, Q, k, sel, metric="l2", sel_bit0=0, row_offset=0, out=None, workspace=None, stats=None, exact_out=None,
                  prepared=None):
     """FILTERED top-k (`ac_knn_l2_topk_sel` / `ac_knn_ip_topk_sel`): the k best rows of P[:N] AMONG the selected ones -- what
@@ -325,70 +404,28 @@ def knn_topk_sel(P, N, D, Q, k, sel, metric="l2", sel_bit0=0, row_offset=0, out=
     `batch_applies(N, nq, k)` holds the search proposes from the store's fp16 plane (`ac_knn_*_topk_batch_sel`, workspace
     `knn_batch_workspace_bytes`) -- the same exact result at any density of the selection, but only worth it for a dense one
     (`sel_batch_applies`); else, and without it, the fp32 rows are searched.  Asynchronous."""
-    nv.require_gpu()
-    assert metric in ("l2", "ip")
-    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
-    assert P.stride(1) == 1 and Q.stride(1) == 1
-    words = sel.words if isinstance(sel, RowSelector) else sel
-    assert words.dtype == torch.int64 and words.is_cuda and words.is_contiguous()
-    if int(sel_bit0) + N > words.numel() * 64:
-        raise ValueError(f"selection of {words.numel() * 64} bits does not cover rows [{sel_bit0}, {int(sel_bit0) + N})")
-    nq, dev = Q.shape[0], Q.device
-    if out is None:
-        outD = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    else:
-        outD, outI = out
-    batch = prepared is not None and batch_applies(N, nq, k)
-    need = knn_batch_workspace_bytes(N, D, nq, k) if batch else knn_workspace_bytes(N, D, nq, k)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    entry = f"ac_knn_{metric}_topk_batch_sel" if batch else f"ac_knn_{metric}_topk_sel"
-    store = (nv.ptr(prepared[0]), nv.ptr(prepared[1])) if batch else ()
-    with torch.cuda.device(dev):
-        rc = getattr(nv.lib(), entry)(
-            nv.ptr(P), N, P.stride(0), D, *store, nv.ptr(Q), nq, Q.stride(0), k, row_offset, nv.ptr(words), int(sel_bit0),
-            nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.ptr(workspace), workspace.numel(), nv.ptr(stats), nv.stream_ptr(dev))
-    nv.check(rc, entry)
-    return outD, outI
+    kind = plan_topk(N, Q.shape[0], k, have_plane=prepared is not None, auto=False).kind
+    return _knn_topk(metric, kind, P, N, D, Q, k, row_offset, out, exact_out, workspace, stats, prepared, sel, sel_bit0)
 
 
 def knn_topk_ids(P, N, D, Q, k, ids, metric="l2", row_offset=0, out=None, exact_out=None):
     """FILTERED top-k over a short id list (`ac_knn_l2_topk_ids` / `ac_knn_ip_topk_ids`): ids = a RowSelector built by
     `from_ids`, or a SORTED, UNIQUE int64 cuda tensor of <= KNN_IDS_MAX row ids (ids outside [0, N) are skipped).  Reads the
     listed rows only; exact by construction, any k and D, no workspace.  Same result as `knn_topk_sel` with those rows."""
-    nv.require_gpu()
-    assert metric in ("l2", "ip")
-    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
-    assert P.stride(1) == 1 and Q.stride(1) == 1
-    ids = ids.ids if isinstance(ids, RowSelector) else ids
-    assert ids is not None and ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
-    nq, dev = Q.shape[0], Q.device
-    if out is None:
-        outD = torch.empty((nq, k), dtype=torch.float32, device=dev)
-        outI = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    else:
-        outD, outI = out
-    entry = f"ac_knn_{metric}_topk_ids"
-    with torch.cuda.device(dev):
-        rc = getattr(nv.lib(), entry)(
-            nv.ptr(P), N, P.stride(0), D, nv.ptr(ids) if ids.numel() else None, ids.numel(), nv.ptr(Q), nq, Q.stride(0), k, row_offset,
-            nv.ptr(outD), nv.ptr(exact_out), nv.ptr(outI), nv.stream_ptr(dev))
-    nv.check(rc, entry)
-    return outD, outI
+    return _knn_topk(metric, "ids", P, N, D, Q, k, row_offset, out, exact_out, ids=ids)
 
 
 def knn_range_workspace_bytes(N, D, nq):
-    b = ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_range_workspace(N, D, nq, ctypes.byref(b)), "ac_knn_range_workspace")
-    return b.value
+    return _planned_bytes("ac_knn_range_workspace", N, D, nq)
 
 
 def knn_range_batch_workspace_bytes(N, D, nq):
     """workspace of `ac_knn_*_range_count_batch[_sel]` (its prefix is the fp32 route's, which the fill reads)"""
-    b = ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_range_batch_workspace(N, D, nq, ctypes.byref(b)), "ac_knn_range_batch_workspace")
-    return b.value
+    return _planned_bytes("ac_knn_range_batch_workspace", N, D, nq)
+
+
+def knn_range_ids_workspace_bytes(M, nq):
+    return _planned_bytes("ac_knn_range_ids_workspace", M, nq)
 
 
 def range_batch_applies(N, D, nq):
@@ -426,6 +463,43 @@ def stitch_range_chunks(parts, device=None):
     return (torch.cat(lims), torch.cat([d for _, d, _ in parts]), torch.cat([i for _, _, i in parts]))
 
 
+def _knn_range(metric, form, P, N, D, Q, radius, row_offset, exact_out, stats, chunk, ws_need, count_mid=(), fill_mid=(), sel_args=()):
+    """THE range search: per chunk of `chunk` queries  count -> the protocol's one host read -> allocate -> fill.
+    count entry ac_knn_{metric}_range_count{form}:  rows *count_mid queries radii *sel_args lims workspace stats stream;
+    fill entry ac_knn_{metric}_range_fill[_ids]:    rows *fill_mid queries row_offset lims total outD outD64 outI workspace stats stream."""
+    nq, dev = Q.shape[0], Q.device
+    if torch.is_tensor(radius):
+        rad = radius.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        assert rad.numel() == nq, "one radius per query"
+    else:
+        rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
+    if nq == 0:
+        empty = stitch_range_chunks([], dev)
+        return empty + (torch.empty(0, dtype=torch.float64, device=dev),) if exact_out else empty
+    count_name, fill_name = f"ac_knn_{metric}_range_count{form}", f"ac_knn_{metric}_range_fill" + ("_ids" if form == "_ids" else "")
+    count, fill = getattr(nv.lib(), count_name), getattr(nv.lib(), fill_name)
+    ws = torch.empty(max(ws_need, 256), dtype=torch.uint8, device=dev)
+    rows, tail = (nv.ptr(P), N, P.stride(0), D), (nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev))
+    parts = []
+    with torch.cuda.device(dev):
+        for s in range(0, nq, chunk):
+            q, r = Q[s:s + chunk], rad[s:s + chunk]
+            queries = (nv.ptr(q), q.shape[0], q.stride(0))
+            lims = torch.empty(q.shape[0] + 1, dtype=torch.int64, device=dev)
+            nv.check(count(*rows, *count_mid, *queries, nv.ptr(r), *sel_args, nv.ptr(lims), *tail), count_name)
+            total = int(lims[-1].item())                      # the protocol's one host read: sizes the outputs
+            outD = torch.empty(total, dtype=torch.float32, device=dev)
+            outI = torch.empty(total, dtype=torch.int64, device=dev)
+            outE = torch.empty(total, dtype=torch.float64, device=dev) if exact_out else None
+            nv.check(fill(*rows, *fill_mid, *queries, row_offset, nv.ptr(lims), total, nv.ptr(outD), nv.ptr(outE), nv.ptr(outI), *tail),
+                     fill_name)
+            parts.append((lims, outD, outI, outE))
+    out = stitch_range_chunks([p[:3] for p in parts], dev)
+    if not exact_out:
+        return out
+    return out + (parts[0][3] if len(parts) == 1 else torch.cat([p[3] for p in parts]),)
+
+
 def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=False, max_ws_bytes=256 << 20, stats=None, sel=None,
                      sel_bit0=0, prepared=None):
     """Exact range search (`ac_knn_l2_range_count` / `_fill`, or the `ip` pair): every row of P[:N] with float32(exact squared
@@ -444,58 +518,15 @@ def knn_range_search(P, N, D, Q, radius, metric="l2", row_offset=0, exact_out=Fa
     the store's fp16 plane (`ac_knn_*_range_count_batch[_sel]`: half the bytes; stats[2] = 2 reports it) -- the same bits at any
     radius, since every pair the plane cannot decide is decided from the fp32 rows as before.  The fill and the host read per chunk
     are unchanged; chunks are sized by the batch workspace."""
-    nv.require_gpu()
-    assert metric in ("l2", "ip")
-    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
-    assert P.stride(1) == 1 and Q.stride(1) == 1
-    nq, dev = Q.shape[0], Q.device
-    batch = prepared is not None and range_batch_applies(N, D, nq)
-    store_args = (nv.ptr(prepared[0]), nv.ptr(prepared[1])) if batch else ()
-    ws_bytes = knn_range_batch_workspace_bytes if batch else knn_range_workspace_bytes
-    sel_args = ()
-    if sel is not None:
-        words = sel.words if isinstance(sel, RowSelector) else sel
-        assert words.dtype == torch.int64 and words.is_cuda and words.is_contiguous()
-        if int(sel_bit0) + N > words.numel() * 64:
-            raise ValueError(f"selection of {words.numel() * 64} bits does not cover rows [{sel_bit0}, {int(sel_bit0) + N})")
-        sel_args = (nv.ptr(words), int(sel_bit0))
-    if torch.is_tensor(radius):
-        rad = radius.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert rad.numel() == nq, "one radius per query"
-    else:
-        rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
-    count_name = f"ac_knn_{metric}_range_count" + ("_batch" if batch else "") + ("_sel" if sel is not None else "")
-    count = getattr(nv.lib(), count_name)
-    fill = getattr(nv.lib(), f"ac_knn_{metric}_range_fill")
+    _check_rows_queries(P, Q, metric)
+    nq = Q.shape[0]
+    plane = plan_range(N, prepared is not None, prepared is not None and range_batch_applies(N, D, nq), auto=False) == "plane"
+    ws_bytes = knn_range_batch_workspace_bytes if plane else knn_range_workspace_bytes
+    sel_args = () if sel is None else _sel_args(sel, sel_bit0, N)
     chunk = range_query_chunk(N, D, nq, max_ws_bytes, ws_bytes) if nq else 1
-    ws = torch.empty(max(ws_bytes(N, D, min(chunk, nq)), 256), dtype=torch.uint8, device=dev)
-    parts = []
-    with torch.cuda.device(dev):
-        for s in range(0, nq, chunk):
-            q, r = Q[s:s + chunk], rad[s:s + chunk]
-            c = q.shape[0]
-            lims = torch.empty(c + 1, dtype=torch.int64, device=dev)
-            nv.check(count(nv.ptr(P), N, P.stride(0), D, *store_args, nv.ptr(q), c, q.stride(0), nv.ptr(r), *sel_args, nv.ptr(lims),
-                           nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)), count_name)
-            total = int(lims[-1].item())                      # the protocol's one host read: sizes the outputs
-            outD = torch.empty(total, dtype=torch.float32, device=dev)
-            outI = torch.empty(total, dtype=torch.int64, device=dev)
-            outE = torch.empty(total, dtype=torch.float64, device=dev) if exact_out else None
-            nv.check(fill(nv.ptr(P), N, P.stride(0), D, nv.ptr(q), c, q.stride(0), row_offset, nv.ptr(lims), total,
-                          nv.ptr(outD), nv.ptr(outE), nv.ptr(outI), nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)),
-                     f"ac_knn_{metric}_range_fill")
-            parts.append((lims, outD, outI, outE))
-    if nq == 0:
-        empty = stitch_range_chunks([], dev)
-        return empty + (torch.empty(0, dtype=torch.float64, device=dev),) if exact_out else empty
-    out = stitch_range_chunks([p[:3] for p in parts], dev)
-    return out + (torch.cat([p[3] for p in parts]),) if exact_out else out
-
-
-def knn_range_ids_workspace_bytes(M, nq):
-    b = ctypes.c_size_t(0)
-    nv.check(nv.lib().ac_knn_range_ids_workspace(M, nq, ctypes.byref(b)), "ac_knn_range_ids_workspace")
-    return b.value
+    return _knn_range(metric, ("_batch" if plane else "") + ("_sel" if sel is not None else ""), P, N, D, Q, radius, row_offset, exact_out,
+                      stats, chunk, ws_bytes(N, D, min(chunk, nq)), count_mid=(nv.ptr(prepared[0]), nv.ptr(prepared[1])) if plane else (),
+                      sel_args=sel_args)
 
 
 def knn_range_ids(P, N, D, Q, radius, ids, metric="l2", row_offset=0, exact_out=False, stats=None):
@@ -504,36 +535,10 @@ def knn_range_ids(P, N, D, Q, radius, ids, metric="l2", row_offset=0, exact_out=
     are skipped).  Reads the listed rows only, any D and N; the workspace (a bitmap over list positions) does not depend on N, so
     the queries go in one call.  Returns what `knn_range_search(..., sel=)` returns for those rows -- bit for bit where that route
     covers the store.  One host read (the hit count).  stats[0] = the listed pairs inside the store (all decided exactly)."""
-    nv.require_gpu()
-    assert metric in ("l2", "ip")
-    assert P.dtype == torch.float32 and Q.dtype == torch.float32 and P.is_cuda and Q.is_cuda
-    assert P.stride(1) == 1 and Q.stride(1) == 1
-    ids = ids.ids if isinstance(ids, RowSelector) else ids
-    assert ids is not None and ids.dtype == torch.int64 and ids.is_cuda and ids.is_contiguous()
-    nq, dev, M = Q.shape[0], Q.device, ids.numel()
-    if torch.is_tensor(radius):
-        rad = radius.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        assert rad.numel() == nq, "one radius per query"
-    else:
-        rad = torch.full((nq,), float(radius), dtype=torch.float32, device=dev)
-    if nq == 0:
-        empty = stitch_range_chunks([], dev)
-        return empty + (torch.empty(0, dtype=torch.float64, device=dev),) if exact_out else empty
-    ws = torch.empty(max(knn_range_ids_workspace_bytes(M, nq), 256), dtype=torch.uint8, device=dev)
-    lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
-    head = (nv.ptr(P), N, P.stride(0), D, nv.ptr(ids) if M else None, M, nv.ptr(Q), nq, Q.stride(0))
-    with torch.cuda.device(dev):
-        nv.check(getattr(nv.lib(), f"ac_knn_{metric}_range_count_ids")(
-            *head, nv.ptr(rad), nv.ptr(lims), nv.ptr(ws), ws.numel(), nv.ptr(stats), nv.stream_ptr(dev)),
-            f"ac_knn_{metric}_range_count_ids")
-        total = int(lims[-1].item())                          # the protocol's one host read: sizes the outputs
-        outD = torch.empty(total, dtype=torch.float32, device=dev)
-        outI = torch.empty(total, dtype=torch.int64, device=dev)
-        outE = torch.empty(total, dtype=torch.float64, device=dev) if exact_out else None
-        nv.check(getattr(nv.lib(), f"ac_knn_{metric}_range_fill_ids")(
-            *head, row_offset, nv.ptr(lims), total, nv.ptr(outD), nv.ptr(outE), nv.ptr(outI), nv.ptr(ws), ws.numel(), nv.ptr(stats),
-            nv.stream_ptr(dev)), f"ac_knn_{metric}_range_fill_ids")
-    return (lims, outD, outI, outE) if exact_out else (lims, outD, outI)
+    _check_rows_queries(P, Q, metric)
+    listed, nq = _ids_args(ids), Q.shape[0]
+    return _knn_range(metric, "_ids", P, N, D, Q, radius, row_offset, exact_out, stats, max(nq, 1),
+                      knn_range_ids_workspace_bytes(listed[1], nq) if nq else 0, count_mid=listed, fill_mid=listed)
 
 
 class _HipFlatIndex:
@@ -590,6 +595,14 @@ class _HipFlatIndex:
             self._prepared = (planes2, norms2)
         if not update_store(self._store, n_old, self._n, self.d, self._prepared, row0, nrows):
             self._prepared = None                                         # scale changed: prepared anew at the next search
+
+    def prepare_plane(self):
+        """Build the fp16 plane NOW (a store of >= BATCH_MIN_ROWS rows; `prepare_store`: two passes over the rows) instead of at
+        the first many-query / second few-query search, and count one search as served: every search of a static store, the
+        first included, then proposes from the plane."""
+        if self.ntotal >= BATCH_MIN_ROWS:
+            self._prepared = prepare_store(self._store, self.ntotal, self.d)
+            self._searches_since_change = 1
 
     @property
     def device(self):
@@ -725,62 +738,41 @@ class _HipFlatIndex:
                 sel.cpu().numpy() if isinstance(sel, torch.Tensor) else sel), device=self.device)
         return RowSelector.from_ids(sel, self._n, device=self.device)
 
-    def _search_sel(self, q, k, sel):
-        """the FILTERED search: a selector built from <= KNN_IDS_MAX ids takes the id-list route (its length is known on the
-        host); a selection KNOWN to be dense (`sel_batch_applies`: known_count * 32 >= ntotal, where the unfiltered search
-        would take the prepared store) takes the prepared store -- the plane is prepared at once for >= BATCH_MIN_QUERIES
-        queries, fewer only use a plane that exists; everything else, an unknown count included, searches the fp32 rows"""
-        self._materialize()
+    def _as_queries(self, q):
+        """[nq, d] fp32 rows on the index's device, unit inner stride, from a tensor on any device (a vector is one query)"""
         q = q.detach().to(device=self.device, dtype=torch.float32)
         if q.dim() == 1:
             q = q.unsqueeze(0)
-        if q.stride(-1) != 1:
-            q = q.contiguous()
-        sel = self._as_selector(sel)
-        if sel.ids is not None and sel.ids.numel() <= KNN_IDS_MAX:
-            return knn_topk_ids(self._store, self._n, self.d, q, k, sel.ids, metric=self.metric)
-        batch = sel_batch_applies(self._n, q.shape[0], k, sel.known_count)
-        if batch and self._prepared is None:
-            if q.shape[0] >= BATCH_MIN_QUERIES:
-                self._prepared = prepare_store(self._store, self._n, self.d, capacity=self._store.shape[0])
-            else:
-                batch = False
-        need = knn_batch_workspace_bytes(self._n, self.d, q.shape[0], k) if batch else knn_workspace_bytes(self._n, self.d, q.shape[0], k)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        return knn_topk_sel(self._store, self._n, self.d, q, k, sel, metric=self.metric, workspace=self._ws, stats=self._stats,
-                            prepared=self._prepared if batch else None)
+        return q if q.stride(-1) == 1 else q.contiguous()
 
     def search_device(self, q, k, sel=None):
         """q: [nq, d] fp32 tensor (any device) -> (dist, ids) CUDA tensors; no host sync.  sel: a RowSelector, a bool mask
-        [ntotal] or row ids -- the k best AMONG those rows (`_search_sel`)."""
-        if sel is not None:
-            return self._search_sel(q, k, sel)
+        [ntotal] or row ids -- the FILTERED search, the k best AMONG those rows.  The route is `plan_topk`'s (module docstring):
+        unfiltered, the L2 index prepares a missing plane on its second small search; the IP index and every filtered search
+        prepare only from BATCH_MIN_QUERIES queries on, fewer use a plane that exists."""
         self._materialize()
-        q = q.detach().to(device=self.device, dtype=torch.float32)
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        if q.stride(-1) != 1:
-            q = q.contiguous()
-        batch = batch_applies(self._n, q.shape[0], k, auto=True)
-        if batch and self._prepared is None:
-            # preparing costs two passes over the rows (~0.14 s at 10M x 768): at once for a many-query search (it pays within
-            # the call); for a small batch only when the store has already served a search since it was last rebuilt / compacted
-            # (appends and in-place updates do not count: once prepared, the plane follows them incrementally); the IP index
-            # never prepares from small searches (class docstring)
-            if q.shape[0] >= BATCH_MIN_QUERIES or (self.metric == "l2" and self._searches_since_change >= 1):
-                # (sized for the store's CAPACITY: the first append after the preparation then updates the plane in place
-                #  instead of allocating capacity-sized buffers and copying the whole old plane beside them)
-                self._prepared = prepare_store(self._store, self._n, self.d, capacity=self._store.shape[0])
-            else:
-                batch = False
-        self._searches_since_change += 1
-        need = knn_batch_workspace_bytes(self._n, self.d, q.shape[0], k) if batch else knn_workspace_bytes(self._n, self.d, q.shape[0], k)
+        q = self._as_queries(q)
+        if sel is not None:
+            sel = self._as_selector(sel)
+        # (appends and in-place updates do not reset the count of searches: once prepared, the plane follows them incrementally)
+        policy = PREPARE_SECOND_SEARCH if sel is None and self.metric == "l2" else PREPARE_NEVER_SMALL
+        route = plan_topk(self._n, q.shape[0], k, selection_facts(sel), self._prepared is not None, self._searches_since_change, policy)
+        if route.kind == "ids":
+            return knn_topk_ids(self._store, self._n, self.d, q, k, sel.ids, metric=self.metric)
+        if route.prepare:
+            # (sized for the store's CAPACITY: the first append after the preparation then updates the plane in place
+            #  instead of allocating capacity-sized buffers and copying the whole old plane beside them)
+            self._prepared = prepare_store(self._store, self._n, self.d, capacity=self._store.shape[0])
+        if sel is None:
+            self._searches_since_change += 1
+        plane = route.kind == "plane"
+        need = (knn_batch_workspace_bytes if plane else knn_workspace_bytes)(self._n, self.d, q.shape[0], k)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        search = knn_ip_topk if self.metric == "ip" else knn_l2_topk
-        return search(self._store, self._n, self.d, q, k, workspace=self._ws, stats=self._stats,
-                      prepared=self._prepared if batch else None)
+        ours = dict(workspace=self._ws, stats=self._stats, prepared=self._prepared if plane else None)
+        if sel is not None:
+            return knn_topk_sel(self._store, self._n, self.d, q, k, sel, metric=self.metric, **ours)
+        return (knn_ip_topk if self.metric == "ip" else knn_l2_topk)(self._store, self._n, self.d, q, k, **ours)
 
     def search(self, x, k, sel=None):
         """faiss signature: numpy in, (float32 [nq,k], int64 [nq,k]) numpy out.  sel (faiss: params=SearchParameters(sel=...)):
@@ -798,20 +790,16 @@ class _HipFlatIndex:
         selector that carries <= KNN_IDS_MAX host ids takes the id-list route (`knn_range_ids`) first, everything else the bitmap
         route; no bitmap is read back to choose."""
         self._materialize()
-        q = q.detach().to(device=self.device, dtype=torch.float32)
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        if q.stride(-1) != 1:
-            q = q.contiguous()
+        q = self._as_queries(q)
         if sel is not None:
             sel = self._as_selector(sel)
-            if sel.ids is not None and sel.ids.numel() <= KNN_IDS_MAX:
-                return knn_range_ids(self._store, self._n, self.d, q, radius, sel.ids, metric=self.metric)
-        prepared = self._prepared if self._prepared is not None and self._n >= PLANE_MIN_ROWS else None
+        kind = plan_range(self._n, self._prepared is not None, True, selection_facts(sel))     # (knn_range_search asks the library)
+        if kind == "ids":
+            return knn_range_ids(self._store, self._n, self.d, q, radius, sel.ids, metric=self.metric)
         if self._range_stats is None and q.is_cuda:
             self._range_stats = torch.zeros(4, dtype=torch.int32, device=q.device)
         return knn_range_search(self._store, self._n, self.d, q, radius, metric=self.metric, max_ws_bytes=max_ws_bytes, sel=sel,
-                                stats=self._range_stats, prepared=prepared)
+                                stats=self._range_stats, prepared=self._prepared if kind == "plane" else None)
 
     def range_search(self, x, radius, sel=None):
         """faiss signature: numpy in, (lims int64 [nq + 1], D float32, I int64) numpy out.  L2: squared distance < radius;
@@ -843,38 +831,32 @@ class HipFlatIPIndex(_HipFlatIndex):
     metric = "ip"
 
 
-def topk_merge_ip(D_in, I_in):
-    """[shards, nq, k] per-shard DESCENDING float64 lists (`knn_ip_topk_exact`) -> global (values fp32, ids) [nq, k] by (value
-    descending, id ascending) -- ac_topk_merge_ip_f64, the merge of a row-sharded inner-product search."""
+def _topk_merge(entry, D_in, I_in):
+    """the merge entries share one argument list: [shards, nq, k] lists in, (values fp32, ids) [nq, k] out"""
     nv.require_gpu()
-    assert D_in.dtype == torch.float64
     S, nq, k = D_in.shape
-    D_in = D_in.contiguous()
-    I_in = I_in.contiguous()
+    D_in, I_in = D_in.contiguous(), I_in.contiguous()
     outD = torch.empty((nq, k), dtype=torch.float32, device=D_in.device)
     outI = torch.empty((nq, k), dtype=torch.int64, device=D_in.device)
     with torch.cuda.device(D_in.device):
-        nv.check(nv.lib().ac_topk_merge_ip_f64(nv.ptr(D_in), nv.ptr(I_in), S, nq, k, nv.ptr(outD), nv.ptr(outI),
-                                               nv.stream_ptr(D_in.device)), "ac_topk_merge_ip_f64")
+        nv.check(getattr(nv.lib(), entry)(nv.ptr(D_in), nv.ptr(I_in), S, nq, k, nv.ptr(outD), nv.ptr(outI), nv.stream_ptr(D_in.device)),
+                 entry)
     return outD, outI
+
+
+def topk_merge_ip(D_in, I_in):
+    """[shards, nq, k] per-shard DESCENDING float64 lists (`knn_ip_topk_exact`) -> global (values fp32, ids) [nq, k] by (value
+    descending, id ascending) -- ac_topk_merge_ip_f64, the merge of a row-sharded inner-product search."""
+    assert D_in.dtype == torch.float64
+    return _topk_merge("ac_topk_merge_ip_f64", D_in, I_in)
 
 
 def topk_merge(D_in, I_in):
     """[shards, nq, k] per-shard ascending lists -> global (dist fp32, ids) [nq, k].  float64 input (the shards' exact
     distances, `knn_l2_topk_exact`) is merged by (exact distance, id) -- ac_topk_merge_f64, what a sharded search needs to
     equal the unsharded one bit for bit; float32 input by (fp32 distance, id) -- ac_topk_merge."""
-    nv.require_gpu()
-    S, nq, k = D_in.shape
-    D_in = D_in.contiguous()
-    I_in = I_in.contiguous()
-    outD = torch.empty((nq, k), dtype=torch.float32, device=D_in.device)
-    outI = torch.empty((nq, k), dtype=torch.int64, device=D_in.device)
-    fn, name = ((nv.lib().ac_topk_merge_f64, "ac_topk_merge_f64") if D_in.dtype == torch.float64
-                else (nv.lib().ac_topk_merge, "ac_topk_merge"))
     assert D_in.dtype in (torch.float32, torch.float64)
-    with torch.cuda.device(D_in.device):
-        nv.check(fn(nv.ptr(D_in), nv.ptr(I_in), S, nq, k, nv.ptr(outD), nv.ptr(outI), nv.stream_ptr(D_in.device)), name)
-    return outD, outI
+    return _topk_merge("ac_topk_merge_f64" if D_in.dtype == torch.float64 else "ac_topk_merge", D_in, I_in)
 
 
 def proto_scores(D, I):

@@ -439,10 +439,7 @@ class PrototypeMemory:
         self.updates_since_rebuild = 0
         self._dirty.clear()
         if prepare and sharded is None:
-            from .index import BATCH_MIN_ROWS, prepare_store
-            if self.index.ntotal >= BATCH_MIN_ROWS:
-                self.index._prepared = prepare_store(self.index._store, self.index.ntotal, self.index.d)
-                self.index._searches_since_change = 1
+            self.index.prepare_plane()
 
     # ------------------------------------------------------------------ search
     def _among_selector(self, among):

@@ -84,21 +84,12 @@ class ShardedSearch:
             from . import index as ix
 
             def _hip_search(P, n, D, Q, k, off):
-                # many queries x a big shard: the prepared-store GEMM-form sweep (same exact result)
-                if ix.batch_applies(n, Q.shape[0], k, auto=True):
-                    if self._prepared is None:
-                        self._prepared = ix.prepare_store(P, n, D)
-                    return ix.knn_l2_topk_exact(P, n, D, Q, k, row_offset=off, prepared=self._prepared)
-                return ix.knn_l2_topk_exact(P, n, D, Q, k, row_offset=off)
+                # a big shard: the prepared store (same exact result, either metric), prepared on first use
+                exact = ix.knn_ip_topk_exact if self.metric == "ip" else ix.knn_l2_topk_exact
+                return exact(P, n, D, Q, k, row_offset=off, prepared=self._plane_for(ix.plan_topk(
+                    n, Q.shape[0], k, have_plane=self._prepared is not None, policy=ix.PREPARE_ALWAYS)))
 
-            def _hip_search_ip(P, n, D, Q, k, off):
-                if ix.batch_applies(n, Q.shape[0], k, auto=True):            # the same prepared store, searched by inner product
-                    if self._prepared is None:
-                        self._prepared = ix.prepare_store(P, n, D)
-                    return ix.knn_ip_topk_exact(P, n, D, Q, k, row_offset=off, prepared=self._prepared)
-                return ix.knn_ip_topk_exact(P, n, D, Q, k, row_offset=off)
-
-            local_search = local_search or (_hip_search_ip if metric == "ip" else _hip_search)
+            local_search = local_search or _hip_search
             merge = merge or (ix.topk_merge_ip if metric == "ip" else ix.topk_merge)
         self._search, self._merge = local_search, merge
         self._range = local_range
@@ -186,24 +177,26 @@ class ShardedSearch:
             return g.reshape(-1, q_local.shape[-1])
         return torch.cat([g[r, :sizes[r]] for r in range(self.world)])
 
+    def _plane_for(self, route):
+        """the shard's plane when `route` (of `index.plan_topk`) takes it -- prepared now, for n_local rows, when it says so"""
+        if route.prepare:
+            from . import index as ix
+            self._prepared = ix.prepare_store(self.rows, self.n_local, self.dim)
+        return self._prepared if route.kind == "plane" else None
+
     def _local(self, Q, k, sel):
         """this rank's shard searched for Q: (exact fp64 values, global ids).  sel: None, or the GLOBAL RowSelector (replicated
         on every rank) -- the shard reads its slice of the bitmap in place (sel_bit0 = row_offset).  The index's routing rule
-        with the GLOBAL figures (`index.sel_batch_applies`: the selector's known count over the rows it covers): a dense
+        (`index.plan_topk`) with the GLOBAL figures (the selector's known count over the rows it covers): a dense
         selection searches the shard's prepared plane -- prepared at once for >= BATCH_MIN_QUERIES queries, fewer only use a
-        plane that exists -- anything else, an unknown count included, the fp32 rows."""
+        plane that exists -- anything else, an unknown count included, the fp32 rows.  A shard has no id-list route."""
         if sel is None:
             return self._search(self.rows, self.n_local, self.dim, Q, k, self.row_offset)
         from . import index as ix
-        batch = ix.sel_batch_applies(self.n_local, Q.shape[0], k, getattr(sel, "known_count", None), total=getattr(sel, "n", None))
-        if batch and self._prepared is None:
-            if Q.shape[0] >= ix.BATCH_MIN_QUERIES:
-                self._prepared = ix.prepare_store(self.rows, self.n_local, self.dim)
-            else:
-                batch = False
+        route = ix.plan_topk(self.n_local, Q.shape[0], k, ix.selection_facts(sel, id_list=False), self._prepared is not None)
         ex = torch.empty((Q.shape[0], k), dtype=torch.float64, device=Q.device)
         _, I = ix.knn_topk_sel(self.rows, self.n_local, self.dim, Q, k, sel, metric=self.metric, sel_bit0=self.row_offset,
-                               row_offset=self.row_offset, exact_out=ex, prepared=self._prepared if batch else None)
+                               row_offset=self.row_offset, exact_out=ex, prepared=self._plane_for(route))
         return ex, I
 
     def search(self, queries, k, sel=None):
@@ -268,9 +261,9 @@ class ShardedSearch:
             from . import index as ix
 
             def _hip_range(P, n, D, Q, radius, off, sel, sel_bit0):
-                prepared = self._prepared if self._prepared is not None and n >= ix.PLANE_MIN_ROWS else None
+                plane = ix.plan_range(n, self._prepared is not None, True) == "plane"      # (knn_range_search asks the library)
                 return ix.knn_range_search(P, n, D, Q, radius, metric=self.metric, row_offset=off, exact_out=True, sel=sel,
-                                           sel_bit0=sel_bit0 if sel is not None else 0, prepared=prepared)
+                                           sel_bit0=sel_bit0 if sel is not None else 0, prepared=self._prepared if plane else None)
             self._range = _hip_range
         return self._range(self.rows, self.n_local, self.dim, queries, radius, self.row_offset, sel, self.row_offset)
 

@@ -75,6 +75,11 @@ class ac_wordpiece_vocab(ctypes.Structure):
                 ("pad_id", c_int), ("lower_case", c_int)]
 
 
+class ac_bpe_vocab(ctypes.Structure):
+    _fields_ = [("keys", c_void_p), ("entries", c_void_p), ("blob", c_void_p), ("byte_id", c_void_p), ("slots", c_int),
+                ("cls_id", c_int), ("sep_id", c_int), ("pad_id", c_int), ("add_prefix_space", c_int)]
+
+
 class ac_bert_weights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in (
         "word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b",
@@ -233,6 +238,10 @@ _SIGNATURES = {
     "ac_wordpiece_hash": (c_uint64, [c_void_p, c_int, c_int]),
     "ac_wordpiece_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_wordpiece_vocab), c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+    "ac_bpe_pair_hash": (c_uint64, [c_void_p, c_int, c_void_p, c_int]),
+    "ac_bpe_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p,
+                              c_void_p]),
+    "ac_bpe_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p]),
     "ac_bert_workspace": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_bert_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ac_bert_encode_cls_packed": (c_int, [ctypes.POINTER(ac_bert_config), ctypes.POINTER(ac_bert_weights), c_void_p, c_void_p,

@@ -1,18 +1,27 @@
-"""HipWordPieceTokenizer: the tokenizer call of the hot path on MI355X.
+"""Device tokenizers: the tokenizer call of the hot path on MI355X.
 
-Replaces `self.tokenizer(texts, max_length=..., truncation=True, padding=True, return_tensors="pt")`
-(/root/reference/src/adaptive_classifier/classifier.py:1259-1265) for BERT-family WordPiece vocabularies
-(transformers BertTokenizer / DistilBertTokenizer ...: tokenizers BertNormalizer + BertPreTokenizer + WordPiece).
-The ids are produced on the device by `ac_wordpiece_encode` and handed to the encoder without a host round trip:
-host work per batch is one concatenation of the texts' bytes, one small H2D and one 4-byte D2H (the padded length,
-which the encoder launch needs).
+Replace `self.tokenizer(texts, max_length=..., truncation=True, padding=True, return_tensors="pt")`
+(/root/reference/src/adaptive_classifier/classifier.py:1259-1265) for the two tokenizer families the encoders cover:
 
-Exactness: identical ids / mask to the wrapped transformers tokenizer.  The kernel covers ASCII texts of up to 4096
-bytes; texts with non-ASCII bytes (accent stripping / CJK spacing / Unicode punctuation live in the host library),
-longer texts, and texts containing a literal special-token string ("[SEP]", "[MASK]" ...) are tokenised by the wrapped
-tokenizer itself and spliced into the batch -- the reference's own tokenizer, not a re-implementation.
+* `HipWordPieceTokenizer` -- BERT-family WordPiece vocabularies (transformers BertTokenizer / DistilBertTokenizer ...:
+  tokenizers BertNormalizer + BertPreTokenizer + WordPiece), ids from `ac_wordpiece_encode`;
+* `HipByteBPETokenizer` -- GPT-2 byte-level BPE (RoBERTa-style and ModernBERT-style tokenizers: tokenizers
+  ByteLevel(use_regex=True) + BPE behind RobertaProcessing or a `<cls> $A <sep>` template), ids from `ac_bpe_encode`.
+  The vocabulary strings and merge sides are turned back into raw bytes (ByteLevel's byte <-> unicode map inverted), so the
+  kernel works on the text's own bytes; `ac_bpe_encode_host` runs the same algorithm on the CPU.
+
+Either way the ids are produced on the device and handed to the encoder without a host round trip: host work per batch is
+one concatenation of the texts' bytes, one small H2D and one small D2H (the padded length, which the encoder launch needs).
+A tokenizer is recognised by its serialised configuration (`_wordpiece_spec`, `_bpe_spec`), never by a model name.
+
+Exactness: identical ids / mask to the wrapped transformers tokenizer.  The kernels cover ASCII texts of up to 4096
+bytes; texts with non-ASCII bytes (accent stripping / CJK spacing / Unicode categories / NFC live in the host library),
+longer texts, texts containing a literal special- or added-token string ("[SEP]", "<s>", ModernBERT's runs of spaces ...)
+and texts the BPE kernel reports as not done (a pre-token of more than 64 bytes) are tokenised by the wrapped tokenizer
+itself and spliced into the batch -- the reference's own tokenizer, not a re-implementation.
 """
 import ctypes
+import json
 
 import numpy as np
 import torch
@@ -22,15 +31,27 @@ from . import _native as nv
 MAX_DEVICE_BYTES = 4096
 
 
-def _wordpiece_spec(tok):
-    """(vocab dict, lower_case, specials) if `tok` is a BERT-style WordPiece tokenizer this module reproduces, else None."""
+def _backend_config(tok):
+    """The serialised tokenizers pipeline behind a transformers fast tokenizer, or None."""
     be = getattr(tok, "backend_tokenizer", None) or getattr(tok, "_tokenizer", None)
     if be is None:
         return None
     try:
-        import json
-        cfg = json.loads(be.to_str())
+        return json.loads(be.to_str())
     except Exception:
+        return None
+
+
+def _literal_tokens(tok, cfg, need):
+    """Strings the host tokenizer cuts out of a text before its model runs: special and added tokens."""
+    return sorted((set(str(t) for t in getattr(tok, "all_special_tokens", need)) |
+                   set(a["content"] for a in cfg.get("added_tokens") or [])) - {""})
+
+
+def _wordpiece_spec(tok):
+    """(vocab dict, lower_case, specials) if `tok` is a BERT-style WordPiece tokenizer this module reproduces, else None."""
+    cfg = _backend_config(tok)
+    if cfg is None:
         return None
     model, norm, pre = cfg.get("model") or {}, cfg.get("normalizer") or {}, cfg.get("pre_tokenizer") or {}
     if model.get("type") != "WordPiece" or norm.get("type") != "BertNormalizer" or pre.get("type") != "BertPreTokenizer":
@@ -46,24 +67,230 @@ def _wordpiece_spec(tok):
     need = [tok.unk_token, tok.cls_token, tok.sep_token, tok.pad_token]
     if any(t is None or t not in vocab for t in need) or model.get("unk_token") != tok.unk_token:
         return None
-    specials = sorted(set(str(t) for t in getattr(tok, "all_special_tokens", need)) |
-                      set(a["content"] for a in cfg.get("added_tokens") or []))
-    return vocab, bool(norm.get("lowercase", True)), specials
+    return vocab, bool(norm.get("lowercase", True)), _literal_tokens(tok, cfg, need)
 
 
-class HipWordPieceTokenizer:
-    """Callable with the signature the classifier uses; returns device tensors."""
+def _byte_to_unicode():
+    """ByteLevel's byte -> printable character map (GPT-2 bytes_to_unicode)."""
+    keep = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+    out, extra = {}, 0
+    for b in range(256):
+        if b in keep:
+            out[b] = chr(b)
+        else:
+            out[b] = chr(256 + extra)
+            extra += 1
+    return out
+
+
+def _template_ends(post):
+    """(first id, last id) of a post-processor that wraps a single sequence as <one special> $A <one special>, else None."""
+    if post.get("type") == "RobertaProcessing":
+        try:
+            return int(post["cls"][1]), int(post["sep"][1])
+        except Exception:
+            return None
+    if post.get("type") != "TemplateProcessing":
+        return None
+    single, table = post.get("single") or [], post.get("special_tokens") or {}
+    if len(single) != 3 or (single[1].get("Sequence") or {}) != {"id": "A", "type_id": 0}:
+        return None
+    ends = []
+    for piece in (single[0], single[2]):
+        sp = piece.get("SpecialToken") or {}
+        ids = (table.get(sp.get("id")) or {}).get("ids") or []
+        if sp.get("type_id") != 0 or len(ids) != 1:
+            return None
+        ends.append(int(ids[0]))
+    return tuple(ends)
+
+
+def _bpe_spec(tok):
+    """What HipByteBPETokenizer needs, as a dict, if `tok` is a GPT-2 byte-level BPE tokenizer this module reproduces
+    (RoBERTa-style / ModernBERT-style), else None:
+    vocab, merges [(left, right)] in rank order, add_prefix_space, cls_id, sep_id, pad_id, specials, token_type_ids."""
+    cfg = _backend_config(tok)
+    if cfg is None:
+        return None
+    model, norm, pre = cfg.get("model") or {}, cfg.get("normalizer"), cfg.get("pre_tokenizer") or {}
+    if model.get("type") != "BPE" or model.get("dropout") or model.get("byte_fallback") or model.get("ignore_merges") \
+            or model.get("continuing_subword_prefix") or model.get("end_of_word_suffix") or model.get("fuse_unk"):
+        return None
+    if norm is not None:                                     # NFC is the identity on ASCII; anything else is not reproduced
+        if norm.get("type") == "Sequence" and len(norm.get("normalizers") or []) == 1:
+            norm = norm["normalizers"][0]
+        if norm.get("type") != "NFC":
+            return None
+    if pre.get("type") != "ByteLevel" or not pre.get("use_regex", True):
+        return None
+    ends = _template_ends(cfg.get("post_processor") or {})
+    if ends is None:
+        return None
+    if getattr(tok, "padding_side", "right") != "right" or getattr(tok, "truncation_side", "right") != "right":
+        return None
+    vocab = model.get("vocab") or {}
+    added = {a["content"]: int(a["id"]) for a in cfg.get("added_tokens") or []}
+    pad = getattr(tok, "pad_token", None)
+    if pad is None or (pad not in vocab and pad not in added):
+        return None
+    b2u = _byte_to_unicode()
+    if any(ch not in vocab for ch in b2u.values()):
+        return None
+    merges = [tuple(m.split(" ")) if isinstance(m, str) else tuple(m) for m in model.get("merges") or []]
+    if any(len(m) != 2 for m in merges):
+        return None
+    return {"vocab": vocab, "merges": merges, "add_prefix_space": bool(pre.get("add_prefix_space", True)),
+            "cls_id": ends[0], "sep_id": ends[1], "pad_id": int(vocab[pad] if pad in vocab else added[pad]),
+            "specials": _literal_tokens(tok, cfg, [pad]),
+            "token_type_ids": "token_type_ids" in (getattr(tok, "model_input_names", None) or [])}
+
+
+def build_bpe_tables(spec):
+    """The arrays behind ac_bpe_vocab for a `_bpe_spec` result, on the host (numpy): keys uint64 [slots], entries int32
+    [slots, 4] (rank, joined id, blob offset, left_len | total_len << 16), blob uint8, byte_id int32 [256].  Needs no GPU:
+    the slots are filled with ac_bpe_pair_hash, the function the kernel probes with."""
+    L = nv.lib()
+    vocab = spec["vocab"]
+    u2b = {u: b for b, u in _byte_to_unicode().items()}
+
+    def raw(s):
+        return bytes(u2b[ch] for ch in s)
+
+    byte_id = np.zeros(256, np.int32)
+    for u, b in u2b.items():
+        byte_id[b] = vocab[u]
+    pairs = {}                                               # (left bytes, right bytes) -> (rank, id); a repeated pair keeps its last rank
+    for rank, (left, right) in enumerate(spec["merges"]):
+        if left + right not in vocab or any(ch not in u2b for ch in left + right) or len(left + right) > 0xffff:
+            raise nv.NativeError("byte-level BPE: merge %r %r does not name a vocabulary entry over the byte alphabet" % (left, right))
+        pairs[(raw(left), raw(right))] = (rank, int(vocab[left + right]))
+    slots = 2
+    while slots < 2 * len(pairs) + 16:
+        slots <<= 1
+    keys = np.zeros(slots, np.uint64)
+    entries = np.zeros((slots, 4), np.int32)
+    blob = bytearray()
+    mask = slots - 1
+    for (lb, rb), (rank, tid) in pairs.items():
+        h = int(L.ac_bpe_pair_hash((ctypes.c_uint8 * len(lb)).from_buffer_copy(lb), len(lb),
+                                   (ctypes.c_uint8 * len(rb)).from_buffer_copy(rb), len(rb)))
+        s = (h ^ (h >> 32)) & mask
+        while keys[s] != 0:
+            s = (s + 1) & mask
+        keys[s] = h
+        entries[s] = (rank, tid, len(blob), len(lb) | ((len(lb) + len(rb)) << 16))
+        blob += lb + rb
+    blob += b"\0" * 16
+    return keys, entries, np.frombuffer(bytes(blob), np.uint8).copy(), byte_id, slots
+
+
+def bpe_vocab_struct(spec, pointers, slots):
+    """ac_bpe_vocab over the four arrays' addresses (device or host), in build_bpe_tables order."""
+    return nv.ac_bpe_vocab(*pointers, slots, spec["cls_id"], spec["sep_id"], spec["pad_id"], 1 if spec["add_prefix_space"] else 0)
+
+
+# ---- what the two wrappers share ---------------------------------------------------------------------------------------
+def _pack_batch(blob, sizes, dev):
+    """Offsets and text in ONE host-to-device copy: [int32 offs[b + 1] | pad to 16 | text bytes | 64 zero bytes]."""
+    b = len(sizes)
+    head = (4 * (b + 1) + 15) // 16 * 16
+    buf = np.zeros(head + len(blob) + 64, np.uint8)
+    buf[:4 * (b + 1)].view(np.int32)[1:] = np.cumsum(sizes, dtype=np.int64).astype(np.int32)
+    buf[head:head + len(blob)] = np.frombuffer(blob, np.uint8)
+    d_buf = torch.from_numpy(buf).to(dev)
+    return d_buf[:4 * (b + 1)], d_buf[head:]
+
+
+def _splice_host_rows(hf, texts, host_rows, M, ids, mask, lens):
+    """The wrapped tokenizer itself for what the kernel does not cover, written over those rows of the batch."""
+    dev = ids.device
+    enc = hf([texts[i] for i in host_rows], max_length=M, truncation=True, padding="max_length", return_tensors="pt")
+    rows = torch.tensor(host_rows, dtype=torch.int64, device=dev)
+    ids[rows] = enc["input_ids"].to(dev)
+    mask[rows] = enc["attention_mask"].to(dev)
+    lens[rows] = enc["attention_mask"].sum(1).to(device=dev, dtype=torch.int32)
+
+
+class _DeviceTokenizer:
+    """Callable with the signature the classifier uses; returns device tensors.  A subclass sets `specials`, `_with_types`
+    (return token_type_ids), `_defers` (its kernel may mark a text not done: lens -1) and launches its kernel in `_encode`."""
+    _defers = False
+    _with_types = True
+
+    def __init__(self, hf_tokenizer, device=None):
+        self.hf = hf_tokenizer
+        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        self.device_texts = self.host_texts = 0          # routing statistics
+
+    def _device_ok(self, text, raw):
+        return len(raw) <= MAX_DEVICE_BYTES and raw.isascii() and not any(sp in text for sp in self.specials)
+
+    def __call__(self, texts, max_length=512, truncation=True, padding=True, return_tensors="pt", **kw):
+        if isinstance(texts, str):
+            texts = [texts]
+        if not truncation or not padding or return_tensors != "pt" or kw:
+            raise nv.NativeError(f"{type(self).__name__} supports the classifier's call only: truncation=True, padding=True, "
+                                 "return_tensors='pt'")
+        b = len(texts)
+        M = int(max_length)
+        dev = self.device
+        # common case first: one pass over the joined batch decides that every text is plain ASCII, short enough and free
+        # of special-token strings (a match across a text boundary only costs the slow path)
+        joined = "".join(texts)
+        if joined.isascii() and not any(sp in joined for sp in self.specials) and max(map(len, texts), default=0) <= MAX_DEVICE_BYTES:
+            on_dev = [True] * b
+            sizes = [len(t) for t in texts]
+            blob = joined.encode("ascii")
+        else:
+            raws = [t.encode("utf-8") for t in texts]
+            on_dev = [self._device_ok(t, r) for t, r in zip(texts, raws)]
+            sizes = [len(r) if ok else 0 for r, ok in zip(raws, on_dev)]
+            blob = b"".join(r for r, ok in zip(raws, on_dev) if ok)
+        ids = torch.empty((b, M), dtype=torch.int64, device=dev)
+        mask = torch.empty((b, M), dtype=torch.int64, device=dev)
+        lens = torch.empty(b, dtype=torch.int32, device=dev)
+        d_offs, d_text = _pack_batch(blob, sizes, dev)
+        with torch.cuda.device(dev):
+            self._encode(d_text, d_offs, b, M, ids, mask, lens)
+        host_rows = [i for i, ok in enumerate(on_dev) if not ok]
+        if host_rows:
+            _splice_host_rows(self.hf, texts, host_rows, M, ids, mask, lens)
+        # the one host sync: the encoder launch needs S (and, where the kernel may defer a text, whether it did: the minimum
+        # of lens travels with the maximum)
+        if not b:
+            S = 0
+        elif self._defers:
+            lo, S = torch.stack(torch.aminmax(lens)).tolist()
+            if lo < 0:                                   # rare: those texts go to the wrapped tokenizer after all
+                later = (lens < 0).nonzero().flatten().tolist()
+                _splice_host_rows(self.hf, texts, later, M, ids, mask, lens)
+                host_rows = host_rows + later
+                S = int(lens.max().item())
+        else:
+            S = int(lens.max().item())
+        self.device_texts += b - len(host_rows)
+        self.host_texts += len(host_rows)
+        ids_s, mask_s = ids[:, :S].contiguous(), mask[:, :S].contiguous()
+        if self._with_types:
+            return {"input_ids": ids_s, "token_type_ids": torch.zeros_like(ids_s), "attention_mask": mask_s}
+        return {"input_ids": ids_s, "attention_mask": mask_s}
+
+    # pass-through of what callers may read from the wrapped tokenizer
+    def __getattr__(self, name):
+        return getattr(self.hf, name)
+
+
+class HipWordPieceTokenizer(_DeviceTokenizer):
+    """BERT WordPiece on the device (ac_wordpiece_encode)."""
 
     def __init__(self, hf_tokenizer, device=None):
         nv.require_gpu()
         spec = _wordpiece_spec(hf_tokenizer)
         if spec is None:
             raise nv.NativeError("HipWordPieceTokenizer: not a BERT WordPiece tokenizer (BertNormalizer + BertPreTokenizer + WordPiece)")
-        self.hf = hf_tokenizer
-        self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
+        super().__init__(hf_tokenizer, device)
         vocab, self.lower, self.specials = spec
         self._build_table(vocab)
-        self.device_texts = self.host_texts = 0          # routing statistics
 
     # ---- vocabulary -> device hash table ---------------------------------------------------------------
     def _build_table(self, vocab):
@@ -104,69 +331,43 @@ class HipWordPieceTokenizer:
                                            1 if self.lower else 0)
         self.pad_id = vocab[hf.pad_token]
 
-    # ---- the call --------------------------------------------------------------------------------------
-    def _device_ok(self, text, raw):
-        return len(raw) <= MAX_DEVICE_BYTES and raw.isascii() and not any(sp in text for sp in self.specials)
+    def _encode(self, d_text, d_offs, b, M, ids, mask, lens):
+        nv.check(nv.lib().ac_wordpiece_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
+                                              nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_wordpiece_encode")
 
-    def __call__(self, texts, max_length=512, truncation=True, padding=True, return_tensors="pt", **kw):
-        if isinstance(texts, str):
-            texts = [texts]
-        if not truncation or not padding or return_tensors != "pt" or kw:
-            raise nv.NativeError("HipWordPieceTokenizer supports the classifier's call only: truncation=True, padding=True, "
-                                 "return_tensors='pt'")
-        b = len(texts)
-        M = int(max_length)
-        dev = self.device
-        # common case first: one pass over the joined batch decides that every text is plain ASCII, short enough and free
-        # of special-token strings (a match across a text boundary only costs the slow path)
-        joined = "".join(texts)
-        if joined.isascii() and not any(sp in joined for sp in self.specials) and max(map(len, texts), default=0) <= MAX_DEVICE_BYTES:
-            on_dev = [True] * b
-            sizes = [len(t) for t in texts]
-            blob = joined.encode("ascii")
-        else:
-            raws = [t.encode("utf-8") for t in texts]
-            on_dev = [self._device_ok(t, r) for t, r in zip(texts, raws)]
-            sizes = [len(r) if ok else 0 for r, ok in zip(raws, on_dev)]
-            blob = b"".join(r for r, ok in zip(raws, on_dev) if ok)
-        ids = torch.empty((b, M), dtype=torch.int64, device=dev)
-        mask = torch.empty((b, M), dtype=torch.int64, device=dev)
-        lens = torch.empty(b, dtype=torch.int32, device=dev)
-        # offsets and text travel in ONE host-to-device copy: [int32 offs[b + 1] | pad to 16 | text bytes | 64 zero bytes]
-        head = (4 * (b + 1) + 15) // 16 * 16
-        buf = np.zeros(head + len(blob) + 64, np.uint8)
-        buf[:4 * (b + 1)].view(np.int32)[1:] = np.cumsum(sizes, dtype=np.int64).astype(np.int32)
-        buf[head:head + len(blob)] = np.frombuffer(blob, np.uint8)
-        d_buf = torch.from_numpy(buf).to(dev)
-        d_offs, d_text = d_buf[:4 * (b + 1)], d_buf[head:]
-        with torch.cuda.device(dev):
-            nv.check(nv.lib().ac_wordpiece_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
-                                                  nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(dev)), "ac_wordpiece_encode")
-        host_rows = [i for i, ok in enumerate(on_dev) if not ok]
-        self.device_texts += b - len(host_rows)
-        self.host_texts += len(host_rows)
-        if host_rows:            # the wrapped tokenizer itself for what the kernel does not cover; spliced into the batch
-            enc = self.hf([texts[i] for i in host_rows], max_length=M, truncation=True, padding="max_length", return_tensors="pt")
-            rows = torch.tensor(host_rows, dtype=torch.int64, device=dev)
-            ids[rows] = enc["input_ids"].to(dev)
-            mask[rows] = enc["attention_mask"].to(dev)
-            lens[rows] = enc["attention_mask"].sum(1).to(device=dev, dtype=torch.int32)
-        S = int(lens.max().item()) if b else 0                    # the one host sync: the encoder launch needs S
-        ids_s, mask_s = ids[:, :S].contiguous(), mask[:, :S].contiguous()
-        return {"input_ids": ids_s, "token_type_ids": torch.zeros_like(ids_s), "attention_mask": mask_s}
 
-    # pass-through of what callers may read from the wrapped tokenizer
-    def __getattr__(self, name):
-        return getattr(self.hf, name)
+class HipByteBPETokenizer(_DeviceTokenizer):
+    """GPT-2 byte-level BPE on the device (ac_bpe_encode): RoBERTa-style and ModernBERT-style tokenizers.  Returns the keys
+    the wrapped tokenizer returns (no token_type_ids where its model_input_names has none)."""
+    _defers = True
+
+    def __init__(self, hf_tokenizer, device=None):
+        nv.require_gpu()
+        spec = _bpe_spec(hf_tokenizer)
+        if spec is None:
+            raise nv.NativeError("HipByteBPETokenizer: not a byte-level BPE tokenizer this build reproduces (ByteLevel(use_regex) + BPE "
+                                 "behind RobertaProcessing or a <cls> $A <sep> template)")
+        super().__init__(hf_tokenizer, device)
+        self.specials, self._with_types, self.pad_id = spec["specials"], spec["token_type_ids"], spec["pad_id"]
+        keys, entries, blob, byte_id, slots = build_bpe_tables(spec)
+        self._t = [torch.from_numpy(a).to(self.device) for a in (keys.view(np.int64), entries, blob, byte_id)]
+        self.vocab = bpe_vocab_struct(spec, [t.data_ptr() for t in self._t], slots)
+
+    def _encode(self, d_text, d_offs, b, M, ids, mask, lens):
+        nv.check(nv.lib().ac_bpe_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
+                                        nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_bpe_encode")
 
 
 def maybe_device_tokenizer(hf_tokenizer, device):
-    """HipWordPieceTokenizer around `hf_tokenizer` when it is a BERT WordPiece tokenizer, else the tokenizer unchanged."""
-    if hf_tokenizer is None or isinstance(hf_tokenizer, HipWordPieceTokenizer):
+    """HipWordPieceTokenizer around a BERT WordPiece tokenizer, HipByteBPETokenizer around a GPT-2 byte-level BPE tokenizer,
+    anything else unchanged."""
+    if hf_tokenizer is None or isinstance(hf_tokenizer, _DeviceTokenizer):
         return hf_tokenizer
     try:
-        if _wordpiece_spec(hf_tokenizer) is None:
-            return hf_tokenizer
-        return HipWordPieceTokenizer(hf_tokenizer, device)
+        if _wordpiece_spec(hf_tokenizer) is not None:
+            return HipWordPieceTokenizer(hf_tokenizer, device)
+        if _bpe_spec(hf_tokenizer) is not None:
+            return HipByteBPETokenizer(hf_tokenizer, device)
+        return hf_tokenizer
     except Exception:
         return hf_tokenizer

@@ -1197,6 +1197,43 @@ int ac_wordpiece_encode(const uint8_t* d_text, const int32_t* d_offsets, int b,
                         const ac_wordpiece_vocab* vocab, int max_length,
                         int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
 
+/* A GPT-2 byte-level BPE vocabulary (RoBERTa-style / ModernBERT-style tokenizers: tokenizers ByteLevel(use_regex) + BPE) with
+ * every vocabulary string turned back into raw bytes (ByteLevel's byte <-> unicode map inverted).  The merges are an
+ * open-addressing hash table, built by the host wrapper and filled to at most half: slot of a merge = (h ^ (h >> 32)) &
+ * (slots - 1), linear probing, h = ac_bpe_pair_hash(left bytes, right bytes).  A merge is the PAIR, not the concatenation:
+ * ("a","bc") and ("ab","c") are two merges; a hit is verified byte-exact including the split point.
+ * Device pointers for ac_bpe_encode, host pointers for ac_bpe_encode_host.  (ac_version() >= 10) */
+typedef struct ac_bpe_vocab {
+    const uint64_t* keys;       /* [slots] stored hash, 0 = empty slot */
+    const int32_t* entries;     /* [slots][4]: rank, id of the joined symbol, offset of left|right in blob, left_len | total_len << 16 */
+    const uint8_t* blob;        /* the merges' bytes, left and right back to back */
+    const int32_t* byte_id;     /* [256] id of each single-byte symbol */
+    int slots;                  /* power of two */
+    int cls_id, sep_id, pad_id; /* the post-processor's first / last token, the padding id */
+    int add_prefix_space;       /* 1 = 0x20 in front of a text unless it is empty or starts with 0x20 */
+} ac_bpe_vocab;
+
+/* FNV-1a 64 over the left bytes, one separator step (the value 0x100), the right bytes; never returns 0. */
+uint64_t ac_bpe_pair_hash(const uint8_t* left, int left_len, const uint8_t* right, int right_len);
+
+/*
+ * Tokenise b ASCII texts on the device exactly as a tokenizers ByteLevel(use_regex = true) + BPE pipeline does (GPT-2
+ * pattern, merges of lowest rank first per pre-token, cls_id ... sep_id, truncation to max_length by tokens, padding with
+ * pad_id).  Arguments as ac_wordpiece_encode: each text <= 4096 bytes, ASCII only, free of literal special / added-token
+ * strings (the caller routes other texts to the host tokenizer).  One launch, no host synchronisation.
+ *   d_lens   int32 [b] sequence lengths incl. the two specials, or -1: NOT DONE -- the text holds a pre-token of more than
+ *            64 bytes, its rows of d_ids / d_mask are undefined and the caller tokenises it on the host
+ */
+int ac_bpe_encode(const uint8_t* d_text, const int32_t* d_offsets, int b,
+                  const ac_bpe_vocab* vocab, int max_length,
+                  int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
+
+/* The same algorithm (csrc/bpe_core.h) text by text on the CPU: host pointers everywhere, no GPU call, exact for every
+ * pre-token length (h_lens is never -1). */
+int ac_bpe_encode_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
+                       const ac_bpe_vocab* vocab, int max_length,
+                       int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,7 +85,8 @@ class ac_bert_weights(ctypes.Structure):
         "word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b",
         "qkv_w", "qkv_b", "ao_w", "ao_b", "ln1_g", "ln1_b",
         "ff1_w", "ff1_b", "ff2_w", "ff2_b", "ln2_g", "ln2_b",
-        "qkv_w3", "ao_w3", "ff1_w3", "ff2_w3", "qkv_wh", "ao_wh", "ff1_wh", "ff2_wh")]
+        "qkv_w3", "ao_w3", "ff1_w3", "ff2_w3", "qkv_wh", "ao_wh", "ff1_wh", "ff2_wh",
+        "attn_rel_bias")] + [("rel_span", c_int)]      # relative position bias table [heads][2 rel_span - 1] (ac_version() >= 11)
 
 
 # name -> (restype, argtypes); must list every symbol include/acamd.h declares

@@ -3,7 +3,8 @@
 Replaces `self.model(**inputs).last_hidden_state[:, 0, :]` + `F.normalize`
 (/root/reference/src/adaptive_classifier/classifier.py:1271-1275) for BERT-architecture, DistilBERT and RoBERTa-family
 checkpoints (bert-base-uncased, bert-large, e5-large-v2, bert-tiny, distilbert-base-*, roberta-*, xlm-roberta-* /
-multilingual-e5-*) with one native call,
+multilingual-e5-*) and MPNet (all-mpnet-base-v2, multi-qa-mpnet-*: the same block plus a relative position bias on the attention
+scores, `ac_bert_weights.attn_rel_bias`) with one native call,
 `ac_bert_encode_cls`, that writes unit-norm CLS vectors straight into a device buffer usable as the
 kNN query block (no device->host copy, cf. classifier.py:1282).  `pooling="mean"` (per encoder or per call) returns the
 attention-masked mean of the token states instead -- the embedding the MiniLM family, e5 and ModernBERT with
@@ -35,6 +36,31 @@ class _Cfg:
 
 
 ROBERTA_TYPES = ("roberta", "xlm-roberta", "camembert")
+
+# MPNet (modeling_mpnet.py): the BERT block under its own parameter names, no token types, RoBERTa-style positions, and one
+# relative position bias table shared by all layers (build_rel_bias)
+MPNET_NAMES = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
+               "type": None, "eln": "embeddings.LayerNorm",
+               "layer": "encoder.layer.{}.", "q": "attention.attn.q", "k": "attention.attn.k",
+               "v": "attention.attn.v", "ao": "attention.attn.o", "ln1": "attention.LayerNorm",
+               "ff1": "intermediate.dense", "ff2": "output.dense", "ln2": "output.LayerNorm"}
+MPNET_REL_BIAS = "encoder.relative_attention_bias.weight"
+
+
+def build_rel_bias(hf_mpnet, span=None):
+    """ac_bert_weights.attn_rel_bias of an MPNetModel: fp32 [heads, 2 span - 1] on the CPU, entry [h, d + span - 1] = the bias head h
+    adds to the score of (query i, key i + d).  span: the longest sequence the table serves (default: the position table's,
+    max_position_embeddings - (pad_token_id + 1)).  The buckets are the loaded model's own relative_position_bucket of the
+    distances -- it takes a logarithm in fp32 and truncates, and a restatement in another precision can land one bucket off."""
+    cfg = hf_mpnet.config
+    if span is None:
+        span = int(cfg.max_position_embeddings) - (int(cfg.pad_token_id) + 1)
+    if span < 1:
+        raise nv.NativeError(f"build_rel_bias: span {span} (max_position_embeddings {cfg.max_position_embeddings})")
+    rel = torch.arange(-(span - 1), span, dtype=torch.long)                    # key position - query position
+    bucket = hf_mpnet.encoder.relative_position_bucket(rel, num_buckets=int(cfg.relative_attention_num_buckets))
+    weight = hf_mpnet.encoder.relative_attention_bias.weight.detach().to(device="cpu", dtype=torch.float32)     # [buckets, heads]
+    return weight[bucket.to("cpu")].t().contiguous()
 
 SMALL_TOKENS = 32     # up to here ac_bert_encode_cls runs the whole forward as one persistent launch (bert_small.hip): no packing
 
@@ -81,43 +107,9 @@ class HipBertEncoder:
         self.arith = None                     # AC_GEMM_* or None
         self.ln_fusion = None                 # True / False / None; set to False by this encoder once an exchange gave up
         cfg = hf_bert.config
-        mtype = getattr(cfg, "model_type", "bert")
-        if mtype not in ("bert", "distilbert", "electra") + ROBERTA_TYPES:
-            raise nv.NativeError(f"HipBertEncoder covers BERT / DistilBERT / RoBERTa-family / ELECTRA encoders, got {mtype!r}")
-        if mtype == "electra" and getattr(cfg, "embedding_size", cfg.hidden_size) != cfg.hidden_size:
-            raise nv.NativeError("HipBertEncoder: ELECTRA with embedding_size != hidden_size (embeddings_project) is not covered")
+        mtype, names, pos_offset, act, (H, L, A, I), type_vocab, eps = self.architecture(cfg)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         sd = {k: v.detach() for k, v in hf_bert.state_dict().items()}
-        pos_offset = 0
-        if mtype in ("bert", "electra") or mtype in ROBERTA_TYPES:          # (ELECTRA's discriminator body is the BERT block, same names)
-            # RoBERTa / XLM-RoBERTa / CamemBERT (modeling_roberta.py): the BERT block under the same parameter names; positions
-            # count from padding_idx + 1 (create_position_ids_from_input_ids: cumsum over the non-pad tokens + padding_idx), which
-            # for right-padded inputs -- the only kind the classifier's tokenizer call produces -- is a constant row offset into
-            # the position table; padded positions never reach the CLS row.  One token type (ids are 0 or absent).
-            if mtype in ROBERTA_TYPES:
-                pos_offset = int(cfg.pad_token_id) + 1
-            if getattr(cfg, "position_embedding_type", "absolute") not in (None, "absolute"):
-                raise nv.NativeError("HipBertEncoder: only absolute position embeddings are supported")
-            act = cfg.hidden_act
-            H, L, A, I = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.intermediate_size
-            type_vocab, eps = cfg.type_vocab_size, float(cfg.layer_norm_eps)
-            names = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
-                     "type": "embeddings.token_type_embeddings.weight", "eln": "embeddings.LayerNorm",
-                     "layer": "encoder.layer.{}.", "q": "attention.self.query", "k": "attention.self.key",
-                     "v": "attention.self.value", "ao": "attention.output.dense", "ln1": "attention.output.LayerNorm",
-                     "ff1": "intermediate.dense", "ff2": "output.dense", "ln2": "output.LayerNorm"}
-        else:
-            # DistilBERT (modeling_distilbert.py): same block, no token-type embeddings -> a single zero row
-            act = cfg.activation
-            H, L, A, I = cfg.dim, cfg.n_layers, cfg.n_heads, cfg.hidden_dim
-            type_vocab, eps = 1, 1e-12
-            names = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
-                     "type": None, "eln": "embeddings.LayerNorm",
-                     "layer": "transformer.layer.{}.", "q": "attention.q_lin", "k": "attention.k_lin",
-                     "v": "attention.v_lin", "ao": "attention.out_lin", "ln1": "sa_layer_norm",
-                     "ff1": "ffn.lin1", "ff2": "ffn.lin2", "ln2": "output_layer_norm"}
-        if act not in ("gelu",):
-            raise nv.NativeError(f"HipBertEncoder: activation {act!r} unsupported (erf-GELU only)")
         self.config = _Cfg(H, getattr(cfg, "_name_or_path", ""))
         self.training = False
         self.ccfg = nv.ac_bert_config(H, L, A, I, cfg.vocab_size, cfg.max_position_embeddings - pos_offset, type_vocab, eps)
@@ -152,6 +144,12 @@ class HipBertEncoder:
         w.emb_ln_g = own(sd[names["eln"] + ".weight"]).data_ptr()
         w.emb_ln_b = own(sd[names["eln"] + ".bias"]).data_ptr()
         self._has_types = names["type"] is not None
+        if mtype == "mpnet":
+            # the relative position bias of every layer's scores, one table for the model (ac_bert_weights.attn_rel_bias): built
+            # once, owned here; its span is the position table's, so every S the native call admits is covered
+            self.rel_bias = own(build_rel_bias(hf_bert, self.ccfg.max_pos))
+            w.attn_rel_bias = self.rel_bias.data_ptr()
+            w.rel_span = self.ccfg.max_pos
         for k, tensors in per.items():
             arr = (ctypes.c_void_p * L)(*[t.data_ptr() for t in tensors])
             self._arrays[k] = arr             # host array of device pointers; must outlive the calls
@@ -177,6 +175,55 @@ class HipBertEncoder:
             except nv.NativeError as e:                           # (an explicit enable_f16x2() call raises; a process-wide
                 import logging                                    #  preference does not stop a model from loading)
                 logging.getLogger(__name__).warning("%s -- this encoder stays in bf16x3", e)
+
+    @staticmethod
+    def architecture(cfg):
+        """What the constructor reads off a transformers config, without a device: (model_type, parameter-name map, position
+        offset, activation, (H, L, heads, I), token-type rows, LayerNorm eps); NativeError for what the encoder does not cover."""
+        mtype = getattr(cfg, "model_type", "bert")
+        if mtype not in ("bert", "distilbert", "electra", "mpnet") + ROBERTA_TYPES:
+            raise nv.NativeError(f"HipBertEncoder covers BERT / DistilBERT / RoBERTa-family / ELECTRA / MPNet encoders, got {mtype!r}")
+        if mtype == "electra" and getattr(cfg, "embedding_size", cfg.hidden_size) != cfg.hidden_size:
+            raise nv.NativeError("HipBertEncoder: ELECTRA with embedding_size != hidden_size (embeddings_project) is not covered")
+        pos_offset = 0
+        if mtype == "mpnet":
+            # positions as in the RoBERTa family (create_position_ids_from_input_ids: padding_idx + 1 onwards, a constant row
+            # offset for right-padded inputs); no token types -> a single zero row, as for DistilBERT; the pooler is not read
+            pos_offset = int(cfg.pad_token_id) + 1
+            act = cfg.hidden_act
+            H, L, A, I = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.intermediate_size
+            type_vocab, eps = 1, float(cfg.layer_norm_eps)
+            names = MPNET_NAMES
+        elif mtype in ("bert", "electra") or mtype in ROBERTA_TYPES:        # (ELECTRA's discriminator body is the BERT block, same names)
+            # RoBERTa / XLM-RoBERTa / CamemBERT (modeling_roberta.py): the BERT block under the same parameter names; positions
+            # count from padding_idx + 1 (create_position_ids_from_input_ids: cumsum over the non-pad tokens + padding_idx), which
+            # for right-padded inputs -- the only kind the classifier's tokenizer call produces -- is a constant row offset into
+            # the position table; padded positions never reach the CLS row.  One token type (ids are 0 or absent).
+            if mtype in ROBERTA_TYPES:
+                pos_offset = int(cfg.pad_token_id) + 1
+            if getattr(cfg, "position_embedding_type", "absolute") not in (None, "absolute"):
+                raise nv.NativeError("HipBertEncoder: only absolute position embeddings are supported")
+            act = cfg.hidden_act
+            H, L, A, I = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.intermediate_size
+            type_vocab, eps = cfg.type_vocab_size, float(cfg.layer_norm_eps)
+            names = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
+                     "type": "embeddings.token_type_embeddings.weight", "eln": "embeddings.LayerNorm",
+                     "layer": "encoder.layer.{}.", "q": "attention.self.query", "k": "attention.self.key",
+                     "v": "attention.self.value", "ao": "attention.output.dense", "ln1": "attention.output.LayerNorm",
+                     "ff1": "intermediate.dense", "ff2": "output.dense", "ln2": "output.LayerNorm"}
+        else:
+            # DistilBERT (modeling_distilbert.py): same block, no token-type embeddings -> a single zero row
+            act = cfg.activation
+            H, L, A, I = cfg.dim, cfg.n_layers, cfg.n_heads, cfg.hidden_dim
+            type_vocab, eps = 1, 1e-12
+            names = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
+                     "type": None, "eln": "embeddings.LayerNorm",
+                     "layer": "transformer.layer.{}.", "q": "attention.q_lin", "k": "attention.k_lin",
+                     "v": "attention.v_lin", "ao": "attention.out_lin", "ln1": "sa_layer_norm",
+                     "ff1": "ffn.lin1", "ff2": "ffn.lin2", "ln2": "output_layer_norm"}
+        if act not in ("gelu",):
+            raise nv.NativeError(f"HipBertEncoder: activation {act!r} unsupported (erf-GELU only)")
+        return mtype, names, pos_offset, act, (H, L, A, I), type_vocab, eps
 
     # -- opt-in fp16x2 arithmetic of the token-row GEMMs (include/acamd.h: AC_GEMM_F16X2) ------
     F16X2_MAX_WEIGHT = 63.9                   # |w| 2^10 must stay below fp16's 65504
@@ -698,8 +745,10 @@ class HipModernBertEncoder:
 
 
 def make_encoder(hf_model, device=None, pooling="cls"):
-    """The native encoder for a transformers model: BERT / DistilBERT -> HipBertEncoder, ModernBERT ->
-    HipModernBertEncoder; anything else raises (there is no eager fallback).  pooling: the encoder's default ("cls" | "mean")."""
+    """The native encoder for a transformers model: BERT / DistilBERT / RoBERTa family / ELECTRA / MPNet -> HipBertEncoder,
+    ModernBERT -> HipModernBertEncoder; anything else raises (there is no eager fallback).  pooling: the encoder's default
+    ("cls" | "mean"; the sentence-transformers MPNet checkpoints -- all-mpnet-base-v2, multi-qa-mpnet-*, paraphrase-mpnet-* -- were
+    trained with "mean")."""
     mtype = getattr(hf_model.config, "model_type", "bert")
     if mtype == "modernbert":
         return HipModernBertEncoder(hf_model, device=device, pooling=pooling)

@@ -48,11 +48,17 @@ __device__ __forceinline__ void rope_rotate(f32x4 (&x)[8], const float* cs, cons
 // window >= 0 (sliding-window layers, masking_utils.py:141-151): key k is visible to query q iff |q - k| <= window.
 // FP32_OUT = false: the caller always passes ctx_planes (the fp32-row store path is not compiled: in a kernel whose operands sit
 // in LDS its generic destination pointer would become flat stores).
-template <bool ROPE, int DHT, bool FP32_OUT = true, bool K_AHEAD = true>
+// BIAS (MPNet's relative position bias, modeling_mpnet.py MPNetSelfAttention: scores / sqrt(d) + position_bias + mask): rel_bias is
+// this head's row of the [heads][2 span - 1] table, offset so that rel_bias[d] is the bias of (query i, key i + d), |d| < span,
+// S <= span.  It is added to the SCALED score (Q is pre-scaled: fl(q k scale) + bias, one rounding each as in the reference) before
+// the validity select and the maximum.  Clamped rows -- a query past S, a key past S -- take the table entry of the row they were
+// clamped to: the index stays inside (-S, S), the value is discarded with the row.  The 16 entries of a lane and tile are plain
+// global loads (the table is <= 49 KB for 12 heads x 1023 and lives in L2), issued ahead of the QK^T MFMAs like the next K fragment.
+template <bool ROPE, int DHT, bool FP32_OUT = true, bool K_AHEAD = true, bool BIAS = false>
 __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_, const float* vb, int64_t ld, int S, int qt, int lane,
                                                float scale, const int64_t* mask_row, const float* rope_cos, const float* rope_sin,
                                                int window, float* ctx_rows, int H, uint16_t* ctx_planes, int64_t rows, int64_t row0,
-                                               int headcol, int f16) {
+                                               int headcol, int f16, const float* rel_bias = nullptr) {
     // No implicit mul + add fusion in here: whether hipcc contracts `l * corr + psum` or packs two of them into v_pk_fma_f32
     // depends on the surrounding kernel, and the two routes must round alike (the one intended fma is written out).
 #pragma clang fp contract(off)
@@ -108,6 +114,15 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
             if constexpr (K_AHEAD) if (k0 + 32 < kend) load_k(k0 + 32);
             continue;
         }
+        float bv[BIAS ? 16 : 1];
+        if constexpr (BIAS) {
+            const int qc = qvalid ? qi : S - 1;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int kr = k0 + crow32(r, h); if (kr > S - 1) kr = S - 1;
+                bv[r] = rel_bias[kr - qc];
+            }
+        }
         f32x16 st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = 0.f;
@@ -123,7 +138,8 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
         for (int r = 0; r < 16; ++r) {
             bool ok = (vmask >> crow32(r, h)) & 1u;
             if (window >= 0) { const int dk = qi - (k0 + crow32(r, h)); ok = ok && dk <= window && -dk <= window; }
-            st[r] = ok ? st[r] : -INFINITY;
+            if constexpr (BIAS) st[r] = ok ? st[r] + bv[r] : -INFINITY;
+            else st[r] = ok ? st[r] : -INFINITY;
             cmax = fmaxf(cmax, st[r]);
         }
         cmax = fmaxf(cmax, __shfl_xor(cmax, 32));

@@ -363,13 +363,20 @@ using acattn::rope_rotate;
 // boundary_stride > 0 (packed mode, after the QKV GEMM with the fused attention epilogue, gemm_pipe.hip EPI_QKV_ATTN): grid z
 // walks the row-tile boundaries boundary_stride * (z + 1) instead of the sequences; the wave serves the sequence that STRADDLES
 // its boundary (whose rows two GEMM tiles share, so neither could finish it) and leaves when a sequence starts exactly there.
-template <bool ROPE, int DHT = 64>
+// BIAS (ac_bert_weights.attn_rel_bias, MPNet): REL = (const float* table, int span), the [heads][2 span - 1] relative position bias
+// added to the scaled scores (attention_core.h); positions count inside the sequence in every mode.  Without BIAS the pack is
+// empty and the kernel's arguments are the ones it always had.
+__device__ __forceinline__ const float* rel_bias_row(int head, const float* table, int span) {
+    return table + (int64_t)head * (2 * span - 1) + (span - 1);
+}
+template <bool ROPE, int DHT = 64, bool BIAS = false, typename... REL>
 __global__ __launch_bounds__(64) void attention_mfma_kernel(const float* qkv, const int64_t* mask, int S_, int H,
                                                             float scale, float* ctx, uint16_t* ctx_planes,
                                                             const float* rope_cos, const float* rope_sin,
                                                             int window, const int32_t* __restrict__ cu = nullptr,
                                                             int64_t total_rows = 0, int f16 = 0, int boundary_stride = 0,
-                                                            int nseq = 0) {
+                                                            int nseq = 0, REL... rel) {
+    static_assert(sizeof...(REL) == (BIAS ? 2 : 0), "the bias table and its span come with BIAS, and only then");
     const int lane = threadIdx.x;
     const int qt = blockIdx.x, head = blockIdx.y;
     int bi = blockIdx.z;
@@ -386,9 +393,15 @@ __global__ __launch_bounds__(64) void attention_mfma_kernel(const float* qkv, co
     if (qt * 32 >= S) return;                                        // (packed mode: short sequence)
     const float* base = qkv + row0 * ld + head * DHT;
     const int64_t rows = cu ? total_rows : (int64_t)gridDim.z * S_;
-    acattn::attention_tile<ROPE, DHT>(base, base + H, base + 2 * H, ld, S, qt, lane, scale, mask ? mask + (int64_t)bi * S_ : nullptr,
-                                      rope_cos, rope_sin, window, ctx ? ctx + row0 * H + head * DHT : nullptr, H, ctx_planes, rows,
-                                      row0, head * DHT, f16);
+    if constexpr (BIAS)
+        acattn::attention_tile<ROPE, DHT, true, true, true>(base, base + H, base + 2 * H, ld, S, qt, lane, scale,
+                                                            mask ? mask + (int64_t)bi * S_ : nullptr, rope_cos, rope_sin, window,
+                                                            ctx ? ctx + row0 * H + head * DHT : nullptr, H, ctx_planes, rows, row0,
+                                                            head * DHT, f16, rel_bias_row(head, rel...));
+    else
+        acattn::attention_tile<ROPE, DHT>(base, base + H, base + 2 * H, ld, S, qt, lane, scale, mask ? mask + (int64_t)bi * S_ : nullptr,
+                                          rope_cos, rope_sin, window, ctx ? ctx + row0 * H + head * DHT : nullptr, H, ctx_planes, rows,
+                                          row0, head * DHT, f16);
 }
 
 // Last layer: only the CLS query of every sequence feeds the output (classifier.py:1272), so its
@@ -396,12 +409,14 @@ __global__ __launch_bounds__(64) void attention_mfma_kernel(const float* qkv, co
 // lane = output dim for the P.V reduction; K tile rows padded to 65 floats (conflict-free column reads).
 // ROPE (ModernBERT): the CLS query is at position 0, whose rotation is the identity, so only the keys rotate;
 // window >= 0: only keys at positions <= window are visible to it.
-template <bool ROPE, int DHT = 64, int KTT = KT>     // KTT: keys per LDS tile (32 when no sequence is longer: half the LDS, twice the waves per CU)
+// BIAS / REL as in attention_mfma_kernel: the query is position 0, so key j takes the table entry of distance j.
+template <bool ROPE, int DHT = 64, int KTT = KT, bool BIAS = false, typename... REL>     // KTT: keys per LDS tile (32 when no sequence is longer: half the LDS, twice the waves per CU)
 __global__ __launch_bounds__(64) void attention_cls_kernel(const float* qkv, const int64_t* mask, int S_, int H,
                                                            float scale, float* ctx_cls, const float* rope_cos,
                                                            const float* rope_sin, int window,
                                                            const int32_t* __restrict__ cu = nullptr,
-                                                           const float* __restrict__ q_cls = nullptr) {
+                                                           const float* __restrict__ q_cls = nullptr, REL... rel) {
+    static_assert(sizeof...(REL) == (BIAS ? 2 : 0), "the bias table and its span come with BIAS, and only then");
     // q_cls: the b CLS queries as compact [b, H] rows (BERT's last layer projects Q for those rows only); else column block 0 of qkv
     static_assert(DHT == 64 || (DHT == 32 && !ROPE), "head dim 64, or 32 without RoPE");
     __shared__ float Ks[KTT][DHT + 1];
@@ -450,6 +465,7 @@ __global__ __launch_bounds__(64) void attention_cls_kernel(const float* qkv, con
 #pragma unroll 16
             for (int d = 0; d < DHT; ++d) sc = fmaf(qs[d], Ks[kl][d], sc);
         }
+        if constexpr (BIAS) sc = sc + rel_bias_row(head, rel...)[(k0 + lane < S) ? k0 + lane : S - 1];     // (scaled score + bias, then the mask)
         sc = valid ? sc : -INFINITY;
         float cmax = sc;
 #pragma unroll
@@ -766,6 +782,14 @@ int check_cfg(const ac_bert_config* c) {
     return AC_OK;
 }
 
+// ac_bert_weights.attn_rel_bias: the table covers distances below rel_span, so no sequence of the call may be longer
+int check_rel_bias(const ac_bert_weights* w, int S, const char* who) {
+    AC_REQUIRE(!w->attn_rel_bias || (w->rel_span >= 1 && S <= w->rel_span), AC_EINVAL,
+               "%s: S=%d exceeds rel_span=%d of the relative position bias table (attn_rel_bias needs 1 <= S <= rel_span)", who, S,
+               w->rel_span);
+    return AC_OK;
+}
+
 }  // namespace
 
 extern "C" int ac_bert_workspace(const ac_bert_config* cfg, int b, int S, size_t* bytes) {
@@ -863,7 +887,10 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
     // Self-attention inside the QKV GEMM's epilogue (gemm_pipe.hip EPI_QKV_ATTN): sequences laid out row after row (packed, or
     // unpacked without a mask = every sequence S real tokens), head dim 64, longest sequence <= 64, layers 0 .. L-2 on planes
     const int32_t* cu_at = cu;
-    const bool fuse_attn = pl && token_layers(c) > 0 && dh == 64 && (cu || !d_mask) && ac::qkv_attn_applies(T, H, c.heads, Smax);
+    // (a relative position bias is not in that epilogue: the QKV GEMM + the stand-alone attention serve such a call's token layers)
+    const float* rel = w->attn_rel_bias;
+    const int rel_span = w->rel_span;
+    const bool fuse_attn = !rel && pl && token_layers(c) > 0 && dh == 64 && (cu || !d_mask) && ac::qkv_attn_applies(T, H, c.heads, Smax);
     if (fuse_attn && !cu) {
         int32_t* cuw = (int32_t*)(base + ws.cu);
         hipLaunchKernelGGL(iota_cu_kernel, dim3((b + 256) / 256), dim3(256), 0, stream, cuw, b, S);
@@ -936,7 +963,16 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
             // (context rows are already in ctxp)
         } else if (last) {
             const float* qc = q_cls_only ? y : nullptr;
-            if (dh == 64 && Smax <= 32)
+            if (rel && dh == 64 && Smax <= 32)
+                hipLaunchKernelGGL((attention_cls_kernel<false, 64, 32, true>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
+                                   ctx, nullptr, nullptr, -1, cu, qc, rel, rel_span);
+            else if (rel && dh == 64)
+                hipLaunchKernelGGL((attention_cls_kernel<false, 64, KT, true>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
+                                   ctx, nullptr, nullptr, -1, cu, qc, rel, rel_span);
+            else if (rel)
+                hipLaunchKernelGGL((attention_cls_kernel<false, 32, KT, true>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
+                                   ctx, nullptr, nullptr, -1, cu, qc, rel, rel_span);
+            else if (dh == 64 && Smax <= 32)
                 hipLaunchKernelGGL((attention_cls_kernel<false, 64, 32>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
                                    ctx, nullptr, nullptr, -1, cu, qc);
             else if (dh == 64)
@@ -946,7 +982,15 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
                 hipLaunchKernelGGL((attention_cls_kernel<false, 32>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
                                    ctx, nullptr, nullptr, -1, cu, qc);
         } else {
-            if (dh == 64)
+            if (rel && dh == 64)
+                hipLaunchKernelGGL((attention_mfma_kernel<false, 64, true>), dim3((Smax + 31) / 32, c.heads, b), dim3(64), 0, stream, qkv,
+                                   d_mask, S, H, scale, ctx, lp ? ctxp : nullptr, nullptr, nullptr, -1, cu, (int64_t)T, (int)f16, 0, 0,
+                                   rel, rel_span);
+            else if (rel)
+                hipLaunchKernelGGL((attention_mfma_kernel<false, 32, true>), dim3((Smax + 31) / 32, c.heads, b), dim3(64), 0, stream, qkv,
+                                   d_mask, S, H, scale, ctx, lp ? ctxp : nullptr, nullptr, nullptr, -1, cu, (int64_t)T, (int)f16, 0, 0,
+                                   rel, rel_span);
+            else if (dh == 64)
                 hipLaunchKernelGGL((attention_mfma_kernel<false, 64>), dim3((Smax + 31) / 32, c.heads, b), dim3(64), 0, stream, qkv,
                                    d_mask, S, H, scale, ctx, lp ? ctxp : nullptr, nullptr, nullptr, -1, cu, (int64_t)T, (int)f16);
             else
@@ -1037,9 +1081,10 @@ extern "C" int ac_bert_encode_cls_opts(const ac_bert_config* cfg, const ac_bert_
     const ac::CallScope scope(cfg->gemm_arith_opt, cfg->ln_fusion_opt, cfg->one_launch_opt);
     AC_REQUIRE(w && d_ids && d_out && b > 0 && S >= 1 && S <= cfg->max_pos && ldo >= cfg->hidden, AC_EINVAL,
                "bert_encode_cls: bad arguments (b=%d S=%d max_pos=%d)", b, S, cfg->max_pos);
+    if ((rc = check_rel_bias(w, S, "bert_encode_cls"))) return rc;
     // a handful of token rows (single-query predict): every layer in ONE persistent launch (which ends in the CLS row: a
-    // mean-pooled call of this size goes layer by layer)
-    if (b * S <= 32 && !(opts & AC_BERT_LAYERED) && !pools_mean(cfg->pool_opt)) {
+    // mean-pooled call of this size goes layer by layer, and so does one with a relative position bias: bert_small.hip has none)
+    if (b * S <= 32 && !(opts & AC_BERT_LAYERED) && !pools_mean(cfg->pool_opt) && !w->attn_rel_bias) {
         const BertWs ws = bert_ws(*cfg, b, S);
         AC_REQUIRE(d_ws && ws_bytes >= ws.total, AC_EWORKSPACE, "bert_encode_cls: workspace %zu < %zu", ws_bytes, ws.total);
         rc = ac::bert_small_encode(*cfg, *w, d_ids, d_type_ids, d_mask, b, S, d_out, ldo, (char*)d_ws + ws.small, (hipStream_t)stream_);
@@ -1136,6 +1181,7 @@ extern "C" int ac_bert_encode_cls_unpad(const ac_bert_config* cfg, const ac_bert
     AC_REQUIRE(w && d_ids && d_mask && d_out && b > 0 && S >= 2 && S <= cfg->max_pos && ldo >= cfg->hidden && (int64_t)b * S > 32 &&
                    (int64_t)b * S < ((int64_t)1 << 30),
                AC_EINVAL, "bert_encode_cls_unpad: bad arguments (b=%d S=%d max_pos=%d; more than 32 token rows)", b, S, cfg->max_pos);
+    if ((rc = check_rel_bias(w, S, "bert_encode_cls_unpad"))) return rc;
     const ac_bert_config& c = *cfg;
     const BertWs ws = bert_ws(c, b, S);
     AC_REQUIRE(d_ws && ws_bytes >= ws.total, AC_EWORKSPACE, "bert_encode_cls_unpad: workspace %zu < %zu", ws_bytes, ws.total);
@@ -1202,6 +1248,7 @@ extern "C" int ac_bert_encode_cls_packed(const ac_bert_config* cfg, const ac_ber
     AC_REQUIRE(w && d_ids && d_out && d_cu && d_tok_src && b > 0 && S >= 1 && S <= cfg->max_pos && ldo >= cfg->hidden &&
                    total_tokens >= b && total_tokens <= b * S && longest >= 1 && longest <= S,
                AC_EINVAL, "bert_encode_cls_packed: bad arguments (b=%d S=%d tokens=%d longest=%d)", b, S, total_tokens, longest);
+    if ((rc = check_rel_bias(w, S, "bert_encode_cls_packed"))) return rc;
     return bert_encode_impl(cfg, w, d_ids, d_type_ids, nullptr, b, S, d_cu, d_tok_src, total_tokens, longest, d_out, ldo, d_ws,
                             ws_bytes, (hipStream_t)stream_);
 }

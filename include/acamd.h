@@ -935,6 +935,13 @@ typedef struct {
     const uint16_t* const* ao_wh;
     const uint16_t* const* ff1_wh;
     const uint16_t* const* ff2_wh;
+    /* Optional (NULL = none; ac_version() >= 11): additive relative-position bias of the self-attention, shared by all layers.
+     * fp32 [heads][2 * rel_span - 1]; entry [h][d + rel_span - 1] is added to the scaled score of (query i, key j = i + d)
+     * of head h before the key mask, positions counted inside the sequence.  MPNet: relative_attention_bias[bucket(j - i)][h].
+     * With a table the self-attention is never fused into the QKV GEMM and a call of <= 32 token rows runs layer by layer
+     * (used_one_launch = 0); every other route, arithmetic and pooling is as without one.  The workspace does not depend on it. */
+    const float* attn_rel_bias;
+    int rel_span;            /* a call with a table needs 1 <= S <= rel_span (else AC_EINVAL) */
 } ac_bert_weights;
 
 /*

@@ -80,12 +80,19 @@ class ac_bpe_vocab(ctypes.Structure):
                 ("cls_id", c_int), ("sep_id", c_int), ("pad_id", c_int), ("add_prefix_space", c_int)]
 
 
+class ac_bert_disentangled(ctypes.Structure):
+    _fields_ = [("pos_key", c_void_p), ("pos_query", c_void_p), ("rel_index", c_void_p),
+                ("rel_rows", c_int), ("rel_span", c_int), ("scale_factor", c_int),
+                ("scratch", c_void_p), ("scratch_bytes", c_size_t)]
+
+
 class ac_bert_weights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in (
         "word_emb", "pos_emb", "type_emb", "emb_ln_g", "emb_ln_b",
         "qkv_w", "qkv_b", "ao_w", "ao_b", "ln1_g", "ln1_b",
         "ff1_w", "ff1_b", "ff2_w", "ff2_b", "ln2_g", "ln2_b",
         "qkv_w3", "ao_w3", "ff1_w3", "ff2_w3", "qkv_wh", "ao_wh", "ff1_wh", "ff2_wh",
+        "attn_disentangled",                           # -> ac_bert_disentangled (host struct), DeBERTa (ac_version() >= 12)
         "attn_rel_bias")] + [("rel_span", c_int)]      # relative position bias table [heads][2 rel_span - 1] (ac_version() >= 11)
 
 
@@ -244,6 +251,7 @@ _SIGNATURES = {
                               c_void_p]),
     "ac_bpe_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p]),
     "ac_bert_workspace": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, ctypes.POINTER(c_size_t)]),
+    "ac_bert_disentangled_scratch": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_bert_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ac_bert_encode_cls_packed": (c_int, [ctypes.POINTER(ac_bert_config), ctypes.POINTER(ac_bert_weights), c_void_p, c_void_p,
                                           c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_size_t,

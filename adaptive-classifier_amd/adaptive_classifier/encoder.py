@@ -3,8 +3,9 @@
 Replaces `self.model(**inputs).last_hidden_state[:, 0, :]` + `F.normalize`
 (/root/reference/src/adaptive_classifier/classifier.py:1271-1275) for BERT-architecture, DistilBERT and RoBERTa-family
 checkpoints (bert-base-uncased, bert-large, e5-large-v2, bert-tiny, distilbert-base-*, roberta-*, xlm-roberta-* /
-multilingual-e5-*) and MPNet (all-mpnet-base-v2, multi-qa-mpnet-*: the same block plus a relative position bias on the attention
-scores, `ac_bert_weights.attn_rel_bias`) with one native call,
+multilingual-e5-*), MPNet (all-mpnet-base-v2, multi-qa-mpnet-*: the same block plus a relative position bias on the attention
+scores, `ac_bert_weights.attn_rel_bias`) and DeBERTa-v2/v3 (deberta-v3-*, mdeberta-v3-base: the same block under a disentangled
+attention, `ac_bert_weights.attn_disentangled`) with one native call,
 `ac_bert_encode_cls`, that writes unit-norm CLS vectors straight into a device buffer usable as the
 kNN query block (no device->host copy, cf. classifier.py:1282).  `pooling="mean"` (per encoder or per call) returns the
 attention-masked mean of the token states instead -- the embedding the MiniLM family, e5 and ModernBERT with
@@ -62,6 +63,82 @@ def build_rel_bias(hf_mpnet, span=None):
     weight = hf_mpnet.encoder.relative_attention_bias.weight.detach().to(device="cpu", dtype=torch.float32)     # [buckets, heads]
     return weight[bucket.to("cpu")].t().contiguous()
 
+
+# DeBERTa-v2/v3 (modeling_deberta_v2.py): the post-LayerNorm BERT block with its own projection names, no position table in the
+# released v3 checkpoints (position_biased_input=False) and often no token types; the attention is disentangled (build_disentangled)
+DEBERTA_NAMES = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
+                 "type": "embeddings.token_type_embeddings.weight", "eln": "embeddings.LayerNorm",
+                 "layer": "encoder.layer.{}.", "q": "attention.self.query_proj", "k": "attention.self.key_proj",
+                 "v": "attention.self.value_proj", "ao": "attention.output.dense", "ln1": "attention.output.LayerNorm",
+                 "ff1": "intermediate.dense", "ff2": "output.dense", "ln2": "output.LayerNorm"}
+DISENT_SCRATCH_FREE = 1 << 30     # a position-score scratch up to here never shrinks a chunk (encode_cls)
+
+
+def deberta_pos_att_type(cfg):
+    """config.pos_att_type as a tuple of terms (a list, or the "c2p|p2c" string of older configs; None = none)."""
+    t = getattr(cfg, "pos_att_type", None)
+    if t is None:
+        return ()
+    if isinstance(t, str):
+        t = [x.strip() for x in t.lower().split("|") if x.strip()]
+    return tuple(t)
+
+
+def deberta_rel_span(cfg):
+    """The longest sequence a DeBERTa model's relative positions cover: max_relative_positions if >= 1, else max_position_embeddings."""
+    m = int(getattr(cfg, "max_relative_positions", -1))
+    return m if m >= 1 else int(cfg.max_position_embeddings)
+
+
+def build_disentangled(hf_model, span=None):
+    """ac_bert_disentangled of a DebertaV2Model, on the CPU: (pos_key, pos_query, rel_index, scale_factor).
+    pos_key[l] / pos_query[l]: fp32 [2 att_span, H] = the layer's key / query projection (pos_key_proj / pos_query_proj without
+    share_att_key), with bias, of the relative-position embeddings (LayerNorm'd when norm_rel_ebd has layer_norm) -- evaluated in
+    fp64 and rounded once; a term pos_att_type lacks is an all-zero table.  rel_index: int32 [2 span - 1], entry [d + span - 1] =
+    the table row of (query i, key i + d) = bucket(i - j) + att_span, read off the model's own build_relative_position (its
+    logarithm is taken in fp32 and rounded up: a restatement can land one bucket off).  scale_factor = 1 + the number of terms.
+    span: the longest sequence served (default deberta_rel_span(config))."""
+    import sys
+    cfg = hf_model.config
+    enc = hf_model.encoder
+    span = deberta_rel_span(cfg) if span is None else int(span)
+    if span < 1:
+        raise nv.NativeError(f"build_disentangled: span {span}")
+    terms = deberta_pos_att_type(cfg)
+    att0 = enc.layer[0].attention.self
+    att_span = int(att0.pos_ebd_size)
+    H = int(cfg.hidden_size)
+    with torch.no_grad():
+        rel = enc.rel_embeddings.weight.detach().to("cpu", torch.float64)[:2 * att_span]
+        if "layer_norm" in enc.norm_rel_ebd:
+            rel = torch.nn.functional.layer_norm(rel, (H,), enc.LayerNorm.weight.detach().to("cpu", torch.float64),
+                                                 enc.LayerNorm.bias.detach().to("cpu", torch.float64), enc.LayerNorm.eps)
+        pos_key, pos_query = [], []
+        for layer in enc.layer:
+            att = layer.attention.self
+            for term, shared, own_name, dst in (("c2p", "key_proj", "pos_key_proj", pos_key), ("p2c", "query_proj", "pos_query_proj", pos_query)):
+                if term not in terms:
+                    dst.append(torch.zeros(2 * att_span, H, dtype=torch.float32))
+                    continue
+                proj = getattr(att, shared if att.share_att_key else own_name)
+                t = rel @ proj.weight.detach().to("cpu", torch.float64).t()
+                if proj.bias is not None:
+                    t = t + proj.bias.detach().to("cpu", torch.float64)
+                dst.append(t.to(torch.float32).contiguous())
+        probe = torch.zeros(span, 1)
+        rp = sys.modules[type(hf_model).__module__].build_relative_position(
+            probe, probe, bucket_size=int(att0.position_buckets), max_position=int(att0.max_relative_positions))[0].to("cpu")
+    i = torch.arange(span)
+    d = torch.arange(-(span - 1), span)                              # key position - query position
+    bucket = torch.where(d >= 0, rp[0, d.clamp(min=0)], rp[(-d).clamp(min=0), 0])      # bucket(i - j) = bucket(-d)
+    if not torch.equal(rp, bucket[(i[None, :] - i[:, None]) + span - 1]):
+        raise nv.NativeError("build_disentangled: the model's relative positions are not a function of i - j")
+    rel_index = (bucket + att_span).to(torch.int32).contiguous()
+    if int(rel_index.min()) < 0 or int(rel_index.max()) >= 2 * att_span:
+        raise nv.NativeError(f"build_disentangled: span {span} reaches outside the {2 * att_span} relative-position rows")
+    return pos_key, pos_query, rel_index, 1 + sum(1 for t in ("c2p", "p2c") if t in terms)
+
+
 SMALL_TOKENS = 32     # up to here ac_bert_encode_cls runs the whole forward as one persistent launch (bert_small.hip): no packing
 
 ARITH_MODES = {"f32": nv.AC_GEMM_F32, "bf16x3": nv.AC_GEMM_BF16X3, "f16x2": nv.AC_GEMM_F16X2}
@@ -112,7 +189,11 @@ class HipBertEncoder:
         sd = {k: v.detach() for k, v in hf_bert.state_dict().items()}
         self.config = _Cfg(H, getattr(cfg, "_name_or_path", ""))
         self.training = False
-        self.ccfg = nv.ac_bert_config(H, L, A, I, cfg.vocab_size, cfg.max_position_embeddings - pos_offset, type_vocab, eps)
+        max_pos = cfg.max_position_embeddings - pos_offset
+        if mtype == "deberta-v2":
+            # S <= rel_span is the family's rule; without a position table nothing else bounds S
+            max_pos = min(max_pos, deberta_rel_span(cfg)) if names["pos"] else deberta_rel_span(cfg)
+        self.ccfg = nv.ac_bert_config(H, L, A, I, cfg.vocab_size, max_pos, type_vocab, eps)
 
         def dev(t):
             return t.to(device=self.device, dtype=torch.float32).contiguous()
@@ -139,7 +220,7 @@ class HipBertEncoder:
         self._arrays = {}
         w = nv.ac_bert_weights()
         w.word_emb = own(sd[names["word"]]).data_ptr()
-        w.pos_emb = own(sd[names["pos"]][pos_offset:]).data_ptr()
+        w.pos_emb = own(sd[names["pos"]][pos_offset:] if names["pos"] else torch.zeros(max_pos, H)).data_ptr()
         w.type_emb = own(sd[names["type"]] if names["type"] else torch.zeros(1, H)).data_ptr()
         w.emb_ln_g = own(sd[names["eln"] + ".weight"]).data_ptr()
         w.emb_ln_b = own(sd[names["eln"] + ".bias"]).data_ptr()
@@ -150,6 +231,27 @@ class HipBertEncoder:
             self.rel_bias = own(build_rel_bias(hf_bert, self.ccfg.max_pos))
             w.attn_rel_bias = self.rel_bias.data_ptr()
             w.rel_span = self.ccfg.max_pos
+        self._dis = None
+        if mtype == "deberta-v2":
+            # the position terms of the disentangled attention (ac_bert_weights.attn_disentangled): PK_l / PQ_l and the index table
+            # are functions of the weights, built once; the scratch of the position scores is sized per call (encode_cls)
+            pos_key, pos_query, rel_index, scale_factor = build_disentangled(hf_bert, self.ccfg.max_pos)
+            rows = pos_key[0].shape[0]
+            if int(rel_index.min()) < 0 or int(rel_index.max()) >= rows:       # (the native call cannot look into device memory)
+                raise nv.NativeError(f"HipBertEncoder: rel_index outside [0, {rows})")
+            d = nv.ac_bert_disentangled()
+            self.pos_key, self.pos_query = [own(t) for t in pos_key], [own(t) for t in pos_query]
+            self.rel_index = rel_index.to(self.device)
+            self._keep.append(self.rel_index)
+            for k, tensors in (("pos_key", self.pos_key), ("pos_query", self.pos_query)):
+                arr = (ctypes.c_void_p * L)(*[t.data_ptr() for t in tensors])
+                self._arrays[k] = arr
+                setattr(d, k, ctypes.cast(arr, ctypes.c_void_p).value)
+            d.rel_index = self.rel_index.data_ptr()
+            d.rel_rows, d.rel_span, d.scale_factor = rows, self.ccfg.max_pos, scale_factor
+            self._dis = d                     # host struct; must outlive the calls
+            self._dis_scratch = None
+            w.attn_disentangled = ctypes.addressof(d)
         for k, tensors in per.items():
             arr = (ctypes.c_void_p * L)(*[t.data_ptr() for t in tensors])
             self._arrays[k] = arr             # host array of device pointers; must outlive the calls
@@ -181,12 +283,42 @@ class HipBertEncoder:
         """What the constructor reads off a transformers config, without a device: (model_type, parameter-name map, position
         offset, activation, (H, L, heads, I), token-type rows, LayerNorm eps); NativeError for what the encoder does not cover."""
         mtype = getattr(cfg, "model_type", "bert")
-        if mtype not in ("bert", "distilbert", "electra", "mpnet") + ROBERTA_TYPES:
-            raise nv.NativeError(f"HipBertEncoder covers BERT / DistilBERT / RoBERTa-family / ELECTRA / MPNet encoders, got {mtype!r}")
+        if mtype == "deberta":
+            raise nv.NativeError("HipBertEncoder: model_type 'deberta' (DeBERTa v1) is a different block -- a fused in_proj without "
+                                 "key bias, its own LayerNorm, unbucketed positions -- and is not covered; DeBERTa-v2/v3 "
+                                 "(model_type 'deberta-v2') is")
+        if mtype not in ("bert", "distilbert", "electra", "mpnet", "deberta-v2") + ROBERTA_TYPES:
+            raise nv.NativeError("HipBertEncoder covers BERT / DistilBERT / RoBERTa-family / ELECTRA / MPNet / DeBERTa-v2/v3 "
+                                 f"encoders, got {mtype!r}")
         if mtype == "electra" and getattr(cfg, "embedding_size", cfg.hidden_size) != cfg.hidden_size:
             raise nv.NativeError("HipBertEncoder: ELECTRA with embedding_size != hidden_size (embeddings_project) is not covered")
         pos_offset = 0
-        if mtype == "mpnet":
+        if mtype == "deberta-v2":
+            # the post-LayerNorm BERT block; what the disentangled attention needs is checked here, key by key (there is no
+            # other route for a model that fails one).  Positions count from 0; a model without a position / type table gets
+            # zero tables (x + 0 is exact), so the embedding kernel is the one every family runs
+            H, L, A, I = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.intermediate_size
+            if getattr(cfg, "embedding_size", None) not in (None, H):
+                raise nv.NativeError(f"HipBertEncoder: DeBERTa with embedding_size {cfg.embedding_size} != hidden_size {H} (embed_proj) is not covered")
+            if int(getattr(cfg, "conv_kernel_size", 0) or 0) > 0:
+                raise nv.NativeError(f"HipBertEncoder: DeBERTa with conv_kernel_size {cfg.conv_kernel_size} > 0 (the convolution after "
+                                     "layer 0: deberta-v2-xlarge / -xxlarge) is not covered")
+            if not getattr(cfg, "relative_attention", False):
+                raise nv.NativeError("HipBertEncoder: DeBERTa with relative_attention false is not covered")
+            bad = [t for t in deberta_pos_att_type(cfg) if t not in ("c2p", "p2c")]
+            if bad:
+                raise nv.NativeError(f"HipBertEncoder: DeBERTa pos_att_type entry {bad[0]!r} is not covered (c2p / p2c only)")
+            if getattr(cfg, "attention_head_size", H // A) != 64 or H != A * 64:
+                raise nv.NativeError(f"HipBertEncoder: DeBERTa needs head dimension 64, got hidden_size {H} / num_attention_heads {A}"
+                                     f" (attention_head_size {getattr(cfg, 'attention_head_size', H // A)})")
+            act = cfg.hidden_act
+            type_vocab, eps = max(1, int(cfg.type_vocab_size)), float(cfg.layer_norm_eps)
+            names = dict(DEBERTA_NAMES)
+            if int(cfg.type_vocab_size) <= 0:
+                names["type"] = None
+            if not getattr(cfg, "position_biased_input", True):
+                names["pos"] = None
+        elif mtype == "mpnet":
             # positions as in the RoBERTa family (create_position_ids_from_input_ids: padding_idx + 1 onwards, a constant row
             # offset for right-padded inputs); no token types -> a single zero row, as for DistilBERT; the pooler is not read
             pos_offset = int(cfg.pad_token_id) + 1
@@ -331,6 +463,13 @@ class HipBertEncoder:
             got = cache[(b, S)] = need.value
         return got
 
+    def disentangled_scratch_bytes(self, b, S):
+        """ac_bert_disentangled_scratch for this encoder's tables (DeBERTa only)."""
+        need = ctypes.c_size_t(0)
+        nv.check(nv.lib().ac_bert_disentangled_scratch(ctypes.byref(self.ccfg), self._dis.rel_rows, b, S, ctypes.byref(need)),
+                 "ac_bert_disentangled_scratch")
+        return need.value
+
     def encode_cls(self, input_ids, token_type_ids=None, attention_mask=None, out=None, verify=True, force_layered=False,
                    verify_small=None, arith=None, pooling=None):
         """int64 [b, S] ids (+ optional type ids / mask) -> unit-norm embeddings [b, H] on device.
@@ -364,6 +503,16 @@ class HipBertEncoder:
             out = torch.empty((b, H), dtype=torch.float32, device=self.device)
         # activations cost ~64 KB per token; very large batches go through in row chunks of <= MAX_TOKENS tokens
         cb = b if b * S <= MAX_TOKENS else max(1, MAX_TOKENS // S)
+        if self._dis is not None:
+            # the position scores of a chunk (ac_bert_disentangled_scratch) grow with S^2: a chunk whose scratch would exceed
+            # both its own workspace and DISENT_SCRATCH_FREE shrinks until it does not; the buffer is kept like the workspace
+            cb = min(b, cb)
+            while cb > 1 and self.disentangled_scratch_bytes(cb, S) > max(self.workspace_bytes(cb, S), DISENT_SCRATCH_FREE):
+                cb = (cb + 1) // 2
+            need_s = self.disentangled_scratch_bytes(cb, S)
+            if self._dis_scratch is None or self._dis_scratch.numel() < need_s:
+                self._dis_scratch = torch.empty(need_s, dtype=torch.uint8, device=self.device)
+            self._dis.scratch, self._dis.scratch_bytes = self._dis_scratch.data_ptr(), self._dis_scratch.numel()
         need = self.workspace_bytes(min(b, cb), S)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
@@ -745,7 +894,8 @@ class HipModernBertEncoder:
 
 
 def make_encoder(hf_model, device=None, pooling="cls"):
-    """The native encoder for a transformers model: BERT / DistilBERT / RoBERTa family / ELECTRA / MPNet -> HipBertEncoder,
+    """The native encoder for a transformers model: BERT / DistilBERT / RoBERTa family / ELECTRA / MPNet / DeBERTa-v2/v3
+    (microsoft/deberta-v3-*, mdeberta-v3-base and checkpoints fine-tuned from them) -> HipBertEncoder,
     ModernBERT -> HipModernBertEncoder; anything else raises (there is no eager fallback).  pooling: the encoder's default
     ("cls" | "mean"; the sentence-transformers MPNet checkpoints -- all-mpnet-base-v2, multi-qa-mpnet-*, paraphrase-mpnet-* -- were
     trained with "mean")."""

@@ -54,15 +54,30 @@ __device__ __forceinline__ void rope_rotate(f32x4 (&x)[8], const float* cs, cons
 // the validity select and the maximum.  Clamped rows -- a query past S, a key past S -- take the table entry of the row they were
 // clamped to: the index stays inside (-S, S), the value is discarded with the row.  The 16 entries of a lane and tile are plain
 // global loads (the table is <= 49 KB for 12 heads x 1023 and lives in L2), issued ahead of the QK^T MFMAs like the next K fragment.
-template <bool ROPE, int DHT, bool FP32_OUT = true, bool K_AHEAD = true, bool BIAS = false>
+// DISENT (DeBERTa's disentangled attention, modeling_deberta_v2.py DisentangledSelfAttention; ac_bert_disentangled): the content-to-
+// position and position-to-content terms of every (token row, distance) were computed ahead by position_scores_kernel (bert.hip),
+// already multiplied by the score scale.  c2p / p2c point at the entry (row 0 of the sequence, this head, distance 0); rows are
+// pos_ld floats apart and entry [d] of a row belongs to the pair (query i, key i + d).  The score of (qi, kr) gains
+// c2p[qi][kr - qi] + p2c[kr][kr - qi] -- the sum of the two first, then onto the scaled score, as the model adds rel_att -- where
+// BIAS adds its table entry.  A lane's 16 c2p entries of a tile lie inside its own row; the p2c entries the 32 lanes of one register
+// read are adjacent floats of one key row.  Clamped rows index like the row they were clamped to, so every read stays inside the
+// 2 S - 1 distances of the sequence.
+struct PosScores {
+    const float* c2p;     // [rows][heads][ld]: q_t . PK[idx(d)] * scale at [t][h][d + span - 1]
+    const float* p2c;     // the same shape: k_t . PQ[idx(d)] * scale
+    int ld, span;         // floats per (row, head) (>= 2 span - 1), span = the call's longest sequence
+};
+template <bool ROPE, int DHT, bool FP32_OUT = true, bool K_AHEAD = true, bool BIAS = false, bool DISENT = false>
 __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_, const float* vb, int64_t ld, int S, int qt, int lane,
                                                float scale, const int64_t* mask_row, const float* rope_cos, const float* rope_sin,
                                                int window, float* ctx_rows, int H, uint16_t* ctx_planes, int64_t rows, int64_t row0,
-                                               int headcol, int f16, const float* rel_bias = nullptr) {
+                                               int headcol, int f16, const float* rel_bias = nullptr, const float* c2p = nullptr,
+                                               const float* p2c = nullptr, int64_t pos_ld = 0) {
     // No implicit mul + add fusion in here: whether hipcc contracts `l * corr + psum` or packs two of them into v_pk_fma_f32
     // depends on the surrounding kernel, and the two routes must round alike (the one intended fma is written out).
 #pragma clang fp contract(off)
     static_assert(DHT == 64 || (DHT == 32 && !ROPE), "head dim 64, or 32 without RoPE");
+    static_assert(!(BIAS && DISENT), "one source of position terms");
     constexpr int NKB = DHT / 8;                                     // 8-dim k-blocks of the QK^T product
     const int j = lane & 31, h = lane >> 5;
     const int qi = qt * 32 + j;
@@ -114,13 +129,23 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
             if constexpr (K_AHEAD) if (k0 + 32 < kend) load_k(k0 + 32);
             continue;
         }
-        float bv[BIAS ? 16 : 1];
+        float bv[(BIAS || DISENT) ? 16 : 1];
         if constexpr (BIAS) {
             const int qc = qvalid ? qi : S - 1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 int kr = k0 + crow32(r, h); if (kr > S - 1) kr = S - 1;
                 bv[r] = rel_bias[kr - qc];
+            }
+        }
+        if constexpr (DISENT) {
+            const int qc = qvalid ? qi : S - 1;
+            const float* cq = c2p + (int64_t)qc * pos_ld - qc;       // cq[kr] = c2p[qc][kr - qc]
+            const float* pk = p2c - qc;                              // pk[kr * pos_ld + kr] = p2c[kr][kr - qc]
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int kr = k0 + crow32(r, h); if (kr > S - 1) kr = S - 1;
+                bv[r] = cq[kr] + pk[(int64_t)kr * pos_ld + kr];
             }
         }
         f32x16 st;
@@ -138,7 +163,7 @@ __device__ __forceinline__ void attention_tile(const float* qb, const float* kb_
         for (int r = 0; r < 16; ++r) {
             bool ok = (vmask >> crow32(r, h)) & 1u;
             if (window >= 0) { const int dk = qi - (k0 + crow32(r, h)); ok = ok && dk <= window && -dk <= window; }
-            if constexpr (BIAS) st[r] = ok ? st[r] + bv[r] : -INFINITY;
+            if constexpr (BIAS || DISENT) st[r] = ok ? st[r] + bv[r] : -INFINITY;
             else st[r] = ok ? st[r] : -INFINITY;
             cmax = fmaxf(cmax, st[r]);
         }

@@ -369,6 +369,12 @@ using acattn::rope_rotate;
 __device__ __forceinline__ const float* rel_bias_row(int head, const float* table, int span) {
     return table + (int64_t)head * (2 * span - 1) + (span - 1);
 }
+// Disentangled attention (ac_bert_weights.attn_disentangled, DeBERTa): REL = (acattn::PosScores), the two position-score blocks
+// position_scores_kernel wrote for this layer; BIAS stays false.  The pack is what tells the variants apart, so the kernels keep
+// their template parameters and every instantiation without position scores its name and its instructions.
+template <typename... REL> struct is_pos_scores { static constexpr bool value = false; };
+template <> struct is_pos_scores<acattn::PosScores> { static constexpr bool value = true; };
+__device__ __forceinline__ acattn::PosScores pos_scores_of(acattn::PosScores p) { return p; }
 template <bool ROPE, int DHT = 64, bool BIAS = false, typename... REL>
 __global__ __launch_bounds__(64) void attention_mfma_kernel(const float* qkv, const int64_t* mask, int S_, int H,
                                                             float scale, float* ctx, uint16_t* ctx_planes,
@@ -376,7 +382,9 @@ __global__ __launch_bounds__(64) void attention_mfma_kernel(const float* qkv, co
                                                             int window, const int32_t* __restrict__ cu = nullptr,
                                                             int64_t total_rows = 0, int f16 = 0, int boundary_stride = 0,
                                                             int nseq = 0, REL... rel) {
-    static_assert(sizeof...(REL) == (BIAS ? 2 : 0), "the bias table and its span come with BIAS, and only then");
+    constexpr bool DISENT = is_pos_scores<REL...>::value;
+    static_assert(DISENT ? (!BIAS && !ROPE && DHT == 64) : sizeof...(REL) == (BIAS ? 2 : 0),
+                  "the bias table and its span come with BIAS, the position scores without it, and nothing else");
     const int lane = threadIdx.x;
     const int qt = blockIdx.x, head = blockIdx.y;
     int bi = blockIdx.z;
@@ -398,7 +406,14 @@ __global__ __launch_bounds__(64) void attention_mfma_kernel(const float* qkv, co
                                                             mask ? mask + (int64_t)bi * S_ : nullptr, rope_cos, rope_sin, window,
                                                             ctx ? ctx + row0 * H + head * DHT : nullptr, H, ctx_planes, rows, row0,
                                                             head * DHT, f16, rel_bias_row(head, rel...));
-    else
+    else if constexpr (DISENT) {
+        const acattn::PosScores ps = pos_scores_of(rel...);
+        const int64_t hl = H / DHT, off = (row0 * hl + head) * ps.ld + ps.span - 1;
+        acattn::attention_tile<ROPE, DHT, true, true, false, true>(base, base + H, base + 2 * H, ld, S, qt, lane, scale,
+                                                                   mask ? mask + (int64_t)bi * S_ : nullptr, rope_cos, rope_sin, window,
+                                                                   ctx ? ctx + row0 * H + head * DHT : nullptr, H, ctx_planes, rows, row0,
+                                                                   head * DHT, f16, nullptr, ps.c2p + off, ps.p2c + off, hl * ps.ld);
+    } else
         acattn::attention_tile<ROPE, DHT>(base, base + H, base + 2 * H, ld, S, qt, lane, scale, mask ? mask + (int64_t)bi * S_ : nullptr,
                                           rope_cos, rope_sin, window, ctx ? ctx + row0 * H + head * DHT : nullptr, H, ctx_planes, rows,
                                           row0, head * DHT, f16);
@@ -416,7 +431,9 @@ __global__ __launch_bounds__(64) void attention_cls_kernel(const float* qkv, con
                                                            const float* rope_sin, int window,
                                                            const int32_t* __restrict__ cu = nullptr,
                                                            const float* __restrict__ q_cls = nullptr, REL... rel) {
-    static_assert(sizeof...(REL) == (BIAS ? 2 : 0), "the bias table and its span come with BIAS, and only then");
+    constexpr bool DISENT = is_pos_scores<REL...>::value;    // c2p holds the b CLS rows compactly (row bi), p2c every token row
+    static_assert(DISENT ? (!BIAS && !ROPE && DHT == 64) : sizeof...(REL) == (BIAS ? 2 : 0),
+                  "the bias table and its span come with BIAS, the position scores without it, and nothing else");
     // q_cls: the b CLS queries as compact [b, H] rows (BERT's last layer projects Q for those rows only); else column block 0 of qkv
     static_assert(DHT == 64 || (DHT == 32 && !ROPE), "head dim 64, or 32 without RoPE");
     __shared__ float Ks[KTT][DHT + 1];
@@ -466,6 +483,13 @@ __global__ __launch_bounds__(64) void attention_cls_kernel(const float* qkv, con
             for (int d = 0; d < DHT; ++d) sc = fmaf(qs[d], Ks[kl][d], sc);
         }
         if constexpr (BIAS) sc = sc + rel_bias_row(head, rel...)[(k0 + lane < S) ? k0 + lane : S - 1];     // (scaled score + bias, then the mask)
+        if constexpr (DISENT) {                       // query 0, key j: distance j
+            const acattn::PosScores ps = pos_scores_of(rel...);
+            const int jc = (k0 + lane < S) ? k0 + lane : S - 1;
+            const int64_t hl = H / DHT;
+            sc = sc + (ps.c2p[((int64_t)bi * hl + head) * ps.ld + ps.span - 1 + jc] +
+                       ps.p2c[((row0 + jc) * hl + head) * ps.ld + ps.span - 1 + jc]);
+        }
         sc = valid ? sc : -INFINITY;
         float cmax = sc;
 #pragma unroll
@@ -486,6 +510,58 @@ __global__ __launch_bounds__(64) void attention_cls_kernel(const float* qkv, con
         m = m_new;
     }
     if (lane < DHT) ctx_cls[(int64_t)bi * H + head * DHT + lane] = l > 0.f ? o / l : 0.f;
+}
+
+// The position scores of one layer's disentangled attention (ac_bert_disentangled): for every query row t, head h and distance d of
+// (-span, span),  c2p[t][h][d + span - 1] = scale * q_t,h . PK[rel_index[d]],  and for every key row the same with k_t,h and PQ
+// (modeling_deberta_v2.py disentangled_attention_bias computes both against all 2 att_span table rows and gathers; here the gather
+// by distance comes first, so the attention reads [row][key - query] directly).  One wave per (32 rows, head, 32 distances, term),
+// K = 64 on v_mfma_f32_32x32x2_f32: A = the 32 rows' pre-scaled q / k fragments, B = the 32 gathered table rows, so the C layout
+// has lane & 31 = distance (coalesced stores) and the registers = the rows.  blockIdx.z < gridDim.z / 2: the c2p term, else p2c.
+// q_gather: the nq query rows are the first rows of the sequences (the CLS-only last layer), read at cu[n] / n * S_ of `q`.
+// rel_index points at distance 0; what it holds is clamped into [0, rel_rows).
+__global__ __launch_bounds__(64) void position_scores_kernel(const float* __restrict__ q, int64_t ld_q, int nq, int q_gather,
+                                                             const float* __restrict__ k, int64_t ld_k, int nk,
+                                                             const int32_t* __restrict__ cu, int S_, const float* __restrict__ pos_key,
+                                                             const float* __restrict__ pos_query, int rel_rows,
+                                                             const int32_t* __restrict__ rel_index, int span, int H, float scale,
+                                                             float* __restrict__ c2p, float* __restrict__ p2c, int ld_out) {
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int head = blockIdx.y, heads = gridDim.y, ndt = gridDim.z >> 1;
+    const bool second = (int)blockIdx.z >= ndt;
+    const int dt = second ? (int)blockIdx.z - ndt : (int)blockIdx.z;
+    const int n = second ? nk : nq, t0 = blockIdx.x * 32;
+    if (t0 >= n) return;
+    int row = t0 + j < n ? t0 + j : n - 1;
+    int64_t srow = row;
+    if (!second && q_gather) srow = cu ? (int64_t)cu[row] : (int64_t)row * S_;
+    const float* ap = (second ? k + srow * ld_k : q + srow * ld_q) + head * 64 + 4 * h;
+    int dc = dt * 32 + j;
+    if (dc > 2 * span - 2) dc = 2 * span - 2;
+    int tr = rel_index[dc - (span - 1)];
+    tr = tr < 0 ? 0 : (tr > rel_rows - 1 ? rel_rows - 1 : tr);
+    const float* bp = (second ? pos_query : pos_key) + (int64_t)tr * H + head * 64 + 4 * h;
+    f32x4 Af[8], Bf[8];
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb) {
+        Af[kb] = *reinterpret_cast<const f32x4*>(ap + 8 * kb) * scale;
+        Bf[kb] = *reinterpret_cast<const f32x4*>(bp + 8 * kb);
+    }
+    acattn::f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < 8; ++kb)
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Af[kb][s4], Bf[kb][s4], acc, 0, 0, 0);
+    float* out = second ? p2c : c2p;
+    const int col = dt * 32 + j;
+    if (col >= ld_out) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int t = t0 + acattn::crow32(r, h);
+        if (t < n) out[((int64_t)t * heads + head) * ld_out + col] = acc[r];
+    }
 }
 
 // ModernBERT MLP gate (modeling_modernbert.py:89-91): u = Wi x is [T, 2I]; g = gelu(u[:, :I]) * u[:, I:]
@@ -790,7 +866,39 @@ int check_rel_bias(const ac_bert_weights* w, int S, const char* who) {
     return AC_OK;
 }
 
+// ac_bert_weights.attn_disentangled: what a call with (b, S) needs of the struct, checked before anything it points to is read
+size_t disentangled_scratch_bytes(const ac_bert_config& c, int b, int S) {
+    return ac::align_up(2 * (size_t)b * S * c.heads * (2 * (size_t)S) * sizeof(float), 256);
+}
+int check_disentangled(const ac_bert_config* c, const ac_bert_weights* w, int b, int S, const char* who) {
+    const ac_bert_disentangled* d = w->attn_disentangled;
+    if (!d) return AC_OK;
+    AC_REQUIRE(!w->attn_rel_bias, AC_EINVAL, "%s: attn_disentangled and attn_rel_bias are both set (one source of position terms)", who);
+    AC_REQUIRE(c->hidden == c->heads * 64, AC_EINVAL, "%s: attn_disentangled needs head dim 64, got %d", who, c->hidden / c->heads);
+    AC_REQUIRE(d->pos_key && d->pos_query && d->rel_index, AC_EINVAL, "%s: attn_disentangled: %s is NULL", who,
+               !d->pos_key ? "pos_key" : !d->pos_query ? "pos_query" : "rel_index");
+    AC_REQUIRE(d->rel_rows >= 1 && d->scale_factor >= 1 && d->scale_factor <= 3, AC_EINVAL,
+               "%s: attn_disentangled: rel_rows=%d (>= 1) / scale_factor=%d (1 .. 3) out of range", who, d->rel_rows, d->scale_factor);
+    AC_REQUIRE(d->rel_span >= 1 && S <= d->rel_span, AC_EINVAL,
+               "%s: S=%d exceeds rel_span=%d of attn_disentangled (rel_index covers 1 <= S <= rel_span)", who, S, d->rel_span);
+    const size_t need = disentangled_scratch_bytes(*c, b, S);
+    AC_REQUIRE(d->scratch && d->scratch_bytes >= need, AC_EINVAL,
+               "%s: attn_disentangled: scratch_bytes %zu < %zu (ac_bert_disentangled_scratch)", who, d->scratch_bytes, need);
+    return AC_OK;
+}
+
 }  // namespace
+
+extern "C" int ac_bert_disentangled_scratch(const ac_bert_config* cfg, int rel_rows, int b, int S, size_t* bytes) {
+    int rc = check_cfg(cfg);
+    if (rc) return rc;
+    AC_REQUIRE(bytes && rel_rows >= 1 && b >= 0 && S >= 1, AC_EINVAL, "bert disentangled scratch: bad arguments (rel_rows=%d b=%d S=%d)",
+               rel_rows, b, S);
+    AC_REQUIRE(cfg->hidden == cfg->heads * 64, AC_EINVAL, "bert disentangled scratch: head dim %d (attn_disentangled needs 64)",
+               cfg->hidden / cfg->heads);
+    *bytes = b > 0 ? disentangled_scratch_bytes(*cfg, b, S) : 0;
+    return AC_OK;
+}
 
 extern "C" int ac_bert_workspace(const ac_bert_config* cfg, int b, int S, size_t* bytes) {
     int rc = check_cfg(cfg);
@@ -883,14 +991,23 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
         AC_LAUNCH_CHECK();
     }
     const int dh = c.hidden / c.heads;                // 64, or 32 (MiniLM family)
-    const float scale = 1.0f / sqrtf((float)dh);
+    // (disentangled attention: three terms under one root, 1 / sqrt(d * scale_factor); scale_factor 1 is the plain scale)
+    const ac_bert_disentangled* dis = w->attn_disentangled;
+    const float scale = 1.0f / sqrtf((float)(dis ? dh * dis->scale_factor : dh));
     // Self-attention inside the QKV GEMM's epilogue (gemm_pipe.hip EPI_QKV_ATTN): sequences laid out row after row (packed, or
     // unpacked without a mask = every sequence S real tokens), head dim 64, longest sequence <= 64, layers 0 .. L-2 on planes
     const int32_t* cu_at = cu;
     // (a relative position bias is not in that epilogue: the QKV GEMM + the stand-alone attention serve such a call's token layers)
     const float* rel = w->attn_rel_bias;
     const int rel_span = w->rel_span;
-    const bool fuse_attn = !rel && pl && token_layers(c) > 0 && dh == 64 && (cu || !d_mask) && ac::qkv_attn_applies(T, H, c.heads, Smax);
+    // (nor are the position terms of a disentangled attention: their scores are computed between the QKV GEMM and the attention)
+    acattn::PosScores ps{nullptr, nullptr, 0, 0};
+    if (dis) {
+        ps.ld = 2 * Smax; ps.span = Smax;
+        ps.c2p = (const float*)dis->scratch;
+        ps.p2c = ps.c2p + (size_t)T * c.heads * ps.ld;
+    }
+    const bool fuse_attn = !rel && !dis && pl && token_layers(c) > 0 && dh == 64 && (cu || !d_mask) && ac::qkv_attn_applies(T, H, c.heads, Smax);
     if (fuse_attn && !cu) {
         int32_t* cuw = (int32_t*)(base + ws.cu);
         hipLaunchKernelGGL(iota_cu_kernel, dim3((b + 256) / 256), dim3(256), 0, stream, cuw, b, S);
@@ -959,11 +1076,29 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
                                       stream, 0.f, 0, qkv_w3, pl ? xp : nullptr);
         }
         if (rc) return rc;
+        if (dis) {
+            // this layer's position scores: q against PK_l and k against PQ_l over the distances (-Smax, Smax).  The CLS-only last
+            // layer needs the c2p term of the b CLS queries alone (compact rows: from y, or gathered from the sequences' first rows)
+            const int nq = last ? b : T;
+            const float* qsrc = last && q_cls_only ? y : qkv;
+            const int ndt = (ps.ld + 31) / 32;
+            hipLaunchKernelGGL(position_scores_kernel, dim3((T + 31) / 32, c.heads, 2 * ndt), dim3(64), 0, stream, qsrc,
+                               last && q_cls_only ? (int64_t)H : 3 * (int64_t)H, nq, (int)(last && !q_cls_only), qkv + H, 3 * (int64_t)H, T, cu, S,
+                               dis->pos_key[l], dis->pos_query[l], dis->rel_rows, dis->rel_index + (dis->rel_span - 1), Smax, H, scale,
+                               (float*)ps.c2p, (float*)ps.p2c, ps.ld);
+            AC_LAUNCH_CHECK();
+        }
         if (fuse_attn && !last) {
             // (context rows are already in ctxp)
         } else if (last) {
             const float* qc = q_cls_only ? y : nullptr;
-            if (rel && dh == 64 && Smax <= 32)
+            if (dis && Smax <= 32)
+                hipLaunchKernelGGL((attention_cls_kernel<false, 64, 32, false, acattn::PosScores>), dim3(c.heads, b), dim3(64), 0, stream, qkv,
+                                   d_mask, S, H, scale, ctx, nullptr, nullptr, -1, cu, qc, ps);
+            else if (dis)
+                hipLaunchKernelGGL((attention_cls_kernel<false, 64, KT, false, acattn::PosScores>), dim3(c.heads, b), dim3(64), 0, stream, qkv,
+                                   d_mask, S, H, scale, ctx, nullptr, nullptr, -1, cu, qc, ps);
+            else if (rel && dh == 64 && Smax <= 32)
                 hipLaunchKernelGGL((attention_cls_kernel<false, 64, 32, true>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
                                    ctx, nullptr, nullptr, -1, cu, qc, rel, rel_span);
             else if (rel && dh == 64)
@@ -982,7 +1117,11 @@ int bert_encode_impl(const ac_bert_config* cfg, const ac_bert_weights* w, const 
                 hipLaunchKernelGGL((attention_cls_kernel<false, 32>), dim3(c.heads, b), dim3(64), 0, stream, qkv, d_mask, S, H, scale,
                                    ctx, nullptr, nullptr, -1, cu, qc);
         } else {
-            if (rel && dh == 64)
+            if (dis)
+                hipLaunchKernelGGL((attention_mfma_kernel<false, 64, false, acattn::PosScores>), dim3((Smax + 31) / 32, c.heads, b), dim3(64), 0,
+                                   stream, qkv, d_mask, S, H, scale, ctx, lp ? ctxp : nullptr, nullptr, nullptr, -1, cu, (int64_t)T, (int)f16,
+                                   0, 0, ps);
+            else if (rel && dh == 64)
                 hipLaunchKernelGGL((attention_mfma_kernel<false, 64, true>), dim3((Smax + 31) / 32, c.heads, b), dim3(64), 0, stream, qkv,
                                    d_mask, S, H, scale, ctx, lp ? ctxp : nullptr, nullptr, nullptr, -1, cu, (int64_t)T, (int)f16, 0, 0,
                                    rel, rel_span);
@@ -1082,9 +1221,11 @@ extern "C" int ac_bert_encode_cls_opts(const ac_bert_config* cfg, const ac_bert_
     AC_REQUIRE(w && d_ids && d_out && b > 0 && S >= 1 && S <= cfg->max_pos && ldo >= cfg->hidden, AC_EINVAL,
                "bert_encode_cls: bad arguments (b=%d S=%d max_pos=%d)", b, S, cfg->max_pos);
     if ((rc = check_rel_bias(w, S, "bert_encode_cls"))) return rc;
+    if ((rc = check_disentangled(cfg, w, b, S, "bert_encode_cls"))) return rc;
     // a handful of token rows (single-query predict): every layer in ONE persistent launch (which ends in the CLS row: a
-    // mean-pooled call of this size goes layer by layer, and so does one with a relative position bias: bert_small.hip has none)
-    if (b * S <= 32 && !(opts & AC_BERT_LAYERED) && !pools_mean(cfg->pool_opt) && !w->attn_rel_bias) {
+    // mean-pooled call of this size goes layer by layer, and so does one with a relative position bias or the position terms of a
+    // disentangled attention: bert_small.hip has neither)
+    if (b * S <= 32 && !(opts & AC_BERT_LAYERED) && !pools_mean(cfg->pool_opt) && !w->attn_rel_bias && !w->attn_disentangled) {
         const BertWs ws = bert_ws(*cfg, b, S);
         AC_REQUIRE(d_ws && ws_bytes >= ws.total, AC_EWORKSPACE, "bert_encode_cls: workspace %zu < %zu", ws_bytes, ws.total);
         rc = ac::bert_small_encode(*cfg, *w, d_ids, d_type_ids, d_mask, b, S, d_out, ldo, (char*)d_ws + ws.small, (hipStream_t)stream_);
@@ -1182,6 +1323,7 @@ extern "C" int ac_bert_encode_cls_unpad(const ac_bert_config* cfg, const ac_bert
                    (int64_t)b * S < ((int64_t)1 << 30),
                AC_EINVAL, "bert_encode_cls_unpad: bad arguments (b=%d S=%d max_pos=%d; more than 32 token rows)", b, S, cfg->max_pos);
     if ((rc = check_rel_bias(w, S, "bert_encode_cls_unpad"))) return rc;
+    if ((rc = check_disentangled(cfg, w, b, S, "bert_encode_cls_unpad"))) return rc;
     const ac_bert_config& c = *cfg;
     const BertWs ws = bert_ws(c, b, S);
     AC_REQUIRE(d_ws && ws_bytes >= ws.total, AC_EWORKSPACE, "bert_encode_cls_unpad: workspace %zu < %zu", ws_bytes, ws.total);
@@ -1249,6 +1391,7 @@ extern "C" int ac_bert_encode_cls_packed(const ac_bert_config* cfg, const ac_ber
                    total_tokens >= b && total_tokens <= b * S && longest >= 1 && longest <= S,
                AC_EINVAL, "bert_encode_cls_packed: bad arguments (b=%d S=%d tokens=%d longest=%d)", b, S, total_tokens, longest);
     if ((rc = check_rel_bias(w, S, "bert_encode_cls_packed"))) return rc;
+    if ((rc = check_disentangled(cfg, w, b, S, "bert_encode_cls_packed"))) return rc;
     return bert_encode_impl(cfg, w, d_ids, d_type_ids, nullptr, b, S, d_cu, d_tok_src, total_tokens, longest, d_out, ldo, d_ws,
                             ws_bytes, (hipStream_t)stream_);
 }

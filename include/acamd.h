@@ -900,6 +900,35 @@ typedef struct {
 #define AC_POOL_CLS     1
 #define AC_POOL_MEAN    2
 
+/*
+ * Disentangled attention (DeBERTa-v2/v3, modeling_deberta_v2.py DisentangledSelfAttention; ac_version() >= 12): the score of
+ * (query i, key j) of head h is
+ *     ( q_i . k_j  +  q_i . PK[idx(j - i)]  +  k_j . PQ[idx(j - i)] ) / sqrt(64 * scale_factor)
+ * -- content-to-content, content-to-position ("c2p") and position-to-content ("p2c").  PK / PQ are the layer's key / query
+ * projections (with bias) of the relative-position embeddings; they depend on the weights only, so the caller builds them once.
+ * A host struct; pos_key / pos_query are host arrays of `layers` device pointers, rel_index and scratch are device memory.
+ *   pos_key[l], pos_query[l]   fp32 [rel_rows][hidden]; head h reads columns h * 64 .. h * 64 + 63.  A term the model does not
+ *                              have is an all-zero table (and scale_factor counts the terms it has: 1 + their number).
+ *   rel_index                  int32 [2 * rel_span - 1]; entry [d + rel_span - 1] = the table row of (query i, key i + d), the index
+ *                              convention of attn_rel_bias.  Every entry must lie in [0, rel_rows) -- the tables are in device
+ *                              memory, so the CALLER checks that (the Python layer does); the kernels clamp what they read.
+ *   scratch, scratch_bytes     device memory of at least ac_bert_disentangled_scratch(cfg, rel_rows, b, S) bytes for a call with
+ *                              that (b, S) (b * S token rows bound the packed forms as well); contents are the call's own.
+ * Each token layer first computes, on the matrix pipe, the position scores of every token row against the 2 * longest - 1
+ * distances the call can reach (q_t . PK[idx(d)] and k_t . PQ[idx(d)], pre-scaled, into the scratch: 2 * rows * heads *
+ * 2 * longest floats); the attention kernels then add the two entries of (i, j) to the scaled score before the key mask.
+ * A call with the struct needs head dimension 64 and 1 <= S <= rel_span, and not attn_rel_bias as well (AC_EINVAL each).  The
+ * self-attention is never fused into the QKV GEMM and a call of <= 32 token rows runs layer by layer (used_one_launch = 0); every
+ * other route, arithmetic and pooling is as without it.  ac_bert_workspace does not depend on it.
+ */
+typedef struct {
+    const float* const* pos_key;    /* [layers] -> fp32 [rel_rows][hidden]: PK_l, head h at columns h*64.. */
+    const float* const* pos_query;  /* [layers] -> fp32 [rel_rows][hidden]: PQ_l */
+    const int32_t* rel_index;       /* [2*rel_span-1]: entry [d + rel_span - 1] = table row for (query i, key i + d) */
+    int rel_rows, rel_span, scale_factor;   /* rows of the tables; S <= rel_span; score scale 1/sqrt(64*scale_factor) */
+    void* scratch; size_t scratch_bytes;    /* device memory for the call, see above */
+} ac_bert_disentangled;
+
 /* Device pointers to the weights, nn.Linear [out,in] layout, fp32.
  * Per-layer arrays have `layers` entries (host arrays of device pointers). */
 typedef struct {
@@ -935,6 +964,9 @@ typedef struct {
     const uint16_t* const* ao_wh;
     const uint16_t* const* ff1_wh;
     const uint16_t* const* ff2_wh;
+    /* Optional (NULL = none; ac_version() >= 12): the position terms of DeBERTa's disentangled attention, see ac_bert_disentangled.
+     * Sits in front of attn_rel_bias so that the two fields after it keep closing the struct; not together with attn_rel_bias. */
+    const ac_bert_disentangled* attn_disentangled;
     /* Optional (NULL = none; ac_version() >= 11): additive relative-position bias of the self-attention, shared by all layers.
      * fp32 [heads][2 * rel_span - 1]; entry [h][d + rel_span - 1] is added to the scaled score of (query i, key j = i + d)
      * of head h before the key mask, positions counted inside the sequence.  MPNet: relative_attention_bias[bucket(j - i)][h].
@@ -1007,6 +1039,9 @@ int ac_host_alloc(size_t bytes, void** p);
 int ac_host_free(void* p);
 
 int ac_bert_workspace(const ac_bert_config* cfg, int b, int S, size_t* bytes);
+/* Bytes of ac_bert_disentangled.scratch a call with (b, S) needs: the two position-score blocks, 2 * (b * S) * heads * 2 * S
+ * floats (every distance a sequence of S tokens reaches, whatever rel_rows >= 1 is).  0 for b == 0. */
+int ac_bert_disentangled_scratch(const ac_bert_config* cfg, int rel_rows, int b, int S, size_t* bytes);
 
 /*
  * classifier.py:1271-1275: BertModel forward in eval mode on

@@ -429,6 +429,46 @@ def test_batched_device_prune_equals_per_example_host_logic(cap, D, stream, cuda
     assert [l for l, _ in ra] == [l for l, _ in rb] and np.allclose([s for _, s in ra], [s for _, s in rb], atol=1e-6)
 
 
+@pytest.mark.parametrize("cap,D", [(8, 128), (10, 66)])
+def test_batched_device_prune_with_exact_duplicate_embeddings(cap, D, cuda_dev):
+    """The same text added twice gives the same embedding twice: the one tie real use produces.  Which copy of a duplicate
+    survives may differ between the batched device prune (on an equal distance the later row goes) and the per-example host
+    logic (numpy's argsort), so per class the sorted multiset of kept embeddings is compared (exact) and the prototypes."""
+    from adaptive_classifier.memory import PrototypeMemory
+    from adaptive_classifier.models import Example, ModelConfig
+    cfg = ModelConfig({"max_examples_per_class": cap, "prototype_update_frequency": 37})
+    a = PrototypeMemory(D, cfg, device=cuda_dev)
+    b = PrototypeMemory(D, cfg, device=cuda_dev)
+    g = torch.Generator().manual_seed(cap * 1000 + D)
+    labels = ["x", "y"]
+    cents = torch.randn(2, D, generator=g)
+    pool = {l: [] for l in labels}
+    for chunk in (5, 9, 16, 1, 24, 12):
+        exs, labs = [], []
+        for _ in range(chunk):
+            c = int(torch.randint(0, 2, (1,), generator=g))
+            if pool[labels[c]] and float(torch.rand(1, generator=g)) < 0.4:      # an exact copy of something this class has seen
+                v = pool[labels[c]][int(torch.randint(0, len(pool[labels[c]]), (1,), generator=g))].clone()
+            else:
+                v = torch.nn.functional.normalize(cents[c] + 0.5 * torch.randn(D, generator=g), dim=0)
+                if float(torch.rand(1, generator=g)) < 0.15:                     # now and then an outlier: copies of it arrive as the farthest row
+                    v = torch.nn.functional.normalize(-cents[c] + 0.1 * torch.randn(D, generator=g), dim=0)
+            pool[labels[c]].append(v)
+            exs.append(v); labs.append(labels[c])
+        for v, l in zip(exs, labs):
+            a.add_example(Example("t", l, v.clone()), l)
+        b.add_examples_batch([Example("t", l, v.clone()) for v, l in zip(exs, labs)], labs)
+        for l in labels:
+            ka = sorted(tuple(e.embedding.tolist()) for e in a.examples[l])
+            kb = sorted(tuple(e.embedding.tolist()) for e in b.examples[l])
+            assert ka == kb, (l, chunk)
+            if l in a.prototypes:
+                assert torch.allclose(a.prototypes[l], b.prototypes[l], atol=1e-6, rtol=0)
+    assert all(len(b.examples[l]) == cap for l in labels)
+    dup = lambda m: sum(len(m.examples[l]) - len({tuple(e.embedding.tolist()) for e in m.examples[l]}) for l in labels)
+    assert dup(a) == dup(b)
+
+
 
 def test_device_class_matrix_cache_hits_with_the_default_device_string(cuda_dev):
     """PrototypeMemory(device="cuda") (the classifier's default string): the device-resident class matrix must be REUSED by

@@ -80,6 +80,12 @@ class ac_bpe_vocab(ctypes.Structure):
                 ("cls_id", c_int), ("sep_id", c_int), ("pad_id", c_int), ("add_prefix_space", c_int)]
 
 
+class ac_unigram_vocab(ctypes.Structure):
+    _fields_ = [("keys", c_void_p), ("entries", c_void_p), ("scores", c_void_p), ("blob", c_void_p), ("slots", c_int),
+                ("max_piece", c_int), ("unk_score", ctypes.c_double), ("unk_id", c_int), ("cls_id", c_int), ("sep_id", c_int),
+                ("pad_id", c_int), ("lowercase", c_int), ("trailing_space_piece", c_int), ("ws_controls", c_int)]
+
+
 class ac_bert_disentangled(ctypes.Structure):
     _fields_ = [("pos_key", c_void_p), ("pos_query", c_void_p), ("rel_index", c_void_p),
                 ("rel_rows", c_int), ("rel_span", c_int), ("scale_factor", c_int),
@@ -250,6 +256,11 @@ _SIGNATURES = {
     "ac_bpe_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
     "ac_bpe_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p]),
+    "ac_unigram_hash": (c_uint64, [c_void_p, c_int]),
+    "ac_unigram_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_unigram_vocab), c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
+    "ac_unigram_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_unigram_vocab), c_int, c_void_p, c_void_p,
+                                       c_void_p]),
     "ac_bert_workspace": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_bert_disentangled_scratch": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_bert_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

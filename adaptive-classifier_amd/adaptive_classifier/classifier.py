@@ -114,8 +114,9 @@ class AdaptiveClassifier:
             if self._gemm_arith == nv.AC_GEMM_F16X2 and hasattr(encoder, "enable_f16x2"):
                 encoder.enable_f16x2()                                           # (builds the fp16 weight planes once; range-checked)
         if tokenizer is not None and (config or {}).get("device_tokenizer", True):
-            # BERT WordPiece vocabularies (ac_wordpiece_encode) and GPT-2 byte-level BPE tokenizers -- RoBERTa-style,
-            # ModernBERT-style (ac_bpe_encode) -- are tokenised on the device; anything else stays as given
+            # BERT WordPiece vocabularies (ac_wordpiece_encode), GPT-2 byte-level BPE tokenizers -- RoBERTa-style,
+            # ModernBERT-style (ac_bpe_encode) -- and Metaspace + Unigram tokenizers -- DeBERTa-v2/v3, XLM-R style
+            # (ac_unigram_encode) -- are tokenised on the device; anything else stays as given
             from .tokenizer import maybe_device_tokenizer
             tokenizer = maybe_device_tokenizer(tokenizer, self.device)
         self.tokenizer = tokenizer

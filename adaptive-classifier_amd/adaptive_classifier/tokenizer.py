@@ -1,24 +1,31 @@
 """Device tokenizers: the tokenizer call of the hot path on MI355X.
 
 Replace `self.tokenizer(texts, max_length=..., truncation=True, padding=True, return_tensors="pt")`
-(/root/reference/src/adaptive_classifier/classifier.py:1259-1265) for the two tokenizer families the encoders cover:
+(/root/reference/src/adaptive_classifier/classifier.py:1259-1265) for the three tokenizer families the encoders cover:
 
 * `HipWordPieceTokenizer` -- BERT-family WordPiece vocabularies (transformers BertTokenizer / DistilBertTokenizer ...:
   tokenizers BertNormalizer + BertPreTokenizer + WordPiece), ids from `ac_wordpiece_encode`;
 * `HipByteBPETokenizer` -- GPT-2 byte-level BPE (RoBERTa-style and ModernBERT-style tokenizers: tokenizers
   ByteLevel(use_regex=True) + BPE behind RobertaProcessing or a `<cls> $A <sep>` template), ids from `ac_bpe_encode`.
   The vocabulary strings and merge sides are turned back into raw bytes (ByteLevel's byte <-> unicode map inverted), so the
-  kernel works on the text's own bytes; `ac_bpe_encode_host` runs the same algorithm on the CPU.
+  kernel works on the text's own bytes; `ac_bpe_encode_host` runs the same algorithm on the CPU;
+* `HipUnigramTokenizer` -- SentencePiece-style Unigram (DeBERTa-v2/v3 and XLM-R style tokenizers: tokenizers
+  Metaspace(prepend_scheme="always") + Unigram behind a `<cls> $A <sep>` template), ids from `ac_unigram_encode`: per
+  whitespace-separated word a Viterbi search in fp64 over the pure-ASCII pieces of the vocabulary, the metaspace stored as
+  0x20; `ac_unigram_encode_host` runs the same algorithm on the CPU, and recognition ends with a probe list on which it
+  must reproduce the wrapped tokenizer (`_unigram_spec`).
 
 Either way the ids are produced on the device and handed to the encoder without a host round trip: host work per batch is
 one concatenation of the texts' bytes, one small H2D and one small D2H (the padded length, which the encoder launch needs).
-A tokenizer is recognised by its serialised configuration (`_wordpiece_spec`, `_bpe_spec`), never by a model name.
+A tokenizer is recognised by its serialised configuration (`_wordpiece_spec`, `_bpe_spec`, `_unigram_spec`), never by a model
+name.
 
 Exactness: identical ids / mask to the wrapped transformers tokenizer.  The kernels cover ASCII texts of up to 4096
 bytes; texts with non-ASCII bytes (accent stripping / CJK spacing / Unicode categories / NFC live in the host library),
 longer texts, texts containing a literal special- or added-token string ("[SEP]", "<s>", ModernBERT's runs of spaces ...)
-and texts the BPE kernel reports as not done (a pre-token of more than 64 bytes) are tokenised by the wrapped tokenizer
-itself and spliced into the batch -- the reference's own tokenizer, not a re-implementation.
+and texts the BPE / Unigram kernels report as not done (a pre-token / word of more than 64 bytes) are tokenised by the wrapped
+tokenizer itself and spliced into the batch -- the reference's own tokenizer, not a re-implementation.  The Unigram wrapper is
+narrower still: bytes 0x20-0x7E and \\t \\n \\r only (the other control bytes go through the host's normalizer).
 """
 import ctypes
 import json
@@ -189,7 +196,220 @@ def bpe_vocab_struct(spec, pointers, slots):
     return nv.ac_bpe_vocab(*pointers, slots, spec["cls_id"], spec["sep_id"], spec["pad_id"], 1 if spec["add_prefix_space"] else 0)
 
 
-# ---- what the two wrappers share ---------------------------------------------------------------------------------------
+# ---- SentencePiece-style Unigram (DeBERTa-v2/v3, XLM-R) ---------------------------------------------------------------------
+METASPACE = "▁"
+_UNIGRAM_NORMALIZERS = {"Lowercase", "NFC", "NFKC", "Nmt", "Strip", "Precompiled", "Replace"}
+_UNIGRAM_REPLACES = {" {2,}", "\\s{2,}|[\\n\\r\\t]"}            # runs of whitespace -> one space: what word splitting does anyway
+_WORD_BYTES = bytes(range(0x20, 0x7f))
+_POLY_BASE, _MIX_MUL = 0x9e3779b97f4a7c15, 0xbf58476d1ce4e5b9    # csrc/unigram_core.h
+_DENSE_PIECE_BYTES = 64                                           # build_unigram_tables: pieces up to here are hashed as one matrix
+
+
+def _unigram_structure(tok):
+    """The structural half of _unigram_spec: the dict without `ws_controls`, from the serialised configuration alone."""
+    cfg = _backend_config(tok)
+    if cfg is None:
+        return None
+    model, norm, pre = cfg.get("model") or {}, cfg.get("normalizer"), cfg.get("pre_tokenizer") or {}
+    if model.get("type") != "Unigram" or model.get("byte_fallback") or model.get("unk_id") is None:
+        return None
+    vocab = model.get("vocab") or []
+    unk_id = int(model["unk_id"])
+    if not 0 <= unk_id < len(vocab) or len(set(p for p, _ in vocab)) != len(vocab):
+        return None
+    lowercase = right_strip = collapses = False
+    if norm is not None:
+        for nm in (norm.get("normalizers") or []) if norm.get("type") == "Sequence" else [norm]:
+            kind = nm.get("type")
+            if kind not in _UNIGRAM_NORMALIZERS:
+                return None
+            if kind == "Replace" and ((nm.get("pattern") or {}).get("Regex") not in _UNIGRAM_REPLACES or nm.get("content") != " "):
+                return None
+            collapses |= kind == "Replace"
+            lowercase |= kind == "Lowercase"
+            right_strip |= kind == "Strip" and bool(nm.get("strip_right"))
+    steps = pre.get("pretokenizers") or [] if pre.get("type") == "Sequence" else [pre]
+    kinds = [st.get("type") for st in steps]
+    if kinds not in (["Metaspace"], ["WhitespaceSplit", "Metaspace"]):
+        return None
+    if kinds == ["Metaspace"] and not collapses:            # every space of a run would become a piece of its own
+        return None
+    meta = steps[-1]
+    if meta.get("replacement") != METASPACE or meta.get("prepend_scheme") != "always" or not meta.get("split", True):
+        return None
+    ends = _template_ends(cfg.get("post_processor") or {})
+    if ends is None:
+        return None
+    if getattr(tok, "padding_side", "right") != "right" or getattr(tok, "truncation_side", "right") != "right":
+        return None
+    added = {a["content"]: int(a["id"]) for a in cfg.get("added_tokens") or []}
+    pieces = {p: i for i, (p, _) in enumerate(vocab)}
+    pad = getattr(tok, "pad_token", None)
+    if pad is None or (pad not in pieces and pad not in added):
+        return None
+    return {"vocab": vocab, "unk_id": unk_id, "cls_id": ends[0], "sep_id": ends[1],
+            "pad_id": int(added[pad] if pad in added else pieces[pad]), "lowercase": bool(lowercase),
+            "trailing_space_piece": kinds == ["Metaspace"] and not right_strip, "specials": _literal_tokens(tok, cfg, [pad]),
+            "token_type_ids": "token_type_ids" in (getattr(tok, "model_input_names", None) or [])}
+
+
+_PROBE_MAX_LENGTH = 128       # no probe comes near it (at most 16 short words or 70 bytes each): nothing is compared truncated
+
+
+def _unigram_probes():
+    """The fixed probe list of the guard: (plain probes, probes with \t \n \r).  Every printable ASCII character stands alone
+    as a word, inside a word (w?w), in front of a letter (?a) and behind one (a?), 16 words per probe, and in runs of 24
+    characters without a space."""
+    printable = [chr(c) for c in range(0x21, 0x7f)]
+    plain = ["", " ", "  ", "   ", "a", " a", "a ", "  a", "a  ", " a ", "a b", "a  b", "a   b  c", "Hello World", "HELLO world",
+             "MiXeD CaSe", "``quoted''", "`` a ''", "''", "``", "it's don't", "3.14 1,000 #1", "x" * 70, "the quick brown fox jumps",
+             "a, b; c: d. e! f?", "(a) [b] {c} <d>", "e-mail under_score", "a/b\\c|d", "100% $5 &co @home ^up ~so *x +y =z",
+             "  lead  and  trail  "]
+    for lo in range(0, len(printable), 16):
+        chunk = printable[lo:lo + 16]
+        plain += [" ".join(chunk), " ".join("w" + ch + "w" for ch in chunk), " ".join(ch + "a" for ch in chunk),
+                  " ".join("a" + ch for ch in chunk)]
+    plain += ["".join(printable[lo:lo + 24]) for lo in range(0, len(printable), 24)]
+    controls = ["\t", "\n", "\r", "a\tb", "a\nb", "a\rb", "\ta", "a\t", "\na", "a\n", "\ra", "a\r", "a\t\tb", "a\n\nb", "a \t b",
+                "a\t \nb", " \n ", "\r\n", "a\r\nb", "tail\n\n", "\n\n lead", "a \n", "a\n "]
+    return plain, controls
+
+
+def _unigram_matches(tok, spec, tables, probes):
+    """Does ac_unigram_encode_host (host tables) give the wrapped tokenizer's ids, mask and lengths on these probes?  A probe
+    that fills max_length on either side counts as a mismatch: its tail would have gone uncompared."""
+    M = _PROBE_MAX_LENGTH
+    arrays, slots = tables
+    vocab = unigram_vocab_struct(spec, [a.ctypes.data for a in arrays], slots)
+    raws = [t.encode("ascii") for t in probes]
+    offs = np.zeros(len(raws) + 1, np.int32)
+    offs[1:] = np.cumsum([len(r) for r in raws])
+    blob = np.frombuffer(b"".join(raws) + b"\0" * 64, np.uint8).copy()
+    ids = np.zeros((len(raws), M), np.int64)
+    mask = np.zeros((len(raws), M), np.int64)
+    lens = np.zeros(len(raws), np.int32)
+    nv.check(nv.lib().ac_unigram_encode_host(blob.ctypes.data, offs.ctypes.data, len(raws), ctypes.byref(vocab), M, ids.ctypes.data,
+                                             mask.ctypes.data, lens.ctypes.data), "ac_unigram_encode_host")
+    want = tok(probes, max_length=M, truncation=True, padding="max_length", return_tensors="np")
+    if int(lens.max(initial=0)) >= M or int(want["attention_mask"].sum(1).max(initial=0)) >= M:
+        return False
+    return np.array_equal(want["input_ids"], ids) and np.array_equal(want["attention_mask"], mask)
+
+
+def _unigram_spec(tok, structure=None):
+    """What HipUnigramTokenizer needs, as a dict, if `tok` is a Metaspace(always) + Unigram tokenizer this module reproduces
+    (DeBERTa-v2/v3 style, XLM-R style), else None: vocab [(piece, score)], unk_id, cls_id, sep_id, pad_id, lowercase,
+    trailing_space_piece, ws_controls, specials, token_type_ids.
+    The serialised form varies across library versions, so the structural reading is never trusted blind: the host entry
+    (ac_unigram_encode_host over host tables; no GPU) must reproduce the wrapped tokenizer on a fixed list of short probes,
+    none compared truncated -- every printable ASCII character alone and inside a word, whitespace of each kind leading / trailing / doubled / mixed, both
+    cases, `` and '', the empty string.  ws_controls is set only if the \t \n \r probes match as well (otherwise texts with
+    those bytes go to the host); any other mismatch gives None.
+    `structure`: an `_unigram_structure(tok)` result the caller already has.  The host tables the probes ran on stay in
+    spec["tables"] (build_unigram_tables' result: ws_controls changes the struct, not the arrays) for the wrapper to upload."""
+    spec = structure if structure is not None else _unigram_structure(tok)
+    if spec is None:
+        return None
+    try:
+        plain, controls = _unigram_probes()
+        keep = lambda ps: [t for t in ps if not any(sp in t for sp in spec["specials"])]      # noqa: E731
+        spec["tables"] = build_unigram_tables(spec)
+        spec["ws_controls"] = False
+        if not _unigram_matches(tok, spec, spec["tables"], keep(plain)):
+            return None
+        spec["ws_controls"] = True
+        spec["ws_controls"] = bool(_unigram_matches(tok, spec, spec["tables"], keep(controls)))
+    except Exception:
+        return None
+    return spec
+
+
+def _unigram_hash_rows(mat, lens):
+    """ac_unigram_hash of every row of a [n, width] uint8 matrix (row i holds lens[i] bytes), vectorised."""
+    h = np.zeros(len(lens), np.uint64)
+    base = np.uint64(_POLY_BASE)
+    for j in range(mat.shape[1]):
+        live = lens > j
+        h[live] = h[live] * base + mat[live, j].astype(np.uint64) + np.uint64(1)
+    h ^= h >> np.uint64(29)
+    h *= np.uint64(_MIX_MUL)
+    h ^= h >> np.uint64(32)
+    h[h == 0] = 1
+    return h
+
+
+def build_unigram_tables(spec):
+    """((keys uint64 [slots], entries int32 [slots, 4] (id, length, blob offset, 0), scores float64 [slots], blob uint8), slots)
+    behind ac_unigram_vocab for a `_unigram_spec` result, on the host (numpy); needs no GPU.  Only the pure-ASCII pieces go in,
+    the metaspace in front as 0x20: a piece with a literal space, a control byte, a non-ASCII character or a metaspace further
+    in can match no word.  Hashing and slot filling are array operations (a 250k-piece vocabulary takes well under a second);
+    the hash restates ac_unigram_hash (tests compare the two).  Adds `max_piece` (longest stored piece) and `unk_score` (the
+    minimum score of the WHOLE vocabulary - 10) to `spec`: unigram_vocab_struct reads them."""
+    vocab = spec["vocab"]
+    texts, tids = [], []
+    for i, (p, _) in enumerate(vocab):
+        q = " " + p[1:] if p[:1] == METASPACE else p
+        if q and " " not in p and q.isascii() and q.isprintable() and len(q) <= MAX_DEVICE_BYTES + 1:
+            texts.append(q)
+            tids.append(i)
+    spec["max_piece"] = max(map(len, texts), default=1)
+    spec["unk_score"] = float(min(s for _, s in vocab)) - 10.0 if vocab else -10.0
+    n = len(texts)
+    slots = 2
+    while slots < 2 * n + 16:
+        slots <<= 1
+    lens = np.fromiter(map(len, texts), np.int64, n)
+    offs = np.zeros(n, np.int64)
+    offs[1:] = np.cumsum(lens)[:-1]
+    flat = np.frombuffer("".join(texts).encode("ascii"), np.uint8)
+    # the dense [pieces, width] matrix holds the pieces of up to 64 bytes (all but a stray few; all a kernel window can match);
+    # longer ones -- only the host entry can meet them, inside a word of that length -- are hashed one by one
+    short = np.flatnonzero(lens <= _DENSE_PIECE_BYTES)
+    rows = np.repeat(np.arange(len(short)), lens[short])
+    at = np.repeat(offs[short], lens[short])
+    within = np.arange(len(rows)) - np.repeat(np.cumsum(lens[short]) - lens[short], lens[short])
+    mat = np.zeros((len(short), int(lens[short].max(initial=1))), np.uint8)
+    mat[rows, within] = flat[at + within]
+    h = np.zeros(n, np.uint64)
+    h[short] = _unigram_hash_rows(mat, lens[short])
+    for i in np.flatnonzero(lens > _DENSE_PIECE_BYTES):
+        h[i] = _unigram_hash_rows(flat[offs[i]:offs[i] + lens[i]][None, :], lens[i:i + 1])[0]
+    keys = np.zeros(slots, np.uint64)
+    where = np.zeros(n, np.int64)
+    mask = slots - 1
+    slot = ((h ^ (h >> np.uint64(32))) & np.uint64(mask)).astype(np.int64)
+    todo = np.arange(n)
+    while len(todo):                                         # linear probing, a round per probe distance: a piece moves on only
+        free = keys[slot[todo]] == 0                         # from a slot that is (or in this round becomes) taken
+        cand = todo[free]
+        _, first = np.unique(slot[cand], return_index=True)
+        placed = cand[first]
+        keys[slot[placed]] = h[placed]
+        where[placed] = slot[placed]
+        stay = np.ones(len(todo), bool)
+        stay[np.flatnonzero(free)[first]] = False
+        todo = todo[stay]
+        slot[todo] = (slot[todo] + 1) & mask
+    entries = np.zeros((slots, 4), np.int32)
+    scores = np.zeros(slots, np.float64)
+    entries[where, 0] = np.asarray(tids, np.int32)
+    entries[where, 1] = lens
+    entries[where, 2] = offs
+    scores[where] = np.asarray([vocab[i][1] for i in tids], np.float64)
+    blob = np.concatenate([flat, np.zeros(16, np.uint8)])
+    return (keys, entries, scores, blob), slots
+
+
+def unigram_vocab_struct(spec, pointers, slots):
+    """ac_unigram_vocab over the four arrays' addresses (device or host), in build_unigram_tables order."""
+    if "max_piece" not in spec:
+        raise nv.NativeError("unigram_vocab_struct: build_unigram_tables(spec) comes first (it measures max_piece and unk_score)")
+    return nv.ac_unigram_vocab(*pointers, slots, spec["max_piece"], spec["unk_score"], spec["unk_id"], spec["cls_id"], spec["sep_id"],
+                               spec["pad_id"], 1 if spec["lowercase"] else 0, 1 if spec["trailing_space_piece"] else 0,
+                               1 if spec.get("ws_controls") else 0)
+
+
+# ---- what the wrappers share ---------------------------------------------------------------------------------------
 def _pack_batch(blob, sizes, dev):
     """Offsets and text in ONE host-to-device copy: [int32 offs[b + 1] | pad to 16 | text bytes | 64 zero bytes]."""
     b = len(sizes)
@@ -216,14 +436,18 @@ class _DeviceTokenizer:
     (return token_type_ids), `_defers` (its kernel may mark a text not done: lens -1) and launches its kernel in `_encode`."""
     _defers = False
     _with_types = True
+    _eligible = None                                     # bytes a device text may hold (None: any ASCII byte)
 
     def __init__(self, hf_tokenizer, device=None):
         self.hf = hf_tokenizer
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.device_texts = self.host_texts = 0          # routing statistics
 
+    def _bytes_ok(self, raw):
+        return raw.isascii() and (self._eligible is None or not raw.translate(None, self._eligible))
+
     def _device_ok(self, text, raw):
-        return len(raw) <= MAX_DEVICE_BYTES and raw.isascii() and not any(sp in text for sp in self.specials)
+        return len(raw) <= MAX_DEVICE_BYTES and self._bytes_ok(raw) and not any(sp in text for sp in self.specials)
 
     def __call__(self, texts, max_length=512, truncation=True, padding=True, return_tensors="pt", **kw):
         if isinstance(texts, str):
@@ -237,10 +461,11 @@ class _DeviceTokenizer:
         # common case first: one pass over the joined batch decides that every text is plain ASCII, short enough and free
         # of special-token strings (a match across a text boundary only costs the slow path)
         joined = "".join(texts)
-        if joined.isascii() and not any(sp in joined for sp in self.specials) and max(map(len, texts), default=0) <= MAX_DEVICE_BYTES:
+        blob = joined.encode("ascii") if joined.isascii() else None
+        if blob is not None and self._bytes_ok(blob) and not any(sp in joined for sp in self.specials) \
+                and max(map(len, texts), default=0) <= MAX_DEVICE_BYTES:
             on_dev = [True] * b
             sizes = [len(t) for t in texts]
-            blob = joined.encode("ascii")
         else:
             raws = [t.encode("utf-8") for t in texts]
             on_dev = [self._device_ok(t, r) for t, r in zip(texts, raws)]
@@ -358,9 +583,33 @@ class HipByteBPETokenizer(_DeviceTokenizer):
                                         nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_bpe_encode")
 
 
+class HipUnigramTokenizer(_DeviceTokenizer):
+    """SentencePiece-style Unigram on the device (ac_unigram_encode): DeBERTa-v2/v3 style and XLM-R style tokenizers.  Device
+    texts hold the bytes 0x20-0x7E and (where the wrapped tokenizer treats them as plain whitespace) \\t \\n \\r only; returns
+    the keys the wrapped tokenizer returns."""
+    _defers = True
+
+    def __init__(self, hf_tokenizer, device=None, structure=None):
+        nv.require_gpu()
+        spec = _unigram_spec(hf_tokenizer, structure)      # structure: the caller's _unigram_structure(hf_tokenizer), if it has one
+        if spec is None:
+            raise nv.NativeError("HipUnigramTokenizer: not a Unigram tokenizer this build reproduces (Metaspace(always) + Unigram "
+                                 "behind a <cls> $A <sep> template, and identical ids on the probe list)")
+        super().__init__(hf_tokenizer, device)
+        self.specials, self._with_types, self.pad_id = spec["specials"], spec["token_type_ids"], spec["pad_id"]
+        self._eligible = _WORD_BYTES + (b"\t\n\r" if spec["ws_controls"] else b"")
+        arrays, slots = spec.pop("tables")                  # the host tables the probe guard ran on
+        self._t = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device) for a in arrays]
+        self.vocab = unigram_vocab_struct(spec, [t.data_ptr() for t in self._t], slots)
+
+    def _encode(self, d_text, d_offs, b, M, ids, mask, lens):
+        nv.check(nv.lib().ac_unigram_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
+                                            nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_unigram_encode")
+
+
 def maybe_device_tokenizer(hf_tokenizer, device):
     """HipWordPieceTokenizer around a BERT WordPiece tokenizer, HipByteBPETokenizer around a GPT-2 byte-level BPE tokenizer,
-    anything else unchanged."""
+    HipUnigramTokenizer around a Metaspace + Unigram tokenizer, anything else unchanged."""
     if hf_tokenizer is None or isinstance(hf_tokenizer, _DeviceTokenizer):
         return hf_tokenizer
     try:
@@ -368,6 +617,9 @@ def maybe_device_tokenizer(hf_tokenizer, device):
             return HipWordPieceTokenizer(hf_tokenizer, device)
         if _bpe_spec(hf_tokenizer) is not None:
             return HipByteBPETokenizer(hf_tokenizer, device)
+        structure = _unigram_structure(hf_tokenizer)
+        if structure is not None:                             # (the probe guard runs inside the constructor)
+            return HipUnigramTokenizer(hf_tokenizer, device, structure)
         return hf_tokenizer
     except Exception:
         return hf_tokenizer

@@ -1276,6 +1276,51 @@ int ac_bpe_encode_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
                        const ac_bpe_vocab* vocab, int max_length,
                        int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
 
+/* A SentencePiece-style Unigram vocabulary (DeBERTa-v2/v3 and XLM-R style tokenizers: tokenizers Metaspace(always) + Unigram)
+ * as an open-addressing hash table over its PURE-ASCII pieces, built by the host wrapper and filled to at most half: slot of a
+ * piece = (h ^ (h >> 32)) & (slots - 1), linear probing, h = ac_unigram_hash(piece bytes).  The metaspace is stored as the byte
+ * 0x20 (whitespace never occurs inside a word); pieces with any other non-ASCII character, or a metaspace anywhere but in front,
+ * can match no text the entries below accept and are left out.  A hit is verified byte-exact against the blob.
+ * Device pointers for ac_unigram_encode, host pointers for ac_unigram_encode_host.  (ac_version() >= 13) */
+typedef struct ac_unigram_vocab {
+    const uint64_t* keys;       /* [slots] stored hash, 0 = empty slot */
+    const int32_t* entries;     /* [slots][4]: token id, piece length in bytes, offset of the piece in blob, 0 */
+    const double* scores;       /* [slots] the piece's score (log probability), the f64 of the serialised vocabulary */
+    const uint8_t* blob;        /* the pieces' bytes */
+    int slots;                  /* power of two */
+    int max_piece;              /* longest piece of the table in bytes (the metaspace counts 1) */
+    double unk_score;           /* min score of the WHOLE vocabulary - 10: what one unknown byte costs */
+    int unk_id, cls_id, sep_id, pad_id;
+    int lowercase;              /* 1 = A-Z -> a-z first */
+    int trailing_space_piece;   /* 1 = a text that ends in whitespace gets a last piece of the metaspace alone (pipelines without
+                                 * WhitespaceSplit and without a right Strip) */
+    int ws_controls;            /* 1 = \t \n \r are whitespace like 0x20; 0 = the caller keeps texts with them away */
+} ac_unigram_vocab;
+
+/* finish(sum (byte[i] + 1) * B^(len - 1 - i) mod 2^64), B = 0x9e3779b97f4a7c15, finish(p): p ^= p >> 29, p *= 0xbf58476d1ce4e5b9,
+ * p ^= p >> 32; never returns 0.  The polynomial makes the hash of any word[s, t) an O(1) function of per-byte prefixes. */
+uint64_t ac_unigram_hash(const uint8_t* bytes, int len);
+
+/*
+ * Tokenise b texts on the device exactly as a tokenizers Metaspace(prepend_scheme = always) + Unigram pipeline does: words are
+ * the whitespace-separated runs, each with a metaspace in front; per word a Viterbi search in fp64 over the vocabulary's scores
+ * (starts ascending, a later proposal wins only when strictly greater, unknown bytes at unk_score each, consecutive unknowns of a
+ * word fused into one unk_id); cls_id ... sep_id, truncation to max_length by tokens, padding with pad_id.  Arguments as
+ * ac_wordpiece_encode: each text <= 4096 bytes, bytes 0x20-0x7E and \t \n \r only, free of literal special / added-token strings
+ * (the caller routes other texts to the host tokenizer).  One launch, no host synchronisation.
+ *   d_lens   int32 [b] sequence lengths incl. the two specials, or -1: NOT DONE -- the text holds a word of more than 64 bytes
+ *            (its metaspace included), its rows of d_ids / d_mask are undefined and the caller tokenises it on the host
+ */
+int ac_unigram_encode(const uint8_t* d_text, const int32_t* d_offsets, int b,
+                      const ac_unigram_vocab* vocab, int max_length,
+                      int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
+
+/* The same algorithm (csrc/unigram_core.h) text by text on the CPU: host pointers everywhere, no GPU call, exact for every
+ * word length (h_lens is never -1). */
+int ac_unigram_encode_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
+                           const ac_unigram_vocab* vocab, int max_length,
+                           int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
+
 #ifdef __cplusplus
 }
 #endif

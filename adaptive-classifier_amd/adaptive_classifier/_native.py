@@ -75,6 +75,10 @@ class ac_wordpiece_vocab(ctypes.Structure):
                 ("pad_id", c_int), ("lower_case", c_int)]
 
 
+class ac_wordpiece_unicode(ctypes.Structure):
+    _fields_ = [("page_of", c_void_p), ("entries", c_void_p), ("images", c_void_p), ("n_pages", c_int), ("image_bytes", c_int)]
+
+
 class ac_bpe_vocab(ctypes.Structure):
     _fields_ = [("keys", c_void_p), ("entries", c_void_p), ("blob", c_void_p), ("byte_id", c_void_p), ("slots", c_int),
                 ("cls_id", c_int), ("sep_id", c_int), ("pad_id", c_int), ("add_prefix_space", c_int)]
@@ -252,6 +256,10 @@ _SIGNATURES = {
     "ac_wordpiece_hash": (c_uint64, [c_void_p, c_int, c_int]),
     "ac_wordpiece_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_wordpiece_vocab), c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p]),
+    "ac_wordpiece_encode_utf8": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_wordpiece_vocab),
+                                         ctypes.POINTER(ac_wordpiece_unicode), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ac_wordpiece_encode_utf8_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_wordpiece_vocab),
+                                              ctypes.POINTER(ac_wordpiece_unicode), c_int, c_void_p, c_void_p, c_void_p]),
     "ac_bpe_pair_hash": (c_uint64, [c_void_p, c_int, c_void_p, c_int]),
     "ac_bpe_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p]),

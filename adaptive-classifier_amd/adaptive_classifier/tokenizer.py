@@ -4,7 +4,8 @@ Replace `self.tokenizer(texts, max_length=..., truncation=True, padding=True, re
 (/root/reference/src/adaptive_classifier/classifier.py:1259-1265) for the three tokenizer families the encoders cover:
 
 * `HipWordPieceTokenizer` -- BERT-family WordPiece vocabularies (transformers BertTokenizer / DistilBertTokenizer ...:
-  tokenizers BertNormalizer + BertPreTokenizer + WordPiece), ids from `ac_wordpiece_encode`;
+  tokenizers BertNormalizer + BertPreTokenizer + WordPiece), ids from `ac_wordpiece_encode` (ASCII texts) and, with
+  `unicode=True`, from `ac_wordpiece_encode_utf8` (UTF-8 texts: below);
 * `HipByteBPETokenizer` -- GPT-2 byte-level BPE (RoBERTa-style and ModernBERT-style tokenizers: tokenizers
   ByteLevel(use_regex=True) + BPE behind RobertaProcessing or a `<cls> $A <sep>` template), ids from `ac_bpe_encode`.
   The vocabulary strings and merge sides are turned back into raw bytes (ByteLevel's byte <-> unicode map inverted), so the
@@ -26,6 +27,17 @@ longer texts, texts containing a literal special- or added-token string ("[SEP]"
 and texts the BPE / Unigram kernels report as not done (a pre-token / word of more than 64 bytes) are tokenised by the wrapped
 tokenizer itself and spliced into the batch -- the reference's own tokenizer, not a re-implementation.  The Unigram wrapper is
 narrower still: bytes 0x20-0x7E and \\t \\n \\r only (the other control bytes go through the host's normalizer).
+
+WordPiece on Unicode text (opt-in: `HipWordPieceTokenizer(hf, unicode=True)`, `maybe_device_tokenizer(hf, device, unicode=True)`,
+`AdaptiveClassifier(config={"device_tokenizer_unicode": True})`).  BertNormalizer and BertPreTokenizer act code point by code
+point, so `build_wordpiece_unicode_tables` turns them into a paged table by probing the wrapped pipeline itself (no Unicode data of
+our own) and `ac_wordpiece_encode_utf8` runs decode, table lookup, segmentation and greedy matching on character boundaries on the
+device (csrc/wordpiece_core.h; `ac_wordpiece_encode_utf8_host` is the same code on the CPU, and a probe list must reproduce the
+wrapped tokenizer on it or the ASCII-only routing stays).  A pure-ASCII batch still takes the ASCII entry.  What still goes to the
+wrapped tokenizer: texts with a host-only code point (a surviving combining mark that NFD may reorder; only with accent
+stripping), over 4096 bytes or with a literal special token -- decided per text by one compiled regular expression -- and what the
+kernel reports as not done (normalised text over 8192 bytes; malformed UTF-8 cannot come out of a str).  It is opt-in because the
+default routing of non-ASCII texts is pinned by existing tests; the BPE and Unigram kernels are ASCII-only either way.
 """
 import ctypes
 import json
@@ -75,6 +87,246 @@ def _wordpiece_spec(tok):
     if any(t is None or t not in vocab for t in need) or model.get("unk_token") != tok.unk_token:
         return None
     return vocab, bool(norm.get("lowercase", True)), _literal_tokens(tok, cfg, need)
+
+
+def build_wordpiece_tables(vocab):
+    """The arrays behind ac_wordpiece_vocab for a WordPiece vocabulary dict, on the host (numpy): (keys uint64 [slots], offs
+    uint32 [slots], ids int32 [slots], lens uint16 [slots], blob uint8), slots, max_piece.  Needs no GPU: the slots are filled
+    with ac_wordpiece_hash, the function the kernels probe with."""
+    L = nv.lib()
+    pieces = []
+    for tokstr, tid in vocab.items():
+        cont = tokstr.startswith("##") and len(tokstr) > 2
+        raw = (tokstr[2:] if cont else tokstr).encode("utf-8")
+        if len(raw) == 0 or len(raw) > 65535:
+            continue
+        pieces.append((raw, int(tid), cont))
+    slots = 1
+    while slots < 2 * len(pieces) + 16:
+        slots <<= 1
+    keys = np.zeros(slots, np.uint64)
+    offs = np.zeros(slots, np.uint32)
+    ids = np.zeros(slots, np.int32)
+    lens = np.zeros(slots, np.uint16)
+    blob = bytearray()
+    mask = slots - 1
+    max_piece = 1
+    for raw, tid, cont in pieces:
+        buf = (ctypes.c_uint8 * len(raw)).from_buffer_copy(raw)
+        h = int(L.ac_wordpiece_hash(buf, len(raw), 1 if cont else 0))
+        s = (h ^ (h >> 32)) & mask
+        while keys[s] != 0:
+            s = (s + 1) & mask
+        keys[s], offs[s], ids[s], lens[s] = h, len(blob), tid | ((1 << 30) if cont else 0), len(raw)
+        blob += raw
+        max_piece = max(max_piece, len(raw))
+    blob += b"\0" * 16
+    return (keys, offs, ids, lens, np.frombuffer(bytes(blob), np.uint8).copy()), slots, max_piece
+
+
+def wordpiece_vocab_struct(hf, vocab, lower, pointers, slots, max_piece):
+    """ac_wordpiece_vocab over the five arrays' addresses (device or host), in build_wordpiece_tables order."""
+    return nv.ac_wordpiece_vocab(*pointers, slots, max_piece, vocab[hf.unk_token], vocab[hf.cls_token], vocab[hf.sep_token],
+                                 vocab[hf.pad_token], 1 if lower else 0)
+
+
+# ---- BertNormalizer + BertPreTokenizer as a probed table (csrc/wordpiece_core.h) ----------------------------------------------
+WP_BUFFER_BYTES = 8192                                            # wpu::kBufBytes: normalised UTF-8 of one text
+_WP_PAGES = 0x1100
+_WP_IDENTITY, _WP_REMOVED, _WP_IMAGE, _WP_HOST_ONLY, _WP_PADDED = range(5)
+_WP_SPACE, _WP_PUNCT, _WP_WORD = 1, 2, 3
+_WP_UNICODE_CACHE = {}
+
+
+def _ranges(cps):
+    """Sorted code points -> [(first, last)] of the runs."""
+    out = []
+    for cp in cps:
+        if out and cp == out[-1][1] + 1:
+            out[-1][1] = cp
+        else:
+            out.append([cp, cp])
+    return [(a, b) for a, b in out]
+
+
+def build_wordpiece_unicode_tables(hf_tokenizer):
+    """BertNormalizer + BertPreTokenizer of `hf_tokenizer` as the table behind ac_wordpiece_unicode, on the host (numpy); needs
+    no GPU.  A dict: page_of uint16 [0x1100], entries uint32 [n_pages, 256], images uint8, n_pages, image_bytes, host_only (the
+    flagged code points, sorted), strips_accents, seconds (of the build).
+
+    No Unicode data of our own: a Python `unicodedata` of another Unicode version would silently disagree with the Rust tables.
+    The wrapped pipeline itself is probed -- image(cp) = normalizer.normalize_str(chr(cp)) for every code point but the
+    surrogates, class(d) = what pre_tokenizer.pre_tokenize_str("a" + d + "b") does to every d that occurs in an image.  The one
+    context dependence: with accent stripping the normaliser runs NFD, which sorts combining marks by combining class.  The Mn
+    marks vanish afterwards, so only a SURVIVING non-starter can end up somewhere else than its image says; whether a survivor
+    is one is probed with the library's own NFD (does it change places with a mark of class 240 in front / of class 1 behind).
+    A code point whose image opens with such a survivor is host-only: in a text without one every surviving non-starter
+    follows a starter of its own image, where NFD already put it in order.
+
+    The result is cached in-process by the serialised normalizer + pre-tokenizer (the sweep takes over a second)."""
+    import time
+    from tokenizers import normalizers
+    cfg = _backend_config(hf_tokenizer) or {}
+    key = json.dumps([cfg.get("normalizer"), cfg.get("pre_tokenizer")], sort_keys=True)
+    if key in _WP_UNICODE_CACHE:
+        return _WP_UNICODE_CACHE[key]
+    t0 = time.perf_counter()
+    be = hf_tokenizer.backend_tokenizer
+    norm, pre = be.normalizer.normalize_str, be.pre_tokenizer.pre_tokenize_str
+    strips = "\u0301" not in norm("e\u0301")
+    cps = list(range(0xD800)) + list(range(0xE000, 0x110000))
+    chars = list(map(chr, cps))
+    imgs = list(map(norm, chars))
+    kind = np.zeros(0x110000, np.uint32)
+    kind[0xD800:0xE000] = _WP_HOST_ONLY                          # (no UTF-8 text holds one: the decoder rejects them)
+    same, gone, other = [], [], {}                               # itself | removed | cp -> image
+    for cp, ch, img in zip(cps, chars, imgs):
+        if img == ch:
+            same.append(cp)
+        elif not img:
+            gone.append(cp)
+        else:
+            other[cp] = img
+    kind[gone] = _WP_REMOVED
+    is_out = np.zeros(0x110000, bool)                            # the code points that occur in normalised text
+    is_out[same] = True
+    where = {}                                                   # image string -> offset | length << 23
+    blob = bytearray()
+    for cp, img in other.items():
+        if img == " " + chr(cp) + " ":
+            kind[cp] = _WP_PADDED
+            is_out[cp] = True
+            continue
+        raw = img.encode("utf-8")
+        if len(raw) > 15 or len(blob) + len(raw) >= 1 << 23:     # what an entry cannot hold (nothing known comes near: <= 12 bytes)
+            kind[cp] = _WP_HOST_ONLY
+            continue
+        if img not in where:
+            where[img] = len(blob) | (len(raw) << 23)
+            blob += raw
+            is_out[[ord(d) for d in img]] = True
+        w = where[img]
+        kind[cp] = _WP_IMAGE | ((w >> 23) << 5) | ((w & ((1 << 23) - 1)) << 9)
+    is_out[0x20] = True
+    # Classes of the output code points, and (accent stripping) which of them are non-starters.  Both properties are per code
+    # point, so a page of 256 is first asked as one string -- "a" + page + "b" stays one piece iff every code point of it is a
+    # word character; marks of class 240 / 1 around every code point stay where they are iff every one is a starter -- and
+    # only a page that fails is asked code point by code point (most pages are CJK, Hangul, unassigned: they pass).
+    cls = np.zeros(0x110000, np.uint8)
+    odd = set()                                                  # outputs without a clean class, or non-starters
+    nfd = normalizers.NFD().normalize_str
+    hi, lo = "\u0345", "\u0334"                                  # combining classes 240 and 1
+    for page in range(_WP_PAGES):
+        at = np.flatnonzero(is_out[page * 256:(page + 1) * 256]) + page * 256
+        if not len(at):
+            continue
+        ds = list(map(chr, at.tolist()))
+        run = "".join(ds)
+        if [p for p, _ in pre("a" + run + "b")] == ["a" + run + "b"]:
+            cls[at] = _WP_WORD
+        else:
+            for d in ds:
+                got = [p for p, _ in pre("a" + d + "b")]
+                cls[ord(d)] = _WP_SPACE if got == ["a", "b"] else _WP_PUNCT if got == ["a", d, "b"] else \
+                    _WP_WORD if got == ["a" + d + "b"] else 0
+                if cls[ord(d)] == 0:
+                    odd.add(d)
+        if strips:
+            marked = "".join(hi + d + lo for d in ds)
+            if nfd(marked) != marked:
+                odd |= {d for d in ds if nfd(hi + d) != hi + nfd(d) or nfd(d + lo) != nfd(d) + lo}
+    kind |= cls.astype(np.uint32) << 3
+    # host-only: a code point that is such an output itself, or whose image opens with one / holds one without a class
+    for d in odd:
+        if (kind[ord(d)] & 7) == _WP_IDENTITY:
+            kind[ord(d)] |= _WP_HOST_ONLY
+    if odd:
+        for cp, img in other.items():
+            first = img[1] if (kind[cp] & 7) == _WP_PADDED else img[0]
+            if first in odd or any(cls[ord(d)] == 0 for d in img):
+                kind[cp] = (kind[cp] & np.uint32(0x18)) | _WP_HOST_ONLY
+    pages, page_of = np.unique(kind.reshape(_WP_PAGES, 256), axis=0, return_inverse=True)
+    images = np.frombuffer(bytes(blob) + b"\0" * 16, np.uint8).copy()
+    host_only = np.flatnonzero((kind & 7) == _WP_HOST_ONLY)
+    host_only = [int(c) for c in host_only if not 0xD800 <= c < 0xE000]
+    tables = {"page_of": page_of.reshape(-1).astype(np.uint16), "entries": np.ascontiguousarray(pages, np.uint32), "images": images,
+              "n_pages": int(len(pages)), "image_bytes": int(len(blob)), "host_only": host_only, "strips_accents": bool(strips),
+              "seconds": time.perf_counter() - t0}
+    _WP_UNICODE_CACHE[key] = tables
+    return tables
+
+
+def wordpiece_unicode_struct(tables, pointers=None):
+    """ac_wordpiece_unicode over the three arrays' addresses (device), or over the host arrays themselves."""
+    if pointers is None:
+        pointers = [tables[k].ctypes.data for k in ("page_of", "entries", "images")]
+    return nv.ac_wordpiece_unicode(*pointers, tables["n_pages"], tables["image_bytes"])
+
+
+def _host_only_regex(tables):
+    """One compiled character class of the host-only code points (None if there is none): eligibility in one C-speed pass."""
+    import re
+    if not tables["host_only"]:
+        return None
+    return re.compile("[" + "".join(re.escape(chr(a)) if a == b else re.escape(chr(a)) + "-" + re.escape(chr(b))
+                                    for a, b in _ranges(tables["host_only"])) + "]")
+
+
+def _wordpiece_unicode_probes():
+    """The fixed probe list of the guard: multi-character strings over what the table encodes -- decompositions, case mappings
+    of one and two code points, CJK spacing, Unicode spaces and punctuation, removed characters, marks in both orders, astral
+    code points, scripts without case -- each also inside a longer text."""
+    base = ["", "a", "Hello, World!", "a\tb\nc\rd", "ctrl\x01in\x7fword \x00 nul",
+            "café naïve résumé", "CAFÉ NAÏVE RÉSUMÉ", "Ångström Œuvre Ærø Ðið Þú ǅemal", "İstanbul ısı ſtraße Maß",
+            "ΣΊΣΥΦΟΣ σίσυφος ς", "\u212a \u212b \u2126 \u00b5", "ﬁn ﬂow ǆ", "한국어 텍스트 각", "\U0001d163 \U0001d15e",
+            "中文 mixed 文本 with 日本語のテキスト", "\U00020000\U0002a6d6 x\U00020000y", "a\u3000b\u00a0c\u2003d\u2028e\u0085f",
+            "zero\u200dwidth soft\u00adhyphen re\ufffdplaced \ufeffbom", "\u200d\u00ad\ufffd",
+            "“quoted” — dash… 、。「」 ！？（）", "full ｗｉｄｔｈ ＡＢＣ １２３",
+            "e\u0327\u0301 e\u0301\u0327 a\u0323\u0302 a\u0302\u0323",              # marks in canonical and in reversed order
+            "ệ Ệ ǖ Ǖ ṩ", "emoji \U0001f600 \U0001f1e9\U0001f1ea here", "Привет, МИР! Ёлка й",
+            "שָׁלוֹם עולם", "مَرْحَبًا بالعالم",
+            "हिन्दी भाषा क़", "ภาษาไทย สวัสดี",
+            "ひらがな カタカナ ｶﾞ が", "¿Qué? ¡Sí! §1 ©2 ª º «x» ±½ µ ¶ · × ÷", "x" * 30 + "é" * 80,
+            "€100 £5 ¥7 ₹9 №3 ™ ℃ Ⅳ ⅷ ① ㈱"]
+    return base + [" ".join(base[i:i + 3]) for i in range(5, len(base) - 2, 3)]
+
+
+def _wordpiece_unicode_matches(hf, specials, vocab_struct, tables, probes):
+    """Does ac_wordpiece_encode_utf8_host (host tables) give the wrapped tokenizer's ids, mask and lengths on these probes, and
+    report as not done exactly those that hold a host-only code point?"""
+    M = _PROBE_MAX_LENGTH
+    probes = [t for t in probes if not any(sp in t for sp in specials)]
+    flagged = _host_only_regex(tables)
+    raws = [t.encode("utf-8") for t in probes]
+    offs = np.zeros(len(raws) + 1, np.int32)
+    offs[1:] = np.cumsum([len(r) for r in raws])
+    blob = np.frombuffer(b"".join(raws) + b"\0" * 64, np.uint8).copy()
+    ids = np.zeros((len(raws), M), np.int64)
+    mask = np.zeros((len(raws), M), np.int64)
+    lens = np.zeros(len(raws), np.int32)
+    uni = wordpiece_unicode_struct(tables)
+    nv.check(nv.lib().ac_wordpiece_encode_utf8_host(blob.ctypes.data, offs.ctypes.data, len(raws), ctypes.byref(vocab_struct),
+                                                    ctypes.byref(uni), M, ids.ctypes.data, mask.ctypes.data, lens.ctypes.data),
+             "ac_wordpiece_encode_utf8_host")
+    want = hf(probes, max_length=M, truncation=True, padding="max_length", return_tensors="np")
+    for i, t in enumerate(probes):
+        if flagged is not None and flagged.search(t):
+            if lens[i] != -1:
+                return False
+        elif lens[i] < 0 or not np.array_equal(want["input_ids"][i], ids[i]) or not np.array_equal(want["attention_mask"][i], mask[i]):
+            return False
+    return True
+
+
+def wordpiece_unicode_tables(hf, specials, vocab_struct):
+    """build_wordpiece_unicode_tables(hf) behind its probe guard: the tables if the host entry over them (and the host
+    vocabulary table behind `vocab_struct`) reproduces the wrapped tokenizer on the probe list, else None -- the tokenizer
+    then keeps its ASCII-only routing."""
+    try:
+        tables = build_wordpiece_unicode_tables(hf)
+        return tables if _wordpiece_unicode_matches(hf, specials, vocab_struct, tables, _wordpiece_unicode_probes()) else None
+    except Exception:
+        return None
 
 
 def _byte_to_unicode():
@@ -433,10 +685,12 @@ def _splice_host_rows(hf, texts, host_rows, M, ids, mask, lens):
 
 class _DeviceTokenizer:
     """Callable with the signature the classifier uses; returns device tensors.  A subclass sets `specials`, `_with_types`
-    (return token_type_ids), `_defers` (its kernel may mark a text not done: lens -1) and launches its kernel in `_encode`."""
+    (return token_type_ids), `_defers` (its kernel may mark a text not done: lens -1) and launches its kernel in `_encode` (ascii_only: every device text of the
+    batch is ASCII)."""
     _defers = False
     _with_types = True
     _eligible = None                                     # bytes a device text may hold (None: any ASCII byte)
+    _utf8 = False                                        # device texts may hold non-ASCII bytes (the subclass overrides _device_ok)
 
     def __init__(self, hf_tokenizer, device=None):
         self.hf = hf_tokenizer
@@ -471,12 +725,13 @@ class _DeviceTokenizer:
             on_dev = [self._device_ok(t, r) for t, r in zip(texts, raws)]
             sizes = [len(r) if ok else 0 for r, ok in zip(raws, on_dev)]
             blob = b"".join(r for r, ok in zip(raws, on_dev) if ok)
+        ascii_only = not self._utf8 or joined.isascii()
         ids = torch.empty((b, M), dtype=torch.int64, device=dev)
         mask = torch.empty((b, M), dtype=torch.int64, device=dev)
         lens = torch.empty(b, dtype=torch.int32, device=dev)
         d_offs, d_text = _pack_batch(blob, sizes, dev)
         with torch.cuda.device(dev):
-            self._encode(d_text, d_offs, b, M, ids, mask, lens)
+            self._encode(d_text, d_offs, b, M, ids, mask, lens, ascii_only)
         host_rows = [i for i, ok in enumerate(on_dev) if not ok]
         if host_rows:
             _splice_host_rows(self.hf, texts, host_rows, M, ids, mask, lens)
@@ -506,59 +761,59 @@ class _DeviceTokenizer:
 
 
 class HipWordPieceTokenizer(_DeviceTokenizer):
-    """BERT WordPiece on the device (ac_wordpiece_encode)."""
+    """BERT WordPiece on the device: ASCII batches through ac_wordpiece_encode; with `unicode=True` a batch that holds
+    non-ASCII text goes through ac_wordpiece_encode_utf8 (the probed normaliser / class table of
+    build_wordpiece_unicode_tables), except the texts with a host-only code point.  Opt-in: without it every non-ASCII text
+    takes the host route, as before.  `unicode` reads False afterwards if the probe guard rejected the tables."""
 
-    def __init__(self, hf_tokenizer, device=None):
+    def __init__(self, hf_tokenizer, device=None, unicode=False):
         nv.require_gpu()
         spec = _wordpiece_spec(hf_tokenizer)
         if spec is None:
             raise nv.NativeError("HipWordPieceTokenizer: not a BERT WordPiece tokenizer (BertNormalizer + BertPreTokenizer + WordPiece)")
         super().__init__(hf_tokenizer, device)
         vocab, self.lower, self.specials = spec
-        self._build_table(vocab)
+        host = self._build_table(vocab)
+        self.unicode = False
+        if unicode:
+            self._enable_unicode(vocab, host)
 
     # ---- vocabulary -> device hash table ---------------------------------------------------------------
     def _build_table(self, vocab):
-        L = nv.lib()
-        pieces = []
-        for tokstr, tid in vocab.items():
-            cont = tokstr.startswith("##") and len(tokstr) > 2
-            raw = (tokstr[2:] if cont else tokstr).encode("utf-8")
-            if len(raw) == 0 or len(raw) > 65535:
-                continue
-            pieces.append((raw, int(tid), cont))
-        slots = 1
-        while slots < 2 * len(pieces) + 16:
-            slots <<= 1
-        keys = np.zeros(slots, np.uint64)
-        offs = np.zeros(slots, np.uint32)
-        ids = np.zeros(slots, np.int32)
-        lens = np.zeros(slots, np.uint16)
-        blob = bytearray()
-        mask = slots - 1
-        max_piece = 1
-        for raw, tid, cont in pieces:
-            buf = (ctypes.c_uint8 * len(raw)).from_buffer_copy(raw)
-            h = int(L.ac_wordpiece_hash(buf, len(raw), 1 if cont else 0))
-            s = (h ^ (h >> 32)) & mask
-            while keys[s] != 0:
-                s = (s + 1) & mask
-            keys[s], offs[s], ids[s], lens[s] = h, len(blob), tid | ((1 << 30) if cont else 0), len(raw)
-            blob += raw
-            max_piece = max(max_piece, len(raw))
-        blob += b"\0" * 16
-        dev = self.device
-        self._t = [torch.from_numpy(a).to(dev) for a in (keys.view(np.int64), offs.view(np.int32), ids, lens.view(np.int16),
-                                                          np.frombuffer(bytes(blob), np.uint8).copy())]
-        hf = self.hf
-        self.vocab = nv.ac_wordpiece_vocab(*[t.data_ptr() for t in self._t], slots, max_piece,
-                                           vocab[hf.unk_token], vocab[hf.cls_token], vocab[hf.sep_token], vocab[hf.pad_token],
-                                           1 if self.lower else 0)
-        self.pad_id = vocab[hf.pad_token]
+        arrays, slots, max_piece = build_wordpiece_tables(vocab)
+        keys, offs, ids, lens, blob = arrays
+        self._t = [torch.from_numpy(a).to(self.device) for a in (keys.view(np.int64), offs.view(np.int32), ids, lens.view(np.int16), blob)]
+        self.vocab = wordpiece_vocab_struct(self.hf, vocab, self.lower, [t.data_ptr() for t in self._t], slots, max_piece)
+        self.pad_id = vocab[self.hf.pad_token]
+        return arrays, slots, max_piece
 
-    def _encode(self, d_text, d_offs, b, M, ids, mask, lens):
-        nv.check(nv.lib().ac_wordpiece_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
-                                              nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_wordpiece_encode")
+    # ---- normaliser / class table -> device (behind the probe guard, which runs on the host arrays) ----
+    def _enable_unicode(self, vocab, host):
+        arrays, slots, max_piece = host
+        host_vocab = wordpiece_vocab_struct(self.hf, vocab, self.lower, [a.ctypes.data for a in arrays], slots, max_piece)
+        tables = wordpiece_unicode_tables(self.hf, self.specials, host_vocab)
+        if tables is None:
+            return
+        self._ut = [torch.from_numpy(a).to(self.device) for a in (tables["page_of"].view(np.int16), tables["entries"].view(np.int32),
+                                                                   tables["images"])]
+        self.unicode_tables = wordpiece_unicode_struct(tables, [t.data_ptr() for t in self._ut])
+        self._host_only = _host_only_regex(tables)
+        self.unicode = self._utf8 = self._defers = True
+
+    def _device_ok(self, text, raw):
+        if not self._utf8 or raw.isascii():
+            return super()._device_ok(text, raw)
+        return len(raw) <= MAX_DEVICE_BYTES and not (self._host_only is not None and self._host_only.search(text)) \
+            and not any(sp in text for sp in self.specials)
+
+    def _encode(self, d_text, d_offs, b, M, ids, mask, lens, ascii_only=True):
+        if ascii_only:
+            nv.check(nv.lib().ac_wordpiece_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
+                                                  nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_wordpiece_encode")
+        else:
+            nv.check(nv.lib().ac_wordpiece_encode_utf8(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab),
+                                                       ctypes.byref(self.unicode_tables), M, nv.ptr(ids), nv.ptr(mask), nv.ptr(lens),
+                                                       nv.stream_ptr(self.device)), "ac_wordpiece_encode_utf8")
 
 
 class HipByteBPETokenizer(_DeviceTokenizer):
@@ -578,7 +833,7 @@ class HipByteBPETokenizer(_DeviceTokenizer):
         self._t = [torch.from_numpy(a).to(self.device) for a in (keys.view(np.int64), entries, blob, byte_id)]
         self.vocab = bpe_vocab_struct(spec, [t.data_ptr() for t in self._t], slots)
 
-    def _encode(self, d_text, d_offs, b, M, ids, mask, lens):
+    def _encode(self, d_text, d_offs, b, M, ids, mask, lens, ascii_only=True):
         nv.check(nv.lib().ac_bpe_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
                                         nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_bpe_encode")
 
@@ -602,19 +857,20 @@ class HipUnigramTokenizer(_DeviceTokenizer):
         self._t = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device) for a in arrays]
         self.vocab = unigram_vocab_struct(spec, [t.data_ptr() for t in self._t], slots)
 
-    def _encode(self, d_text, d_offs, b, M, ids, mask, lens):
+    def _encode(self, d_text, d_offs, b, M, ids, mask, lens, ascii_only=True):
         nv.check(nv.lib().ac_unigram_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
                                             nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_unigram_encode")
 
 
-def maybe_device_tokenizer(hf_tokenizer, device):
+def maybe_device_tokenizer(hf_tokenizer, device, unicode=False):
     """HipWordPieceTokenizer around a BERT WordPiece tokenizer, HipByteBPETokenizer around a GPT-2 byte-level BPE tokenizer,
-    HipUnigramTokenizer around a Metaspace + Unigram tokenizer, anything else unchanged."""
+    HipUnigramTokenizer around a Metaspace + Unigram tokenizer, anything else unchanged.  unicode: non-ASCII texts on the device
+    too where the family has a kernel for them (WordPiece; the BPE and Unigram kernels are ASCII-only)."""
     if hf_tokenizer is None or isinstance(hf_tokenizer, _DeviceTokenizer):
         return hf_tokenizer
     try:
         if _wordpiece_spec(hf_tokenizer) is not None:
-            return HipWordPieceTokenizer(hf_tokenizer, device)
+            return HipWordPieceTokenizer(hf_tokenizer, device, unicode=unicode)
         if _bpe_spec(hf_tokenizer) is not None:
             return HipByteBPETokenizer(hf_tokenizer, device)
         structure = _unigram_structure(hf_tokenizer)

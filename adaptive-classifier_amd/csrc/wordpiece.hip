@@ -10,7 +10,9 @@
 //                   more than 100 characters or with an unmatched remainder -> [UNK]
 //   post-processor  [CLS] pieces[: max_length - 2] [SEP], padded with id 0; attention mask
 // Texts with non-ASCII bytes or literal special-token strings are tokenised by the host tokenizer (the Python wrapper
-// routes them); everything else never leaves the GPU: the ids feed ac_bert_encode_cls directly.
+// routes them); everything else never leaves the GPU: the ids feed ac_bert_encode_cls directly.  UTF-8 texts have an entry of
+// their own, ac_wordpiece_encode_utf8 over a probed normaliser / class table (second half of this file, wordpiece_core.h); the
+// wrapper uses it when asked to (unicode=True), and this entry and its kernel are what they were.
 //
 // One wave per text (texts of up to 4096 bytes; their cleaned bytes live in LDS).  Step 1 compacts the cleaned bytes
 // (ballot + prefix popcount); step 2 walks them in 64-byte
@@ -184,4 +186,172 @@ extern "C" uint64_t ac_wordpiece_hash(const uint8_t* bytes, int len, int continu
     if (continuation) { h = fnv_step(h, '#'); h = fnv_step(h, '#'); }
     for (int i = 0; i < len; ++i) h = fnv_step(h, bytes[i]);
     return h == 0 ? 1 : h;
+}
+
+// ---- UTF-8 texts (ac_wordpiece_encode_utf8[_host], ac_version() >= 14) -----------------------------------------------------------
+// The same pipeline for Unicode text; the algorithm -- strict UTF-8 decoding, the probed normaliser / class table, character-
+// boundary matching -- is wordpiece_core.h, shared with ac_wordpiece_encode_utf8_host.  One wave per text, four waves per
+// workgroup, no communication between waves:
+//   1. lanes take the text's bytes in chunks of 64; the lanes on a lead byte decode their code point (reading their own
+//      continuation bytes, never past the text's end), look up its table entry and the bytes it contributes (0 .. 12); a wave
+//      prefix sum places them in the wave's LDS buffer (wpu::kBufBytes = 8 KiB per wave, 32 KiB per workgroup: five workgroups fit
+//      the 160 KiB of a CU).  The same prefix sum adds up the sequence lengths: they cover the text exactly iff no continuation
+//      byte stands alone.
+//   2. ac_wordpiece_encode's count / prefix sum / write scheme over the word starts of the normalised text, classes from the
+//      table, the 100-character limit counted in characters, match ends on character boundaries only.
+//   3. specials, padding, mask.
+// NOT DONE (lens[tx] = -1, the row left unwritten; the wrapper hands the text to the host tokenizer): malformed UTF-8, a
+// host-only code point, more than 4096 bytes, a normalised text that does not fit the buffer.
+#include "wordpiece_core.h"
+
+namespace {
+
+__global__ __launch_bounds__(256) void wordpiece_utf8_kernel(const uint8_t* __restrict__ text, const int32_t* __restrict__ offs, int b,
+                                                             wpu::Vocab v, wpu::Unicode u, int max_len, int64_t* __restrict__ ids,
+                                                             int64_t* __restrict__ mask, int32_t* __restrict__ lens) {
+    __shared__ uint8_t norm[4][wpu::kBufBytes];
+    const int lane = threadIdx.x & 63;
+    const int tx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tx >= b) return;
+    const int o0 = offs[tx];
+    const int n = offs[tx + 1] - o0;
+    const uint8_t* t = text + o0;
+    uint8_t* c = norm[threadIdx.x >> 6];
+    // ---- 1. decode + normalise + compact (everything that decides `ok` is wave-uniform) ----
+    bool ok = n >= 0 && n <= wpu::kMaxTextBytes;
+    int m = 0, covered = 0;
+    for (int base = 0; ok && base < n; base += 64) {
+        const int p = base + lane;
+        int len = 0, k = 0;
+        uint32_t e = 0;
+        bool bad = false;
+        if (p < n && !wpu::is_cont(t[p])) {
+            uint32_t cp;
+            len = wpu::decode(t + p, n - p, cp);
+            if (len == 0) bad = true;
+            else {
+                e = wpu::entry(u, cp);
+                k = wpu::out_bytes(e, len);
+                if (k < 0) { bad = true; k = 0; }
+            }
+        }
+        if (__ballot(bad)) { ok = false; break; }
+        int incl = k | (len << 16);                                 // both sums in one scan: <= 64 * 12 and <= 64 + 3
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int s = __shfl_up(incl, o); if (lane >= o) incl += s; }
+        const int tot = __shfl(incl, 63);
+        if (m + (tot & 0xffff) > wpu::kBufBytes) { ok = false; break; }
+        if (k) wpu::emit(u, e, t + p, len, c + m + (incl & 0xffff) - k);
+        m += tot & 0xffff;
+        covered += tot >> 16;
+    }
+    if (!ok || covered != n) {                                      // covered < n: a continuation byte no sequence owns
+        if (lane == 0) lens[tx] = -1;
+        return;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // ---- 2. words -> pieces ----
+    int64_t* row = ids + (size_t)tx * max_len;
+    const int room_total = max_len - 2;
+    int total = 0;
+    for (int base = 0; base < m && total < room_total; base += 64) {
+        const int p = base + lane;
+        int wb = 0, chars = 0;
+        if (p < m && !wpu::is_cont(c[p])) {
+            int len;
+            const int k = wpu::class_at(u, c, m, p, len);
+            if (wpu::is_start(u, c, m, p, k)) {
+                chars = 1;
+                wb = k == wpu::kPunct ? len : wpu::word_extent(u, c, m, p, len, chars);
+            }
+        }
+        const int cnt = wb ? wpu::match(v, c + p, wb, chars, nullptr, 0, 0) : 0;
+        int incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int s = __shfl_up(incl, o); if (lane >= o) incl += s; }
+        const int slot = total + incl - cnt;
+        if (wb && slot < room_total) wpu::match(v, c + p, wb, chars, row + 1 + slot, room_total - slot, cnt);
+        total += __shfl(incl, 63);
+    }
+    if (total > room_total) total = room_total;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    // ---- 3. specials, padding, mask ----
+    const int L = total + 2;
+    if (lane == 0) { row[0] = v.cls_id; row[L - 1] = v.sep_id; lens[tx] = L; }
+    int64_t* mrow = mask + (size_t)tx * max_len;
+    for (int i = lane; i < max_len; i += 64) {
+        if (i >= L) row[i] = v.pad_id;
+        mrow[i] = i < L ? 1 : 0;
+    }
+}
+
+int check_utf8_args(const ac_wordpiece_vocab* v, const ac_wordpiece_unicode* u, const void* offsets, const void* ids, const void* mask,
+                    const void* lens, int b, int max_length) {
+    AC_REQUIRE(v && u && offsets && ids && mask && lens && b >= 0 && max_length >= 2, AC_EINVAL, "wordpiece utf8: bad arguments");
+    AC_REQUIRE(v->slots >= 2 && (v->slots & (v->slots - 1)) == 0 && v->keys && v->offs && v->ids && v->lens && v->blob, AC_EINVAL,
+               "wordpiece utf8: vocabulary table must have a power-of-two slot count and all arrays");
+    AC_REQUIRE(u->page_of && u->entries && u->images && u->n_pages >= 1 && u->n_pages <= 65535 && u->image_bytes >= 0, AC_EINVAL,
+               "wordpiece utf8: unicode table must have all arrays and 1 .. 65535 pages");
+    return AC_OK;
+}
+
+wpu::Vocab utf8_vocab_of(const ac_wordpiece_vocab* v) {
+    wpu::Vocab t;
+    t.keys = v->keys; t.offs = v->offs; t.ids = v->ids; t.lens = v->lens; t.blob = v->blob; t.mask = (uint32_t)(v->slots - 1);
+    t.max_piece = v->max_piece_bytes; t.unk_id = v->unk_id; t.cls_id = v->cls_id; t.sep_id = v->sep_id; t.pad_id = v->pad_id;
+    return t;
+}
+
+wpu::Unicode utf8_tables_of(const ac_wordpiece_unicode* u) {
+    wpu::Unicode t;
+    t.page_of = u->page_of; t.entries = u->entries; t.images = u->images; t.n_pages = u->n_pages; t.image_bytes = u->image_bytes;
+    return t;
+}
+
+}  // namespace
+
+extern "C" int ac_wordpiece_encode_utf8(const uint8_t* d_text, const int32_t* d_offsets, int b, const ac_wordpiece_vocab* v,
+                                        const ac_wordpiece_unicode* u, int max_length, int64_t* d_ids, int64_t* d_mask, int32_t* d_lens,
+                                        ac_stream_t stream) {
+    const int rc = check_utf8_args(v, u, d_offsets, d_ids, d_mask, d_lens, b, max_length);
+    if (rc != AC_OK) return rc;
+    if (b == 0) return AC_OK;
+    AC_REQUIRE(d_text, AC_EINVAL, "wordpiece utf8: text is NULL");
+    hipLaunchKernelGGL(wordpiece_utf8_kernel, dim3((b + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_text, d_offsets, b, utf8_vocab_of(v),
+                       utf8_tables_of(u), max_length, d_ids, d_mask, d_lens);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
+}
+
+// The same wordpiece_core.h routines text by text on the CPU (host pointers everywhere, no GPU call), with the kernel's buffer
+// size: it reports exactly the texts the kernel reports as not done.
+extern "C" int ac_wordpiece_encode_utf8_host(const uint8_t* h_text, const int32_t* h_offsets, int b, const ac_wordpiece_vocab* v,
+                                             const ac_wordpiece_unicode* u, int max_length, int64_t* h_ids, int64_t* h_mask,
+                                             int32_t* h_lens) {
+    const int rc = check_utf8_args(v, u, h_offsets, h_ids, h_mask, h_lens, b, max_length);
+    if (rc != AC_OK) return rc;
+    if (b == 0) return AC_OK;
+    AC_REQUIRE(h_text, AC_EINVAL, "wordpiece utf8: text is NULL");
+    const wpu::Vocab t = utf8_vocab_of(v);
+    const wpu::Unicode ut = utf8_tables_of(u);
+    uint8_t* buf = new uint8_t[wpu::kBufBytes];
+    for (int tx = 0; tx < b; ++tx) {
+        int64_t* row = h_ids + (size_t)tx * max_length;
+        int64_t* mrow = h_mask + (size_t)tx * max_length;
+        const int k = wpu::encode_text(ut, t, h_text + h_offsets[tx], h_offsets[tx + 1] - h_offsets[tx], buf, wpu::kBufBytes,
+                                       max_length - 2, row + 1);
+        if (k < 0) { h_lens[tx] = -1; continue; }
+        const int L = k + 2;
+        row[0] = v->cls_id;
+        row[L - 1] = v->sep_id;
+        h_lens[tx] = L;
+        for (int i = 0; i < max_length; ++i) {
+            if (i >= L) row[i] = v->pad_id;
+            mrow[i] = i < L ? 1 : 0;
+        }
+    }
+    delete[] buf;
+    return AC_OK;
 }

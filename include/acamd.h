@@ -1239,6 +1239,45 @@ int ac_wordpiece_encode(const uint8_t* d_text, const int32_t* d_offsets, int b,
                         const ac_wordpiece_vocab* vocab, int max_length,
                         int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
 
+/* BertNormalizer + BertPreTokenizer as a table over the code points U+0000 .. U+10FFFF, built by the host wrapper by probing the
+ * wrapped tokenizers pipeline code point by code point (tokenizer.py build_wordpiece_unicode_tables; no Unicode data lives in this
+ * library).  page_of[cp >> 8] names a page of 256 uint32 entries, identical pages stored once.  An entry:
+ *   bits 0-2   what the normaliser makes of the code point: 0 itself, 1 nothing (removed), 2 an image of up to 15 bytes in
+ *              `images`, 3 host-only (its result depends on its neighbours: NFD reorders it), 4 itself between two spaces (CJK)
+ *   bits 3-4   its class where it occurs in normalised text: 1 space, 2 punctuation, 3 word character (0: never occurs there)
+ *   bits 5-8   image length in bytes, bits 9-31 image offset
+ * Lower-casing and accent stripping are in the images: ac_wordpiece_vocab.lower_case is not read by the _utf8 entries.
+ * Device pointers for ac_wordpiece_encode_utf8, host pointers for ac_wordpiece_encode_utf8_host.  (ac_version() >= 14) */
+typedef struct ac_wordpiece_unicode {
+    const uint16_t* page_of;    /* [0x1100] page of the code points cp with cp >> 8 == index */
+    const uint32_t* entries;    /* [n_pages][256] */
+    const uint8_t* images;      /* [image_bytes] UTF-8 of the images, back to back */
+    int n_pages;                /* 1 .. 65535 */
+    int image_bytes;
+} ac_wordpiece_unicode;
+
+/*
+ * ac_wordpiece_encode for UTF-8 texts: accents, case mappings, CJK spacing, Unicode whitespace / punctuation / control
+ * characters as the wrapped BertNormalizer + BertPreTokenizer treat them (the table above), greedy longest match on character
+ * boundaries, the 100-character word limit counted in characters.  Arguments as ac_wordpiece_encode; `vocab` is the same table
+ * (pieces are stored as UTF-8 bytes).  One launch, no host synchronisation.  The entry needs no wrapper in front of it to be safe:
+ *   d_lens   int32 [b] sequence lengths incl. [CLS] / [SEP], or -1: NOT DONE, the text's rows of d_ids / d_mask are left
+ *            unwritten and the caller tokenises it on the host.  That is a text with malformed UTF-8 (truncated sequence, lone
+ *            continuation byte, overlong form, encoded surrogate, value above U+10FFFF), with a host-only code point, of more
+ *            than 4096 bytes, or whose normalised UTF-8 exceeds the kernel's buffer (8192 bytes; CJK spacing and NFD can grow a
+ *            text up to threefold).  Nothing is read past a text's own end and the other rows are unaffected.
+ * Literal special / added-token strings are the caller's to route, as for ac_wordpiece_encode.
+ */
+int ac_wordpiece_encode_utf8(const uint8_t* d_text, const int32_t* d_offsets, int b,
+                             const ac_wordpiece_vocab* vocab, const ac_wordpiece_unicode* unicode, int max_length,
+                             int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
+
+/* The same routines (csrc/wordpiece_core.h) text by text on the CPU: host pointers everywhere, no GPU call, the same buffer
+ * size, so the same texts come back as -1.  The wrapper's probe guard and the CPU tests run on it. */
+int ac_wordpiece_encode_utf8_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
+                                  const ac_wordpiece_vocab* vocab, const ac_wordpiece_unicode* unicode, int max_length,
+                                  int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
+
 /* A GPT-2 byte-level BPE vocabulary (RoBERTa-style / ModernBERT-style tokenizers: tokenizers ByteLevel(use_regex) + BPE) with
  * every vocabulary string turned back into raw bytes (ByteLevel's byte <-> unicode map inverted).  The merges are an
  * open-addressing hash table, built by the host wrapper and filled to at most half: slot of a merge = (h ^ (h >> 32)) &

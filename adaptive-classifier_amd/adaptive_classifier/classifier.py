@@ -807,8 +807,9 @@ class AdaptiveClassifier:
             return res
         n = host[:off_cls].view(np.int32)
         cls = host[off_cls:off_cls + 4 * b * kk].view(np.int32)
-        val = host[off_val:].view(np.float64)
-        self._last_nan = bool(np.isnan(val).any())
+        val = host[off_val:off_val + 8 * b * kk].view(np.float64)
+        # only the n[q] slots the device wrote: the rest of a row is whatever the staging buffer held before
+        self._last_nan = bool((np.isnan(val).reshape(b, kk) & (np.arange(kk)[None, :] < n[:, None])).any())
         if self._last_nan and check:
             self._raise_if_encoder_gave_up()
         names = getattr(self, "_label_array", None)              # (kept for big label sets only: small ones are rebuilt per call)

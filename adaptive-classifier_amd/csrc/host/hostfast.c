@@ -31,12 +31,13 @@ static PyObject* hf_unpack(PyObject* self, PyObject* args) {
         const int32_t* cls = (const int32_t*)(base + off_cls);
         const double* val = (const double*)(base + off_val);
         int has_nan = 0;
-        for (Py_ssize_t i = 0; i < b * kk; ++i) has_nan |= isnan(val[i]);
         out = PyList_New(b);
         if (!out) goto done;
         for (Py_ssize_t q = 0; q < b; ++q) {
             Py_ssize_t m = n[q] < 0 ? 0 : n[q];
             if (m > kk) m = kk;
+            /* only the n[q] slots the device wrote: the rest of a row is whatever the staging buffer held before */
+            for (Py_ssize_t j = 0; j < m; ++j) has_nan |= isnan(val[q * kk + j]);
             if (m > kcap) m = kcap;
             PyObject* row = PyList_New(m);
             if (!row) { Py_CLEAR(out); goto done; }

@@ -4,7 +4,8 @@ that put the Python layer behind one route planner and two call builders) and re
 A record is the ordered list of `ac_knn_*` / `ac_topk_merge*` calls a case makes, workspace planners included; per call one line:
 the entry name (without `ac_`) and every argument: integers as they are, a pointer as `name+byte offset` of the caller-supplied
 tensor it points into, `fresh` for a buffer the wrapper allocated, `NULL` for a null pointer, `out` for a host out-parameter.
-D = 8 and k = 4 throughout; 3 and 70 queries; stores of 300, 65535 / 65536 (the library's batch limit) and 2^18 rows (the index's plane rule)."""
+The case functions RETURN what their calls returned, in call order (tests/test_poison_knn_gpu.py compares the results; the record
+does not depend on it).  D = 8 and k = 4 throughout; 3 and 70 queries; stores of 300, 65535 / 65536 (the library's batch limit) and 2^18 rows (the index's plane rule)."""
 import ctypes
 
 import numpy as np
@@ -199,8 +200,8 @@ def _store_functions(e):
     ix.store_buffers_sizes(N_BATCH, D)
     ix.store_buffers(N_BATCH, D, e.dev)
     prepared = ix.prepare_store(e.P, N_BATCH, D, capacity=N_BATCH + 1000)
-    ix.update_store(e.P, N_BATCH, N_BATCH + 10, D, prepared, N_BATCH, 10)
-    ix.prepare_store(e.P, N_SMALL, D)
+    ok = ix.update_store(e.P, N_BATCH, N_BATCH + 10, D, prepared, N_BATCH, 10)
+    return [prepared, ok, ix.prepare_store(e.P, N_SMALL, D)]
 
 
 @case("merges")
@@ -208,55 +209,62 @@ def _merges(e):
     ix = e.ix
     d = torch.arange(2 * 3 * K, dtype=torch.float64, device=e.dev).reshape(2, 3, K)
     i = torch.arange(2 * 3 * K, dtype=torch.int64, device=e.dev).reshape(2, 3, K)
-    ix.topk_merge(d, i)
-    ix.topk_merge(d.to(torch.float32), i)
-    ix.topk_merge_ip(d.flip(-1), i)
+    return [ix.topk_merge(d, i), ix.topk_merge(d.to(torch.float32), i), ix.topk_merge_ip(d.flip(-1), i)]
 
 
 # ---- the index methods ------------------------------------------------------------------------------------------------------------
 def _index_small(e, metric):
     idx = e.index(metric, N_SMALL)
-    idx.search_device(e.Q3, K)
-    idx.search_device(e.Q, K)
-    idx.search_device(e.Q3, K, sel=[3, 10, 11, 200, 299])
-    idx.search_device(e.Q3, K, sel=np.arange(N_SMALL) % 3 != 0)
-    idx.range_search_device(e.Q3, e.radius(metric))
-    idx.range_search_device(e.Q, e.rad[metric], sel=np.arange(N_SMALL) % 3 != 0)
-    idx.range_search_device(e.Q3, e.radius(metric), sel=[3, 10, 11, 200, 299])
-    idx.range_search_device(e.Q, e.radius(metric), max_ws_bytes=e.chunk_ws)
+    return [
+        idx.search_device(e.Q3, K),
+        idx.search_device(e.Q, K),
+        idx.search_device(e.Q3, K, sel=[3, 10, 11, 200, 299]),
+        idx.search_device(e.Q3, K, sel=np.arange(N_SMALL) % 3 != 0),
+        idx.range_search_device(e.Q3, e.radius(metric)),
+        idx.range_search_device(e.Q, e.rad[metric], sel=np.arange(N_SMALL) % 3 != 0),
+        idx.range_search_device(e.Q3, e.radius(metric), sel=[3, 10, 11, 200, 299]),
+        idx.range_search_device(e.Q, e.radius(metric), max_ws_bytes=e.chunk_ws),
+    ]
 
 
 def _index_batch_limit(e, metric):
     idx = e.index(metric, N_BATCH)
-    idx.search_device(e.Q3, K)
-    idx.search_device(e.Q3, K)                       # below PLANE_MIN_ROWS: no plane from small searches
-    idx.search_device(e.Q, K)                        # 70 x 65536 pairs: below BATCH_MIN_PAIRS
-    idx.search_device(e.Q, K, sel=e.sel_for(N_BATCH))
-    idx.range_search_device(e.Q3, e.radius(metric))
+    return [
+        idx.search_device(e.Q3, K),
+        idx.search_device(e.Q3, K),                  # below PLANE_MIN_ROWS: no plane from small searches
+        idx.search_device(e.Q, K),                   # 70 x 65536 pairs: below BATCH_MIN_PAIRS
+        idx.search_device(e.Q, K, sel=e.sel_for(N_BATCH)),
+        idx.range_search_device(e.Q3, e.radius(metric)),
+    ]
 
 
 def _index_plane(e, metric):
     ix = e.ix
     idx = e.index(metric, N_PLANE)
     dense = e.sel_for(N_PLANE)
-    idx.search_device(e.Q3, K)
-    idx.search_device(e.Q3, K)                       # the L2 index prepares here; the IP index never from small searches
-    idx.search_device(e.Q3, K, sel=dense)
+    res = [
+        idx.search_device(e.Q3, K),
+        idx.search_device(e.Q3, K),                  # the L2 index prepares here; the IP index never from small searches
+        idx.search_device(e.Q3, K, sel=dense),
+    ]
     if idx._prepared is None:
         idx.prepare_plane() if hasattr(idx, "prepare_plane") else _prepare_from_outside(ix, idx)
-    idx.search_device(e.Q3, K)
-    idx.search_device(e.Q3, K, sel=dense)
-    idx.search_device(e.Q3, K, sel=ix.RowSelector(dense.words, N_PLANE))                    # unknown count
-    idx.search_device(e.Q3, K, sel=[3, 10, 11, 200, 299])
-    idx.range_search_device(e.Q3, e.radius(metric))
-    idx.range_search_device(e.Q3, e.rad[metric][:3], sel=dense)
-    idx.range_search_device(e.Q3, e.radius(metric), sel=[3, 10, 11, 200, 299])
+    res += [
+        idx.search_device(e.Q3, K),
+        idx.search_device(e.Q3, K, sel=dense),
+        idx.search_device(e.Q3, K, sel=ix.RowSelector(dense.words, N_PLANE)),                # unknown count
+        idx.search_device(e.Q3, K, sel=[3, 10, 11, 200, 299]),
+        idx.range_search_device(e.Q3, e.radius(metric)),
+        idx.range_search_device(e.Q3, e.rad[metric][:3], sel=dense),
+        idx.range_search_device(e.Q3, e.radius(metric), sel=[3, 10, 11, 200, 299]),
+    ]
     idx.add(e.P[:5, :D])                             # the plane follows the append
     idx.update_rows([1, 2, 3, 9], e.P[10:14, :D])
-    idx.search_device(e.Q3, K)
+    res.append(idx.search_device(e.Q3, K))
     idx.remove_ids([0])                              # compaction drops the plane
-    idx.search_device(e.Q3, K)
-    idx.range_search_device(e.Q3, e.radius(metric))
+    res.append(idx.search_device(e.Q3, K))
+    res.append(idx.range_search_device(e.Q3, e.radius(metric)))
+    return res
 
 
 def _prepare_from_outside(ix, idx):
@@ -271,15 +279,16 @@ def _sharded(e, metric):
     off = 64
     ss = ShardedSearch(e.P, N_PLANE, D, off, metric=metric)
     e.obj = ss
-    ss.search(e.Q3, K)                               # the sharded search prepares wherever batch_applies(auto=True) holds
-    ss.search(e.Q, K)
-    ss.search(e.Q3, K, sel=e.sel)                    # the global selector: N_PLANE + 128 rows, known dense
-    ss.range_search(e.Q3, e.radius(metric))
-    ss.range_search(e.Q3, e.rad[metric][:3], sel=e.sel)
+    res = [
+        ss.search(e.Q3, K),                          # the sharded search prepares wherever batch_applies(auto=True) holds
+        ss.search(e.Q, K),
+        ss.search(e.Q3, K, sel=e.sel),               # the global selector: N_PLANE + 128 rows, known dense
+        ss.range_search(e.Q3, e.radius(metric)),
+        ss.range_search(e.Q3, e.rad[metric][:3], sel=e.sel),
+    ]
     small = ShardedSearch(e.P, N_SMALL, D, off, metric=metric)
     e.obj = small
-    small.search(e.Q3, K, sel=e.sel)
-    small.range_search(e.Q3, e.radius(metric), sel=e.sel)
+    return res + [small.search(e.Q3, K, sel=e.sel), small.range_search(e.Q3, e.radius(metric), sel=e.sel)]
 
 
 case("index_l2_300")(lambda e: _index_small(e, "l2"))

@@ -610,6 +610,8 @@ def test_hostfast_unpack_builds_the_lists_of_the_python_form():
         layout = (b, kk, off_cls, off_val, C)
         for nan in (False, True):
             if nan:
+                q, j = divmod(b * kk // 2, kk)                  # (a NaN counts in a slot the device wrote: j < n[q])
+                host[:off_cls].view(np.int32)[q] = max(int(host[:off_cls].view(np.int32)[q]), j + 1)
                 host[off_val:].view(np.float64)[b * kk // 2] = np.nan
             fast = cm.AdaptiveClassifier._unpack(o, host, layout, k, False)
             assert o._last_nan == nan

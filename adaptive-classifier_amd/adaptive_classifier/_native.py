@@ -90,6 +90,10 @@ class ac_unigram_vocab(ctypes.Structure):
                 ("pad_id", c_int), ("lowercase", c_int), ("trailing_space_piece", c_int), ("ws_controls", c_int)]
 
 
+class ac_unigram_unicode(ctypes.Structure):
+    _fields_ = [("page_of", c_void_p), ("entries", c_void_p), ("images", c_void_p), ("n_pages", c_int), ("image_bytes", c_int)]
+
+
 class ac_bert_disentangled(ctypes.Structure):
     _fields_ = [("pos_key", c_void_p), ("pos_query", c_void_p), ("rel_index", c_void_p),
                 ("rel_rows", c_int), ("rel_span", c_int), ("scale_factor", c_int),
@@ -269,6 +273,10 @@ _SIGNATURES = {
                                   c_void_p]),
     "ac_unigram_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_unigram_vocab), c_int, c_void_p, c_void_p,
                                        c_void_p]),
+    "ac_unigram_encode_utf8": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_unigram_vocab),
+                                       ctypes.POINTER(ac_unigram_unicode), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ac_unigram_encode_utf8_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_unigram_vocab),
+                                            ctypes.POINTER(ac_unigram_unicode), c_int, c_void_p, c_void_p, c_void_p]),
     "ac_bert_workspace": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_bert_disentangled_scratch": (c_int, [ctypes.POINTER(ac_bert_config), c_int, c_int, c_int, ctypes.POINTER(c_size_t)]),
     "ac_bert_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),

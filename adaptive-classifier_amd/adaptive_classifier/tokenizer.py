@@ -37,10 +37,21 @@ wrapped tokenizer on it or the ASCII-only routing stays).  A pure-ASCII batch st
 wrapped tokenizer: texts with a host-only code point (a surviving combining mark that NFD may reorder; only with accent
 stripping), over 4096 bytes or with a literal special token -- decided per text by one compiled regular expression -- and what the
 kernel reports as not done (normalised text over 8192 bytes; malformed UTF-8 cannot come out of a str).  It is opt-in because the
-default routing of non-ASCII texts is pinned by existing tests; the BPE and Unigram kernels are ASCII-only either way.
+default routing of non-ASCII texts is pinned by existing tests; the BPE kernel is ASCII-only either way.
+
+Unigram on Unicode text (the same opt-in switch: `HipUnigramTokenizer(hf, unicode=True)`).  The whole normalizer chain (Precompiled /
+NFC / NFKC / Nmt / Lowercase / Replace / Strip) becomes a paged table by probing the wrapped pipeline (`build_unigram_unicode_tables`:
+images inside a carrier; host-only where the chain does not act on the code point alone -- grapheme clusters of Precompiled,
+composition under NFC, Strip and runs of Unicode spaces), `build_unigram_tables(spec, utf8=True)` stores every piece as UTF-8 bytes,
+and `ac_unigram_encode_utf8` runs decode, table lookup, word splitting and the character-aware Viterbi on the device, long words
+in blocks of 64 piece ends (csrc/unigram_core.h, csrc/unigram_utf8.hip; `ac_unigram_encode_utf8_host` is the same code on the CPU,
+and a probe list must reproduce the wrapped tokenizer on it or the ASCII-only routing stays).  What still goes to the wrapped
+tokenizer: texts with a host-only code point, over 4096 bytes or with a literal special token, and what the kernel reports as
+not done (normalised text over 5120 bytes).
 """
 import ctypes
 import json
+import re
 
 import numpy as np
 import torch
@@ -455,6 +466,7 @@ _UNIGRAM_REPLACES = {" {2,}", "\\s{2,}|[\\n\\r\\t]"}            # runs of whites
 _WORD_BYTES = bytes(range(0x20, 0x7f))
 _POLY_BASE, _MIX_MUL = 0x9e3779b97f4a7c15, 0xbf58476d1ce4e5b9    # csrc/unigram_core.h
 _DENSE_PIECE_BYTES = 64                                           # build_unigram_tables: pieces up to here are hashed as one matrix
+_UNMATCHABLE = re.compile("[\x00-\x20\x7f" + METASPACE + "]")   # in a piece (behind its leading metaspace): it matches no word
 
 
 def _unigram_structure(tok):
@@ -590,30 +602,48 @@ def _unigram_hash_rows(mat, lens):
     return h
 
 
-def build_unigram_tables(spec):
+def build_unigram_tables(spec, utf8=False):
     """((keys uint64 [slots], entries int32 [slots, 4] (id, length, blob offset, 0), scores float64 [slots], blob uint8), slots)
     behind ac_unigram_vocab for a `_unigram_spec` result, on the host (numpy); needs no GPU.  Only the pure-ASCII pieces go in,
     the metaspace in front as 0x20: a piece with a literal space, a control byte, a non-ASCII character or a metaspace further
     in can match no word.  Hashing and slot filling are array operations (a 250k-piece vocabulary takes well under a second);
     the hash restates ac_unigram_hash (tests compare the two).  Adds `max_piece` (longest stored piece) and `unk_score` (the
-    minimum score of the WHOLE vocabulary - 10) to `spec`: unigram_vocab_struct reads them."""
+    minimum score of the WHOLE vocabulary - 10) to `spec`: unigram_vocab_struct reads them.
+
+    utf8=True: the table ac_unigram_encode_utf8 reads -- the same struct, hash, open addressing and array operations over EVERY
+    piece as its UTF-8 bytes (the metaspace in front as 0x20); only pieces that can match nothing stay out: a literal space, a
+    control byte (a code point with one in its image is host-only), a metaspace further in.  The default call's result and its
+    `max_piece` are untouched: the longest stored piece in BYTES goes to spec["max_piece_utf8"].  The UTF-8 kernel matches pieces of
+    up to 64 bytes (its reach); a vocabulary with a longer storable piece keeps the Unicode route off (unigram_unicode_tables) and
+    the ASCII routing stays.  SentencePiece's trainer caps a piece at 16 characters by default, i.e. at most 64 bytes."""
     vocab = spec["vocab"]
     texts, tids = [], []
+    unmatchable = _UNMATCHABLE.search
     for i, (p, _) in enumerate(vocab):
         q = " " + p[1:] if p[:1] == METASPACE else p
-        if q and " " not in p and q.isascii() and q.isprintable() and len(q) <= MAX_DEVICE_BYTES + 1:
+        if utf8:
+            if q and not unmatchable(q, 1 if q is not p else 0):
+                texts.append(q)
+                tids.append(i)
+        elif q and " " not in p and q.isascii() and q.isprintable() and len(q) <= MAX_DEVICE_BYTES + 1:
             texts.append(q)
             tids.append(i)
-    spec["max_piece"] = max(map(len, texts), default=1)
-    spec["unk_score"] = float(min(s for _, s in vocab)) - 10.0 if vocab else -10.0
     n = len(texts)
+    flat = np.frombuffer("".join(texts).encode("utf-8"), np.uint8)
+    if utf8 and len(flat) != sum(map(len, texts)):           # byte lengths: ASCII pieces as they are, the others one by one
+        lens = np.fromiter((len(t) if t.isascii() else len(t.encode("utf-8")) for t in texts), np.int64, n)
+    else:
+        lens = np.fromiter(map(len, texts), np.int64, n)
+    if utf8:
+        spec["max_piece_utf8"] = int(lens.max(initial=1))
+    else:
+        spec["max_piece"] = max(map(len, texts), default=1)
+    spec["unk_score"] = float(min(s for _, s in vocab)) - 10.0 if vocab else -10.0
     slots = 2
     while slots < 2 * n + 16:
         slots <<= 1
-    lens = np.fromiter(map(len, texts), np.int64, n)
     offs = np.zeros(n, np.int64)
     offs[1:] = np.cumsum(lens)[:-1]
-    flat = np.frombuffer("".join(texts).encode("ascii"), np.uint8)
     # the dense [pieces, width] matrix holds the pieces of up to 64 bytes (all but a stray few; all a kernel window can match);
     # longer ones -- only the host entry can meet them, inside a word of that length -- are hashed one by one
     short = np.flatnonzero(lens <= _DENSE_PIECE_BYTES)
@@ -652,13 +682,234 @@ def build_unigram_tables(spec):
     return (keys, entries, scores, blob), slots
 
 
-def unigram_vocab_struct(spec, pointers, slots):
-    """ac_unigram_vocab over the four arrays' addresses (device or host), in build_unigram_tables order."""
-    if "max_piece" not in spec:
+def unigram_vocab_struct(spec, pointers, slots, utf8=False):
+    """ac_unigram_vocab over the four arrays' addresses (device or host), in build_unigram_tables order (utf8: of its utf8=True
+    form, with that table's max_piece)."""
+    which = "max_piece_utf8" if utf8 else "max_piece"
+    if which not in spec:
         raise nv.NativeError("unigram_vocab_struct: build_unigram_tables(spec) comes first (it measures max_piece and unk_score)")
-    return nv.ac_unigram_vocab(*pointers, slots, spec["max_piece"], spec["unk_score"], spec["unk_id"], spec["cls_id"], spec["sep_id"],
+    return nv.ac_unigram_vocab(*pointers, slots, spec[which], spec["unk_score"], spec["unk_id"], spec["cls_id"], spec["sep_id"],
                                spec["pad_id"], 1 if spec["lowercase"] else 0, 1 if spec["trailing_space_piece"] else 0,
                                1 if spec.get("ws_controls") else 0)
+
+
+# ---- the Unigram normalizer chain as a probed table (csrc/unigram_core.h) -------------------------------------------------------
+UNIGRAM_BUFFER_BYTES = 5120                                       # unigram::kUtf8BufBytes: 0x20 + normalised UTF-8 of one text
+UNIGRAM_REACH = 64                                                # unigram::kReach: longest piece the UTF-8 entries match
+_UNI_IDENTITY, _UNI_REMOVED, _UNI_IMAGE, _UNI_HOST_ONLY = range(4)
+_UNI_MAX_IMAGE = 63                                               # an entry's length field: 6 bits
+_UNI_UNICODE_CACHE = {}
+
+
+def build_unigram_unicode_tables(hf_tokenizer):
+    """The whole normalizer chain of a Unigram tokenizer (Precompiled / NFC / NFKC / Nmt / Lowercase / Replace / Strip) as the
+    table behind ac_unigram_unicode, on the host (numpy); needs no GPU.  A dict: page_of uint16 [0x1100], entries uint32
+    [n_pages, 256], images uint8, n_pages, image_bytes, host_only (the flagged code points, sorted), reasons (counts per probe),
+    seconds (of the build).  An entry: bits 0-1 itself | removed | image | host-only, bits 2-7 image bytes, bits 8-31 image offset.
+
+    No Unicode data of our own: every fact is probed from the wrapped normalizer and pre-tokenizer, per code point d (surrogates
+    excluded), and where a probe cannot show that the chain acts on d alone the answer is host-only:
+    * image(d) = normalize_str("a" + d + "b") without its carrier -- alone in a string a Unicode space may be stripped;
+    * the same image at the end ("a" + d), at the start and next to a multi-byte character that has an image (X + d + X + "b",
+      d + "b"; X = U+00AA): Precompiled replaces a whole grapheme cluster of fewer than 6 bytes by the image of its shortest
+      matching prefix, so a d that clusters with X (combining marks, vowel signs, ZWJ, variation selectors, jamo, prepended marks)
+      shows here; Strip and `\\s{2,}` show at the ends and doubled ("a" + d + d + "b");
+    * a d whose image is one space must behave as U+0020 does at the end, at the start, doubled and next to a U+0020 -- the
+      ASCII probe guard has shown what that is, and the kernel treats every 0x20 of the buffer alike;
+    * composition and reordering (NFC / NFKC / Precompiled in the chain): every code point in a non-first position of the
+      library's NFD of some code point, and every non-starter (it changes places with U+0345 in front or U+0334 behind under the
+      library's NFD; asked of fully decomposed code points, a decomposing one is judged by its first);
+    * an image that OPENS with a flagged code point, holds a control character, holds a character the pre-tokenizer splits off
+      other than U+0020 (a literal metaspace), or is longer than an entry can say (63 bytes).
+    The result is cached in-process by the serialised normalizer + pre-tokenizer (the sweeps take a few seconds)."""
+    import time
+    from tokenizers import normalizers
+    cfg = _backend_config(hf_tokenizer) or {}
+    key = json.dumps([cfg.get("normalizer"), cfg.get("pre_tokenizer")], sort_keys=True)
+    if key in _UNI_UNICODE_CACHE:
+        return _UNI_UNICODE_CACHE[key]
+    t0 = time.perf_counter()
+    be = hf_tokenizer.backend_tokenizer
+    norm = be.normalizer.normalize_str if be.normalizer is not None else (lambda s: s)
+    pre = be.pre_tokenizer.pre_tokenize_str
+    X = "ª"
+    iX = norm(X)
+    if norm("ab") != "ab" or norm("a" + X + "b") != "a" + iX + "b":
+        raise nv.NativeError("build_unigram_unicode_tables: the normalizer does not keep the probe carrier")
+    cps = list(range(0xD800)) + list(range(0xE000, 0x110000))
+    chars = list(map(chr, cps))
+    host = np.zeros(0x110000, bool)
+    host[0xD800:0xE000] = True                                   # (no UTF-8 text holds one: the decoder rejects them)
+    reasons = {}
+
+    def flag(which, why):
+        which = [c for c in which if not host[c]]
+        host[which] = True
+        reasons[why] = reasons.get(why, 0) + len(which)
+
+    # the image inside a carrier
+    mids = [norm("a" + ch + "b") for ch in chars]
+    flag([cp for cp, r in zip(cps, mids) if len(r) < 2 or r[0] != "a" or r[-1] != "b"], "carrier")
+    imgs = [r[1:-1] for r in mids]
+    del mids
+    spaces = {cp for cp, img in zip(cps, imgs) if img == " " and not host[cp]}
+    # position, doubling, neighbours with an image (grapheme clusters)
+    bad = [cp for cp, ch, img in zip(cps, chars, imgs) if cp not in spaces and norm(X + ch + X + "b") != iX + img + iX + "b"]
+    flag(bad, "neighbour")
+    bad = [cp for cp, ch, img in zip(cps, chars, imgs) if cp not in spaces and norm("a" + ch) != "a" + img]
+    flag(bad, "end")
+    bad = [cp for cp, ch, img in zip(cps, chars, imgs) if cp not in spaces and norm(ch + "b") != img + "b"]
+    flag(bad, "start")
+    bad = [cp for cp, ch, img in zip(cps, chars, imgs) if cp not in spaces and norm("a" + ch + ch + "b") != "a" + img + img + "b"]
+    flag(bad, "doubled")
+    # a code point that becomes one space is U+0020 to the chain, wherever it stands
+    like = [norm(s.replace("_", " ")) for s in ("a_", "_b", "a__b", "a__b", "a__b", X + "_" + X + "b")]
+    flag([cp for cp in sorted(spaces) if [norm(s.replace("_", chr(cp))) for s in ("a_", "_b", "a__b")] +
+          [norm("a" + chr(cp) + " b"), norm("a " + chr(cp) + "b"), norm(X + chr(cp) + X + "b")] != like], "space")
+    # composition seconds and non-starters, by the library's own NFD
+    chain = json.dumps(cfg.get("normalizer") or {})
+    if any(k in chain for k in ('"NFC"', '"NFKC"', '"NFD"', '"NFKD"', '"Precompiled"')):
+        nfd = normalizers.NFD().normalize_str
+        decs = list(map(nfd, chars))
+        seconds = {ord(d) for dec in decs if len(dec) > 1 for d in dec[1:]}
+        hi, lo = "\u0345", "\u0334"                              # combining classes 240 and 1
+        nonstart = set()
+        for page in range(0x1100):
+            ds = [ch for ch in map(chr, range(page * 256, page * 256 + 256)) if not 0xD800 <= ord(ch) < 0xE000]
+            ds = [d for d in ds if nfd(d) == d]
+            marked = "".join(hi + d + lo for d in ds)
+            if nfd(marked) != marked:
+                nonstart |= {ord(d) for d in ds if nfd(hi + d) != hi + d or nfd(d + lo) != d + lo}
+        flag(sorted(seconds), "composes")
+        flag(sorted(nonstart), "non-starter")
+        flag([cp for cp, dec in zip(cps, decs) if dec and (ord(dec[0]) in nonstart or ord(dec[0]) in seconds)], "decomposes to one")
+        del decs
+    # what the images hold
+    outs = np.zeros(0x110000, bool)
+    for cp, img in zip(cps, imgs):
+        if not host[cp] and img:
+            outs[[ord(d) for d in img] if len(img) > 1 else ord(img)] = True
+    split_off = set()                                            # output characters the pre-tokenizer does not keep inside a word
+    for page in range(0x1100):
+        at = np.flatnonzero(outs[page * 256:(page + 1) * 256]) + page * 256
+        if not len(at):
+            continue
+        ds = list(map(chr, at.tolist()))
+        run = "".join(ds)
+        if [p for p, _ in pre("a" + run + "b")] != [METASPACE + "a" + run + "b"]:
+            split_off |= {d for d in ds if d != " " and [p for p, _ in pre("a" + d + "b")] != [METASPACE + "a" + d + "b"]}
+    bad_img = []
+    for cp, img in zip(cps, imgs):
+        if host[cp] or not img:
+            continue
+        if host[ord(img[0])] and img[0] != chr(cp):
+            bad_img.append(cp)
+        elif any(d in split_off or d < " " or d == "\x7f" for d in img) or len(img.encode("utf-8")) > _UNI_MAX_IMAGE:
+            bad_img.append(cp)
+    flag(bad_img, "image")
+    # entries and the image blob (identical images stored once)
+    kind = np.zeros(0x110000, np.uint32)
+    where, blob = {}, bytearray()
+    for cp, ch, img in zip(cps, chars, imgs):
+        if host[cp] or img == ch:
+            continue
+        if not img:
+            kind[cp] = _UNI_REMOVED
+            continue
+        if img not in where:
+            raw = img.encode("utf-8")
+            if len(blob) + len(raw) >= 1 << 24:
+                host[cp] = True
+                continue
+            where[img] = _UNI_IMAGE | (len(raw) << 2) | (len(blob) << 8)
+            blob += raw
+        kind[cp] = where[img]
+    kind[host] = _UNI_HOST_ONLY
+    pages, page_of = np.unique(kind.reshape(0x1100, 256), axis=0, return_inverse=True)
+    host_only = [int(c) for c in np.flatnonzero(host) if not 0xD800 <= c < 0xE000]
+    tables = {"page_of": page_of.reshape(-1).astype(np.uint16), "entries": np.ascontiguousarray(pages, np.uint32),
+              "images": np.frombuffer(bytes(blob) + b"\0" * 16, np.uint8).copy(), "n_pages": int(len(pages)),
+              "image_bytes": int(len(blob)), "host_only": host_only, "reasons": reasons, "seconds": time.perf_counter() - t0}
+    _UNI_UNICODE_CACHE[key] = tables
+    return tables
+
+
+def unigram_unicode_struct(tables, pointers=None):
+    """ac_unigram_unicode over the three arrays' addresses (device), or over the host arrays themselves."""
+    if pointers is None:
+        pointers = [tables[k].ctypes.data for k in ("page_of", "entries", "images")]
+    return nv.ac_unigram_unicode(*pointers, tables["n_pages"], tables["image_bytes"])
+
+
+_CJK_99 = "\u6771\u4eac\u90fd\u306b\u4f4f\u3093\u3067\u3044\u307e\u3059\u3002\u4eca\u65e5\u306f\u5929\u6c17\u304c\u3044\u3044\u3067\u3059\u306d\u3001\u6563\u6b69\u306b\u884c\u304d\u307e\u3057\u3087\u3046\u3002"       # a Japanese sentence without a space: one word of 99 bytes
+
+
+def _unigram_unicode_probes():
+    """The fixed probe list of the Unicode guard: multi-character strings over what the table encodes -- accented Latin, Cyrillic,
+    Greek, CJK and kana without spaces and over 64 bytes, precomposed Hangul, full-width forms, Unicode spaces leading / trailing /
+    doubled, ligatures, one- and two-code-point case mappings, astral code points -- and strings that must defer where the table
+    flags them: combining sequences, CRLF, ZWJ emoji, a literal metaspace."""
+    base = ["", "a", "Hello, World!", "caf\u00e9 na\u00efve r\u00e9sum\u00e9", "CAF\u00c9 NA\u00cfVE R\u00c9SUM\u00c9",
+            "\u00c5ngstr\u00f6m \u0152uvre \u00c6r\u00f8 \u00d0i\u00f0 \u00de\u00fa \u01c5emal",
+            "\u0130stanbul \u0131s\u0131 \u017ftra\u00dfe Ma\u00df", "\u03a3\u038a\u03a3\u03a5\u03a6\u039f\u03a3 \u03c3\u03af\u03c3\u03c5\u03c6\u03bf\u03c2 \u03c2",
+            "\u212a \u212b \u2126 \u00b5", "\ufb01n \ufb02ow \u01c6 \ufb03", "\ud55c\uad6d\uc5b4 \ud14d\uc2a4\ud2b8 \uac01",
+            "\u041f\u0440\u0438\u0432\u0435\u0442, \u041c\u0418\u0420! \u0401\u043b\u043a\u0430 \u0439", _CJK_99,
+            "\u4e2d\u6587 mixed \u6587\u672c with \u65e5\u672c\u8a9e\u306e\u30c6\u30ad\u30b9\u30c8",
+            "\u8fd9\u4e2a\u4ea7\u54c1\u5f88\u7cdf\u7cd5\u6d6a\u8d39\u94b1\u4e0d\u8981\u4e70" * 3,
+            "\u3072\u3089\u304c\u306a \u30ab\u30bf\u30ab\u30ca \uff76\uff9e \u304c", "\U00020000\U0002a6d6 x\U00020000y",
+            "emoji \U0001f600 \U0001f1e9\U0001f1ea here", "full \uff57\uff49\uff44\uff54\uff48 \uff21\uff22\uff23 \uff11\uff12\uff13",
+            "a\u3000b\u00a0c\u2003d", "\u00a0lead", "trail\u3000", "a\u00a0\u00a0b", "a \u2003 b", "\u3000\u3000",
+            "\u201cquoted\u201d \u2014 dash\u2026 \u3001\u3002\u300c\u300d \uff01\uff1f\uff08\uff09",
+            "\u00bfQu\u00e9? \u00a1S\u00ed! \u00a71 \u00a92 \u00aa \u00ba \u00abx\u00bb \u00b1\u00bd \u00b5 \u00b6 \u00b7 \u00d7 \u00f7 \u00a8 \u00b4",
+            "x" * 20 + "\u00e9" * 30, "\u20ac100 \u00a35 \u00a57 \u20b99 \u21163 \u2122 \u2103 \u2163 \u2177 \u2460 \u3231 \ufdfa",
+            "zero\u200bwidth soft\u00adhyphen re\ufffdplaced \ufeffbom", "\u1ec7 \u1ec6 \u01d6 \u01d5 \u1e69",
+            "Stra\u00dfe STRASSE \u1e9e", "\u0386\u0388\u0389 \u03ac\u03ad\u03ae", "\u0e20\u0e32\u0e29\u0e32", "\u0939\u093f\u0928\u094d\u0926\u0940",
+            "e\u0301 combining", "A\u0301\u0323", "\uff21\u0301", "a\r\nb", "\U0001f468\u200d\U0001f469\u200d\U0001f467 zwj",
+            "literal " + METASPACE + " metaspace", "a" + METASPACE + "b", "\uac00\u11a8 \u1100\u1161 jamo"]
+    return base + [" ".join(base[i:i + 3]) for i in range(3, 30, 3)]
+
+
+def _unigram_unicode_matches(hf, spec, pieces, tables, probes):
+    """Does ac_unigram_encode_utf8_host (host tables) give the wrapped tokenizer's ids, mask and lengths on these probes, and
+    report as not done exactly those that hold a host-only code point?  A probe that fills max_length counts as a mismatch."""
+    M = _PROBE_MAX_LENGTH
+    probes = [t for t in probes if not any(sp in t for sp in spec["specials"])]
+    flagged = _host_only_regex(tables)
+    arrays, slots = pieces
+    vocab = unigram_vocab_struct(spec, [a.ctypes.data for a in arrays], slots, utf8=True)
+    raws = [t.encode("utf-8") for t in probes]
+    offs = np.zeros(len(raws) + 1, np.int32)
+    offs[1:] = np.cumsum([len(r) for r in raws])
+    blob = np.frombuffer(b"".join(raws) + b"\0" * 64, np.uint8).copy()
+    ids = np.zeros((len(raws), M), np.int64)
+    mask = np.zeros((len(raws), M), np.int64)
+    lens = np.zeros(len(raws), np.int32)
+    uni = unigram_unicode_struct(tables)
+    nv.check(nv.lib().ac_unigram_encode_utf8_host(blob.ctypes.data, offs.ctypes.data, len(raws), ctypes.byref(vocab), ctypes.byref(uni),
+                                                  M, ids.ctypes.data, mask.ctypes.data, lens.ctypes.data), "ac_unigram_encode_utf8_host")
+    want = hf(probes, max_length=M, truncation=True, padding="max_length", return_tensors="np")
+    for i, t in enumerate(probes):
+        if flagged is not None and flagged.search(t):
+            if lens[i] != -1:
+                return False
+        elif lens[i] < 0 or lens[i] >= M or not np.array_equal(want["input_ids"][i], ids[i]) \
+                or not np.array_equal(want["attention_mask"][i], mask[i]):
+            return False
+    return True
+
+
+def unigram_unicode_tables(hf, spec):
+    """(build_unigram_unicode_tables(hf), build_unigram_tables(spec, utf8=True)) behind their probe guard, or None -- the
+    tokenizer then keeps its ASCII-only routing: a storable piece of more than 64 bytes (the kernel's reach), or a probe on which
+    the host entry over these tables does not reproduce the wrapped tokenizer."""
+    try:
+        pieces = build_unigram_tables(spec, utf8=True)
+        if spec["max_piece_utf8"] > UNIGRAM_REACH:
+            return None
+        tables = build_unigram_unicode_tables(hf)
+        return (tables, pieces) if _unigram_unicode_matches(hf, spec, pieces, tables, _unigram_unicode_probes()) else None
+    except Exception:
+        return None
 
 
 # ---- what the wrappers share ---------------------------------------------------------------------------------------
@@ -841,10 +1092,17 @@ class HipByteBPETokenizer(_DeviceTokenizer):
 class HipUnigramTokenizer(_DeviceTokenizer):
     """SentencePiece-style Unigram on the device (ac_unigram_encode): DeBERTa-v2/v3 style and XLM-R style tokenizers.  Device
     texts hold the bytes 0x20-0x7E and (where the wrapped tokenizer treats them as plain whitespace) \\t \\n \\r only; returns
-    the keys the wrapped tokenizer returns."""
+    the keys the wrapped tokenizer returns.
+
+    With `unicode=True` a batch that holds non-ASCII text goes through ac_unigram_encode_utf8: the whole normalizer chain as the
+    probed table of build_unigram_unicode_tables, every piece of the vocabulary as UTF-8 bytes, words of any length (a Chinese
+    or Japanese sentence is one word).  A non-ASCII text is a device text if it has at most 4096 bytes, no literal special /
+    added-token string and no host-only code point (one compiled character class).  Opt-in: without it every non-ASCII text takes
+    the host route, as before.  `unicode` reads False afterwards if the probe guard rejected the tables or the vocabulary holds a
+    piece of more than 64 bytes."""
     _defers = True
 
-    def __init__(self, hf_tokenizer, device=None, structure=None):
+    def __init__(self, hf_tokenizer, device=None, structure=None, unicode=False):
         nv.require_gpu()
         spec = _unigram_spec(hf_tokenizer, structure)      # structure: the caller's _unigram_structure(hf_tokenizer), if it has one
         if spec is None:
@@ -856,16 +1114,44 @@ class HipUnigramTokenizer(_DeviceTokenizer):
         arrays, slots = spec.pop("tables")                  # the host tables the probe guard ran on
         self._t = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device) for a in arrays]
         self.vocab = unigram_vocab_struct(spec, [t.data_ptr() for t in self._t], slots)
+        self.unicode = False
+        if unicode:
+            self._enable_unicode(spec)
+
+    # ---- normalizer table and the all-piece table -> device (behind the probe guard, which runs on the host arrays) ----
+    def _enable_unicode(self, spec):
+        got = unigram_unicode_tables(self.hf, spec)
+        if got is None:
+            return
+        tables, (arrays, slots) = got
+        self._ut = [torch.from_numpy(a).to(self.device) for a in (tables["page_of"].view(np.int16), tables["entries"].view(np.int32),
+                                                                   tables["images"])]
+        self._t8 = [torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(self.device) for a in arrays]
+        self.unicode_tables = unigram_unicode_struct(tables, [t.data_ptr() for t in self._ut])
+        self.vocab_utf8 = unigram_vocab_struct(spec, [t.data_ptr() for t in self._t8], slots, utf8=True)
+        self._host_only = _host_only_regex(tables)
+        self.unicode = self._utf8 = True
+
+    def _device_ok(self, text, raw):
+        if not self._utf8 or raw.isascii():
+            return super()._device_ok(text, raw)
+        return len(raw) <= MAX_DEVICE_BYTES and not (self._host_only is not None and self._host_only.search(text)) \
+            and not any(sp in text for sp in self.specials)
 
     def _encode(self, d_text, d_offs, b, M, ids, mask, lens, ascii_only=True):
-        nv.check(nv.lib().ac_unigram_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
-                                            nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_unigram_encode")
+        if ascii_only:
+            nv.check(nv.lib().ac_unigram_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
+                                                nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_unigram_encode")
+        else:
+            nv.check(nv.lib().ac_unigram_encode_utf8(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab_utf8),
+                                                     ctypes.byref(self.unicode_tables), M, nv.ptr(ids), nv.ptr(mask), nv.ptr(lens),
+                                                     nv.stream_ptr(self.device)), "ac_unigram_encode_utf8")
 
 
 def maybe_device_tokenizer(hf_tokenizer, device, unicode=False):
     """HipWordPieceTokenizer around a BERT WordPiece tokenizer, HipByteBPETokenizer around a GPT-2 byte-level BPE tokenizer,
     HipUnigramTokenizer around a Metaspace + Unigram tokenizer, anything else unchanged.  unicode: non-ASCII texts on the device
-    too where the family has a kernel for them (WordPiece; the BPE and Unigram kernels are ASCII-only)."""
+    too where the family has a kernel for them (WordPiece and Unigram; the BPE kernel is ASCII-only)."""
     if hf_tokenizer is None or isinstance(hf_tokenizer, _DeviceTokenizer):
         return hf_tokenizer
     try:
@@ -875,7 +1161,7 @@ def maybe_device_tokenizer(hf_tokenizer, device, unicode=False):
             return HipByteBPETokenizer(hf_tokenizer, device)
         structure = _unigram_structure(hf_tokenizer)
         if structure is not None:                             # (the probe guard runs inside the constructor)
-            return HipUnigramTokenizer(hf_tokenizer, device, structure)
+            return HipUnigramTokenizer(hf_tokenizer, device, structure, unicode=unicode)
         return hf_tokenizer
     except Exception:
         return hf_tokenizer

@@ -1360,6 +1360,49 @@ int ac_unigram_encode_host(const uint8_t* h_text, const int32_t* h_offsets, int 
                            const ac_unigram_vocab* vocab, int max_length,
                            int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
 
+/* The normalizer chain of a Unigram tokenizer (Precompiled / NFC / NFKC / Nmt / Lowercase / Replace / Strip) as a table over the
+ * code points U+0000 .. U+10FFFF, built by the host wrapper by probing the wrapped tokenizers pipeline (tokenizer.py
+ * build_unigram_unicode_tables; no Unicode data lives in this library).  page_of[cp >> 8] names a page of 256 uint32 entries,
+ * identical pages stored once.  An entry:
+ *   bits 0-1   what the chain makes of the code point: 0 itself, 1 nothing (removed), 2 an image of up to 63 bytes in `images`,
+ *              3 host-only (its result depends on its neighbours or its place in the text: grapheme clusters of Precompiled,
+ *              composition under NFC, Strip, runs of Unicode spaces; or the pre-tokenizer splits it off)
+ *   bits 2-7   image length in bytes, bits 8-31 image offset
+ * Lower-casing is in the images: ac_unigram_vocab.lowercase is not read by the _utf8 entries.  A 0x20 (and, with ws_controls,
+ * \t \n \r) inside an image is whitespace like any other.  A page number or an image outside the tables reads as host-only.
+ * Device pointers for ac_unigram_encode_utf8, host pointers for ac_unigram_encode_utf8_host.  (ac_version() >= 15) */
+typedef struct ac_unigram_unicode {
+    const uint16_t* page_of;    /* [0x1100] page of the code points cp with cp >> 8 == index */
+    const uint32_t* entries;    /* [n_pages][256] */
+    const uint8_t* images;      /* [image_bytes] UTF-8 of the images, back to back */
+    int n_pages;                /* 1 .. 65535 */
+    int image_bytes;
+} ac_unigram_unicode;
+
+/*
+ * ac_unigram_encode for UTF-8 texts and words of any length.  `vocab` is an ac_unigram_vocab over ALL pieces as their UTF-8 bytes
+ * (tokenizer.py build_unigram_tables(spec, utf8=True); the metaspace in front stored as 0x20) with max_piece <= 64.  The text is
+ * decoded strictly, normalised through `unicode` into [0x20][images ...], split at whitespace, and every word goes through the
+ * Viterbi rule of ac_unigram_encode on CHARACTERS: pieces start and end on character boundaries, the unknown spans one character
+ * (1-4 bytes) and is proposed only where no piece of exactly that character starts, consecutive unknowns of a word are one unk_id.
+ * Other arguments as ac_unigram_encode.  One launch, no host synchronisation.  The entry needs no wrapper in front of it to be safe:
+ *   d_lens   int32 [b] sequence lengths incl. the two specials, or -1: NOT DONE, the text's rows of d_ids / d_mask are left
+ *            unwritten and the caller tokenises it on the host.  That is a text with malformed UTF-8 (truncated sequence, lone
+ *            continuation byte, overlong form, encoded surrogate, value above U+10FFFF), with a host-only code point, of more
+ *            than 4096 bytes, or whose normalised UTF-8 with its leading 0x20 exceeds the kernel's buffer (5120 bytes).  Nothing
+ *            is read past a text's own end and the other rows are unaffected.  A long word is NOT a reason: it is done.
+ * Literal special / added-token strings are the caller's to route, as for ac_unigram_encode.
+ */
+int ac_unigram_encode_utf8(const uint8_t* d_text, const int32_t* d_offsets, int b,
+                           const ac_unigram_vocab* vocab, const ac_unigram_unicode* unicode, int max_length,
+                           int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
+
+/* The same routines (csrc/unigram_core.h) text by text on the CPU: host pointers everywhere, no GPU call, the same buffer size,
+ * so the same texts come back as -1.  The wrapper's probe guard and the CPU tests run on it. */
+int ac_unigram_encode_utf8_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
+                                const ac_unigram_vocab* vocab, const ac_unigram_unicode* unicode, int max_length,
+                                int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
+
 #ifdef __cplusplus
 }
 #endif

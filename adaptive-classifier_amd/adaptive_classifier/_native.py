@@ -202,6 +202,7 @@ _SIGNATURES = {
     "ac_gemm_set_ln_fusion": (c_int, [c_int]),
     "ac_gemm_ln_fusion_launches": (c_int64, []),
     "ac_gemm_qkv_attn_launches": (c_int64, []),
+    "ac_gemm_f16x2_launches": (c_int64, []),
     "ac_set_persistent_kernels": (c_int, [c_int]),
     "ac_clock_stamp": (c_int, [c_void_p, c_void_p]),
     "ac_gemm_occupancy": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),

@@ -412,6 +412,8 @@ inline bool arith_split() { return gemm_arith() != AC_GEMM_F32; }   // bf16x3, o
 bool linear_f16x2_takes(int M, int N, int K);
 int linear_f16x2(const uint16_t* Ap, const uint16_t* Wp, const float* bias, const float* residual, int64_t ldr, float* C,
                  int64_t ldc, uint16_t* Cp, int M, int N, int K, int act, hipStream_t stream, int64_t w_plane_rows = 0);
+// one more host-side launch of a GEMM on fp16x2 operand planes (diagnostic: ac_gemm_f16x2_launches; gemm_pipe.hip)
+void count_f16x2_launch();
 //   C = alpha * op(A) op(B) + beta * C; if gate != null: C = gate[m,n] != 0 ? C * gate_scale : 0
 int gemm_f32(int transA, int transB, int M, int N, int K, float alpha, const float* A, int64_t lda,
              const float* B, int64_t ldb, float beta, float* C, int64_t ldc, const float* gate,

@@ -910,6 +910,7 @@ int linear_f16x2(const uint16_t* Ap, const uint16_t* Wp, const float* bias, cons
                "linear_f16x2: act %d / residual / planes-out combination not built", act);
     Epilogue e;
     e.bias = bias; e.residual = residual; e.ldr = ldr; e.act = act;
+    count_f16x2_launch();
     return launch_gemm_pipe(p.cfg, Ap, M, Wp, w_plane_rows > 0 ? w_plane_rows : N, C, ldc, Cp, M, N, K, p.cls, e, stream, 1);
 }
 // linear_f32 for shapes with few output tiles: split-K over `scratch` (see gemm_planes_splitk_nt); falls back to

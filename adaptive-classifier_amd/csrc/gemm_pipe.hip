@@ -738,6 +738,8 @@ static int exchange_fences() {
 }
 // ---- the QKV projection with the self-attention of the packed sequences in its epilogue (EPI_QKV_ATTN) ----
 static std::atomic<long long> g_qkv_attn_launches{0};
+static std::atomic<long long> g_f16x2_launches{0};     // GEMM launches on fp16x2 operand planes: linear_f16x2 and the f16 forms below
+void count_f16x2_launch() { g_f16x2_launches.fetch_add(1, std::memory_order_relaxed); }
 bool qkv_attn_applies(int M, int H, int heads, int smax) {
     if (const char* e = getenv("AC_QKV_ATTN_FUSION"); e && atoi(e) == 0) return false;      // (A/B runs and the two-launch route's tests)
     return qkv_attn_shape(M, H, heads, smax, gemm_env());
@@ -807,6 +809,7 @@ int launch_gemm_pipe_qkv_attn(const uint16_t* Ap, int64_t a_rows, const uint16_t
                "gemm_pipe_qkv_attn: the in-launch exchange needs every tile resident (%d rows x %d heads) and an abort word", M, heads);
     p.at.exchange = exchange; p.at.epoch = epoch; p.at.abort_ = abort_flag; p.at.fences = exchange_fences();
     g_qkv_attn_launches.fetch_add(1, std::memory_order_relaxed);
+    if (f16) count_f16x2_launch();
     return f16 ? launch_one<EPI_QKV_ATTN, 2, 3, 4, 2, 4, false, 2, 2>(p, stream)
                : launch_one<EPI_QKV_ATTN, 2, 3, 4, 2, 3, false, 2, 3>(p, stream);
 }
@@ -852,6 +855,7 @@ int launch_gemm_pipe_ln(const uint16_t* Ap, int64_t a_rows, const uint16_t* Wp, 
     p.ln.fences = exchange_fences();
     p.ln.planes = planes; p.ln.starve = (call_opts().ln_fusion >= 0 ? call_opts().ln_fusion : g_ln_fusion.load(std::memory_order_relaxed)) == 2 ? 1 : 0;
     g_ln_launches.fetch_add(1, std::memory_order_relaxed);
+    if (f16) count_f16x2_launch();
     return f16 ? launch_cfg<1, 2, 4, 2, 6, 2, 2>(EPI_BIAS_RES_LN, false, p, stream)
                : launch_cfg<1, 2, 4, 2, 6, 2>(EPI_BIAS_RES_LN, false, p, stream);
 }
@@ -870,6 +874,8 @@ extern "C" int ac_gemm_set_ln_fusion(int on) {
 extern "C" int64_t ac_gemm_ln_fusion_launches(void) { return (int64_t)ac::g_ln_launches.load(std::memory_order_relaxed); }
 /* diagnostic (tests assert that the fused route really ran): launches of the QKV GEMM with the attention epilogue so far */
 extern "C" int64_t ac_gemm_qkv_attn_launches(void) { return (int64_t)ac::g_qkv_attn_launches.load(std::memory_order_relaxed); }
+/* diagnostic (tests assert that a call really ran in fp16x2 and did not fall back to bf16x3): GEMM launches on fp16x2 planes so far */
+extern "C" int64_t ac_gemm_f16x2_launches(void) { return (int64_t)ac::g_f16x2_launches.load(std::memory_order_relaxed); }
 
 static int parse_pipe_table(const char* spec, acg::PipeTable* t) {
     if (!spec) { t->n = -1; return AC_OK; }

@@ -634,6 +634,12 @@ int64_t ac_gemm_ln_fusion_launches(void);      /* fused launches of this process
  * the attention launch disappear (gemm_pipe.hip EPI_QKV_ATTN).  Env AC_QKV_ATTN_FUSION=0 keeps the two launches (A/B, tests).
  * Diagnostic: launches of the fused form by this process so far. */
 int64_t ac_gemm_qkv_attn_launches(void);
+/* AC_GEMM_F16X2 falls back to bf16x3 without a word (fewer than 192 token rows, a GEMM that does not take the ring-staged kernel,
+ * fp16 weight planes missing).  Diagnostic (ac_version() >= 16): host-side launches so far of a GEMM on fp16x2 operand planes --
+ * ac_linear_f16x2 and the encoder's plain, LayerNorm-fused and attention-fused GEMMs in that arithmetic.  One encoder chunk whose
+ * token-row GEMMs run in fp16x2 adds 4 (layers - 1) + 1 (the last layer's QKV or K|V GEMM; its CLS tail stays bf16x3), or
+ * 4 layers under AC_POOL_MEAN; a chunk that fell back adds 0. */
+int64_t ac_gemm_f16x2_launches(void);
 
 /* The persistent one-launch kernels of the latency-bound ends of the path are chosen automatically when the shape fits;
  * this switch (A/B tests, diagnosis) turns them off or on process-wide.  mask bit 0: ac_head_train_step / _epoch through

@@ -99,9 +99,12 @@ def relative_index(model, S, mut=()):
 
 
 @torch.no_grad()
-def deberta_forward(model, ids, types, mask, dtype=torch.float64, mm=R.mm_plain, mut=(), hidden_out=None, sqrt32=False):
-    """unit-norm CLS rows [b, H] of a DebertaV2Model on (ids, types, mask)"""
+def deberta_forward(model, ids, types, mask, dtype=torch.float64, mm=R.mm_plain, mut=(), hidden_out=None, sqrt32=False, lin_mm=None):
+    """unit-norm CLS rows [b, H] of a DebertaV2Model on (ids, types, mask).  lin_mm: encoder_ref._lin_mm, for the nn.Linear layers of
+    the token rows only -- the projections of the relative-position embeddings keep `mm` (on the device they are made once, outside
+    the token-row GEMMs), as do the three score products and P.V."""
     sd, cfg = model.state_dict(), model.config
+    lmm = R._lin_mm(mm, lin_mm)
     W = lambda k: sd[k].to(dtype)
     H, L, heads, eps = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, float(cfg.layer_norm_eps)
     b, S = ids.shape
@@ -128,15 +131,15 @@ def deberta_forward(model, ids, types, mask, dtype=torch.float64, mm=R.mm_plain,
     idx = relative_index(model, S, mut)[None, None].expand(b, heads, S, S)
     share = bool(getattr(cfg, "share_att_key", False))
 
-    def lin(t, name, bias=True):
-        y = mm(t, W(name + ".weight").T)
+    def lin(t, name, bias=True, token_rows=True):
+        y = lmm(t, W(name + ".weight").T, name) if token_rows else mm(t, W(name + ".weight").T)
         return y + W(name + ".bias") if bias else y
 
     def ln(t, name):
         return R._layer_norm(t, W(name + ".weight"), W(name + ".bias"), eps, mut)
 
     def pos_proj(name):
-        t = lin(rel, name, bias="pos_proj_bias_dropped" not in mut).view(2 * att_span, heads, dh).transpose(0, 1)      # [heads, 2 A, dh]
+        t = lin(rel, name, bias="pos_proj_bias_dropped" not in mut, token_rows=False).view(2 * att_span, heads, dh).transpose(0, 1)      # [heads, 2 A, dh]
         return torch.roll(t, 1, dims=0) if "pos_heads_rolled" in mut else t
 
     for l in range(L):

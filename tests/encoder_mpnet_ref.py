@@ -113,10 +113,12 @@ def _attention(q, k, v, bias, allow, scale, mm, probs_out):
 
 
 @torch.no_grad()
-def mpnet_forward(model, ids, mask, dtype=torch.float64, mm=R.mm_plain, mut=(), hidden_out=None, probs_out=None, packed=True):
+def mpnet_forward(model, ids, mask, dtype=torch.float64, mm=R.mm_plain, mut=(), hidden_out=None, probs_out=None, packed=True,
+                  lin_mm=None):
     """unit-norm CLS rows [b, H] of an MPNetModel on (ids, mask); `packed` only tells the bias_absolute_rows mutant which rows
-    the device call would see."""
+    the device call would see.  lin_mm: encoder_ref._lin_mm (the nn.Linear layers only; scores, bias and P.V keep `mm`)."""
     sd, cfg = model.state_dict(), model.config
+    lmm = R._lin_mm(mm, lin_mm)
     W = lambda k: sd[k].to(dtype)
     H, L, heads, eps = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, float(cfg.layer_norm_eps)
     b, S = ids.shape
@@ -134,7 +136,7 @@ def mpnet_forward(model, ids, mask, dtype=torch.float64, mm=R.mm_plain, mut=(), 
     bias = position_bias(model, b, S, dtype, mut, mask, packed)
 
     def lin(t, name):
-        return mm(t, W(name + ".weight").T) + W(name + ".bias")
+        return lmm(t, W(name + ".weight").T, name) + W(name + ".bias")
 
     def ln(t, name):
         return R._layer_norm(t, W(name + ".weight"), W(name + ".bias"), eps, mut)

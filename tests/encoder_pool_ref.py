@@ -44,12 +44,12 @@ POOL_MUTANTS = {
 # ------------------------------------------------------------------------------------------------------------------------
 # the pooled forward
 # ------------------------------------------------------------------------------------------------------------------------
-def _last_hidden(m, bs, dtype=torch.float64, mm=R.mm_plain):
-    """[b, S, H] after the last layer (ModernBERT: BEFORE the final norm), in `dtype`"""
+def _last_hidden(m, bs, dtype=torch.float64, mm=R.mm_plain, lin_mm=None):
+    """[b, S, H] after the last layer (ModernBERT: BEFORE the final norm), in `dtype` (lin_mm: encoder_ref._lin_mm)"""
     model = R.make_model(m)
     ids, types, mask = R.make_batch(bs)
     hs = []
-    R.FORWARD[m.family](model.state_dict(), model.config, ids, types, mask, dtype=dtype, mm=mm, hidden_out=hs)
+    R.FORWARD[m.family](model.state_dict(), model.config, ids, types, mask, dtype=dtype, mm=mm, hidden_out=hs, lin_mm=lin_mm)
     return hs[-1]
 
 

@@ -138,6 +138,12 @@ def _heads(x, heads):
     return x.view(b, S, heads, H // heads).transpose(1, 2)
 
 
+def _lin_mm(mm, lin_mm):
+    """the matmul of the nn.Linear layers: `lin_mm(t, w_t, name)` where a caller hooks it (name = the layer's parameter prefix;
+    tests/encoder_f16x2_ref.py states the fp16x2 arithmetic of the token-row GEMMs through it), else `mm` like every other matmul"""
+    return (lambda t, w_t, name: mm(t, w_t)) if lin_mm is None else lin_mm
+
+
 BERT_NAMES = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.position_embeddings.weight",
               "type": "embeddings.token_type_embeddings.weight", "eln": "embeddings.LayerNorm",
               "layer": "encoder.layer.{}.", "q": "attention.self.query", "k": "attention.self.key",
@@ -151,11 +157,13 @@ DISTIL_NAMES = {"word": "embeddings.word_embeddings.weight", "pos": "embeddings.
 
 @torch.no_grad()
 def post_norm_forward(sd, cfg, ids, types, mask, dtype=torch.float64, mm=mm_plain, mut=(), names=BERT_NAMES, positions=None,
-                      hidden_out=None, probs_out=None):
+                      hidden_out=None, probs_out=None, lin_mm=None):
     """The BERT block (post-norm, erf GELU, absolute positions) from a state_dict: BERT / ELECTRA (names=BERT_NAMES),
     DistilBERT (DISTIL_NAMES, no token types); `positions` [b, S] overrides arange(S) (RoBERTa).  hidden_out / probs_out: lists
-    that receive the hidden states after the embeddings and after every layer / every layer's attention probabilities."""
+    that receive the hidden states after the embeddings and after every layer / every layer's attention probabilities.
+    lin_mm: see _lin_mm (the attention's score and P.V matmuls keep `mm`)."""
     W = lambda k: sd[k].to(dtype)
+    lmm = _lin_mm(mm, lin_mm)
     if names is DISTIL_NAMES:
         H, L, heads, eps = cfg.dim, cfg.n_layers, cfg.n_heads, 1e-12
     else:
@@ -176,7 +184,7 @@ def post_norm_forward(sd, cfg, ids, types, mask, dtype=torch.float64, mm=mm_plai
     scale = 1.0 / math.sqrt(H if "scale_hidden" in mut else dh)
 
     def lin(t, name):
-        return mm(t, W(name + ".weight").T) + W(name + ".bias")
+        return lmm(t, W(name + ".weight").T, name) + W(name + ".bias")
 
     def ln(t, name):
         return _layer_norm(t, W(name + ".weight"), W(name + ".bias"), eps, mut)
@@ -237,18 +245,20 @@ def _rope(x, cos, sin, interleaved):
 
 
 @torch.no_grad()
-def modernbert_forward(sd, cfg, ids, types, mask, dtype=torch.float64, mm=mm_plain, mut=(), hidden_out=None, probs_out=None):
+def modernbert_forward(sd, cfg, ids, types, mask, dtype=torch.float64, mm=mm_plain, mut=(), hidden_out=None, probs_out=None,
+                       lin_mm=None):
     """ModernBERT: RoPE with the per-layer theta, global attention every n-th layer and the |q - k| <= local/2 window otherwise,
     pre-norm with no attention norm in layer 0, GeGLU with erf GELU, optional biases, the final norm."""
     W = lambda k: sd[k].to(dtype)
     O = lambda k: sd[k].to(dtype) if k in sd else None
+    lmm = _lin_mm(mm, lin_mm)
     H, L, heads, eps = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads, float(cfg.norm_eps)
     b, S = ids.shape
     dh = H // heads
     scale = 1.0 / math.sqrt(H if "scale_hidden" in mut else dh)
 
     def lin(t, name):
-        y = mm(t, W(name + ".weight").T)
+        y = lmm(t, W(name + ".weight").T, name)
         bias = O(name + ".bias")
         return y if bias is None else y + bias
 

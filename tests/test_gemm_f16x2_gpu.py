@@ -7,7 +7,13 @@ tests MEASURE it next to the fp32-input MFMA and the bf16x3 split against fp64, 
   * the encoder stays within SURVEY 8c's 1e-4 of transformers fp32 (measured: ~1e-6), for flat and peaked attention;
   * an operand beyond the fp16 range gives NaN rows, never a wrong finite number, and the encoder then repeats the call in
     bf16x3 by itself.
-The reference computes these products in torch fp32 (transformers BertModel called at classifier.py:1271)."""
+The reference computes these products in torch fp32 (transformers BertModel called at classifier.py:1271).
+
+Which layer of the evidence this is: tests/test_f16x2_model_cpu.py states what one product promises a priori; this file holds ONE
+GEMM to it per element against fp64, and the encoder to the 1e-4 contract on one family, one batch and four forward forms (a
+contract a lost low plane at every GEMM would still pass); tests/test_encoder_f16x2_gpu.py, with tests/encoder_f16x2_ref.py and
+tests/test_encoder_f16x2_cpu.py behind it, holds the whole encoder in this arithmetic to fp64 on every dispatch branch and family,
+asserts through ac_gemm_f16x2_launches that the arithmetic really ran, and uses an rms criterion that sees one lost low plane."""
 import ctypes
 
 import numpy as np

@@ -78,6 +78,10 @@ class ShardedSearch:
         if self.block_rows is not None and self.block_rows < 1:
             raise ValueError("block_rows must be >= 1")
         self._bufs = {}                # fixed-batch path: (name, shape, dtype) -> tensor, allocated once
+        # gather slots 0 / 1 alternate under prefetch handles; per slot: the generation of the handle that owns it and whether that
+        # handle has been searched.  Slot 2 is the handle-less search_block's own pair, taken only while both others are owned.
+        self._slot_gen, self._slot_consumed = [0, 0, 0], [True, True, True]
+        self._generation, self._next_slot = 0, 0
         self.stats = {"size_exchanges": 0, "buffer_allocations": 0, "prefetched_gathers": 0}
         self._prepared = None          # fp16 plane + norms of the local shard (batched searches, either metric), built on first use
         if local_search is None or merge is None:
@@ -280,36 +284,62 @@ class ShardedSearch:
         """Start the all-gather of a query block (padded to block_rows) WITHOUT waiting for it: under RCCL the collective runs on
         the communicator's own stream, so it proceeds while the caller's stream is still busy with the previous batch's sweep.
         Returns a handle for `search_block(..., gathered=handle)`.  Two buffers alternate, so one batch may be in flight while
-        the previous one is being searched."""
+        the previous one is being searched.  A handle owns its buffers until it has been searched: a third prefetch while two
+        handles are outstanding raises RuntimeError instead of overwriting the queries of one of them."""
         if self.block_rows is None:
             raise ValueError("prefetch_queries needs the fixed-batch path (construct with block_rows=...)")
+        slot = self._next_slot
+        if not self._slot_consumed[slot]:
+            slot ^= 1
+        if not self._slot_consumed[slot]:
+            raise RuntimeError("prefetch_queries: both gather buffers belong to handles that have not been searched yet; "
+                               "search one of them (search_block(..., gathered=handle)) before prefetching a third block")
+        h = self._gather_into(q_local, slot)
+        self._next_slot = slot ^ 1
+        return h
+
+    def _gather_into(self, q_local, slot):
+        """the gather of one padded block into the buffers of `slot`; the handle records the slot and its generation"""
         m, br, G = int(q_local.shape[0]), self.block_rows, self.world
         if m > br:
             raise ValueError(f"query block of {m} rows exceeds block_rows = {br}")
-        slot = self.stats["prefetched_gathers"] & 1
         self.stats["prefetched_gathers"] += 1
+        self._generation += 1
+        self._slot_gen[slot], self._slot_consumed[slot] = self._generation, False
+        own = {"m": m, "slot": slot, "gen": self._generation}
         dev = q_local.device
         pad = self._buf(f"qpad{slot}", (br, self.dim), q_local.dtype, dev)
         pad[:m].copy_(q_local)
         if m < br:
             pad[m:].zero_()
         if not self._collective:
-            return {"m": m, "all": pad, "work": None}
+            return dict(own, all=pad, work=None)
         if self._staged(pad):
             parts = [torch.empty((br, self.dim), dtype=pad.dtype) for _ in range(G)]
             dist.all_gather(parts, pad.cpu(), group=self.group)
             out = self._buf(f"qall{slot}", (G, br, self.dim), pad.dtype, dev)
             out.copy_(torch.stack(parts))
-            return {"m": m, "all": out.view(G * br, self.dim), "work": None}
+            return dict(own, all=out.view(G * br, self.dim), work=None)
         out = self._buf(f"qall{slot}", (G, br, self.dim), pad.dtype, dev)
         if pad.is_cuda:
             work = dist.all_gather_into_tensor(out, pad, group=self.group, async_op=True)
         else:
             work = dist.all_gather(list(out.unbind(0)), pad, group=self.group, async_op=True)
-        return {"m": m, "all": out.view(G * br, self.dim), "work": work}
+        return dict(own, all=out.view(G * br, self.dim), work=work)
 
     def _search_block_fixed(self, q_local, k, gathered=None):
-        h = gathered if gathered is not None else self.prefetch_queries(q_local)
+        if gathered is None:
+            # handle-less: a buffer pair no outstanding handle owns -- one of the two that is free, else the private third
+            free = [s for s in (self._next_slot, self._next_slot ^ 1) if self._slot_consumed[s]]
+            gathered = self._gather_into(q_local, free[0] if free else 2)
+        h = gathered
+        slot = h["slot"]
+        if self._slot_gen[slot] != h["gen"]:
+            raise RuntimeError("search_block: the gather buffers of this handle have been reissued to a later block; "
+                               "its queries are gone")
+        if self._slot_consumed[slot]:
+            raise RuntimeError("search_block: this handle has already been searched; prefetch the block again")
+        self._slot_consumed[slot] = True
         m, br, G = h["m"], self.block_rows, self.world
         if h["work"] is not None:
             h["work"].wait()                       # (RCCL: the caller's STREAM waits for the collective; the host does not)

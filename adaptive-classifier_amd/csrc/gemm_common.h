@@ -48,6 +48,26 @@ struct LnFuse {
     // relaxed poll, sc1 (L2-bypassing) payload loads: nothing of the payload ever sits in a non-coherent cache, so no cache write-back /
     // invalidate is needed (MI355X_MICROARCH.md "handoff-flag"; the grid barrier of grid_sync.h is built the same way).  1
     // (AC_EXCHANGE_FENCES=1, A/B): release on the arrival + acquire after the poll (buffer_wbl2 / buffer_inv: ~3.5 us per exchange).
+    // tests/test_exchange_fences_gpu.py runs both values and requires bit-identical results.
+    //
+    // What the fence-free form rests on -- every access below must keep its cache policy, or a reader sees stale partials
+    // (silently: the bounded wait only covers a MISSING arrival).  gemm_pipe.hip, line numbers of the two exchanges:
+    //   LayerNorm panel exchange (epilogue_bias_res_ln)
+    //     published   the (mean, M2) partial of every row: ONE 8-byte agent-scope atomic store into ln.part (:157) -- write-through;
+    //                 a plain float2 store there breaks the protocol.  s_waitcnt vmcnt(0) in every wave, then __syncthreads (:160-161)
+    //     arrival     thread 0's agent-scope fetch_add on ln.count[bm] (:165-166); relaxed is enough only because of the line above
+    //     poll        agent-scope atomic load of ln.count[bm] (:174), then a compiler barrier (:177)
+    //     consumed    the partials of the panel's other tiles: acp::ld2_sc1 (:195) -- L2-bypassing; a plain load may hit a line
+    //                 this CU cached during an earlier launch that used the same `part` block
+    //   QKV-attention straddle exchange (epilogue_qkv_attn, at.exchange != null)
+    //     published   the q | k | v rows of the straddling sequence's upper part: raw_buffer_store_b128 with aux = 16 (sc1) in
+    //                 spill_rows (:270; the plain store of :271 is the no-exchange form and is never polled for);
+    //                 s_waitcnt vmcnt(0) (:352) before the word
+    //     arrival     lane 0's agent-scope atomic store of at.epoch into at.exchange[tile * heads + head] (:354-355)
+    //     poll        agent-scope atomic load of that word (:279), then a compiler barrier (:290)
+    //     consumed    the rows, by batches of sc1 buffer loads in pull_rows (:291 ff.)
+    //   Both: abort_ is only ever touched by agent-scope atomics.  The control words (count, exchange) are zeroed / epoch-stamped
+    //   by the encoder call's prologue ON THE CALL'S STREAM before the launch (tests/test_stream_encoder_gpu.py).
     int fences;
 };
 

@@ -166,3 +166,80 @@ def test_fixed_batch_path_pipelined_no_size_exchange(world, batches, br):
         assert stats["prefetched_gathers"] == len(batches) + 1
         assert stats["buffer_allocations"] == allocs_after_loop <= 6          # two query pads, two gathered blocks, one send, one receive
         assert too_big is not None and "block_rows" in too_big
+
+
+def _worker_slots(rank, world, port, N, D, br, k, ret):
+    """Gather-slot ownership on the fixed-batch path: two prefetched handles outstanding, a handle-less search between them."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [root, os.path.join(root, "adaptive-classifier_amd")]
+    from adaptive_classifier.sharded import ShardedSearch, shard_bounds
+    from oracle import knn_oracle, synth
+    os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    lo, hi = shard_bounds(N, world, rank)
+    rows = torch.from_numpy(synth.synth_unit_rows(hi - lo, D, 1, row_offset=lo))
+
+    def local_search(P, n, Dd, Q, kk, off):
+        d, i = knn_oracle.knn_l2_topk(P.numpy()[:n], Q.numpy(), kk, row_offset=off, return_exact=True)
+        return torch.from_numpy(d), torch.from_numpy(i)
+
+    def merge(Ds, Is):
+        d, i = knn_oracle.topk_merge(Ds.numpy(), Is.numpy(), Ds.shape[2])
+        return torch.from_numpy(d), torch.from_numpy(i)
+
+    ss = ShardedSearch(rows, hi - lo, D, lo, local_search=local_search, merge=merge, block_rows=br)
+    # block b of the global query stream: rank r owns rows [b * world * br + r * br, + br); q3 is short (br - 1 rows)
+    q1, q2, q3 = (torch.from_numpy(synth.synth_unit_rows(br - (b == 2), D, 2, row_offset=(b * world + rank) * br)) for b in range(3))
+    h1, h2 = ss.prefetch_queries(q1), ss.prefetch_queries(q2)
+    third = None
+    try:                                                    # (ii) both slots owned and unsearched: loud, before any collective
+        ss.prefetch_queries(q3)
+    except RuntimeError as e:
+        third = str(e)
+    gathers_before = ss.stats["prefetched_gathers"]
+    r3 = ss.search_block(q3, k)                             # (i) handle-less while two handles are outstanding
+    r1 = ss.search_block(None, k, gathered=h1)
+    r2 = ss.search_block(None, k, gathered=h2)
+    twice = None
+    try:                                                    # (iii)
+        ss.search_block(None, k, gathered=h1)
+    except RuntimeError as e:
+        twice = str(e)
+    h4 = ss.prefetch_queries(q1)                            # the slots are free again; a handle whose slot was reissued raises
+    r4 = ss.search_block(None, k, gathered=h4)
+    h5, h6 = ss.prefetch_queries(q2), ss.prefetch_queries(q3)
+    reissued = None
+    try:
+        ss.search_block(None, k, gathered=h4)
+    except RuntimeError as e:
+        reissued = str(e)
+    r5, r6 = ss.search_block(None, k, gathered=h5), ss.search_block(None, k, gathered=h6)
+    ret[rank] = ([(d.numpy(), i.numpy()) for d, i in (r1, r2, r3, r4, r5, r6)], third, twice, reissued,
+                 ss.stats["prefetched_gathers"] - gathers_before, ss.stats["buffer_allocations"])
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_a_gather_slot_is_never_reused_under_an_unsearched_handle(world):
+    from oracle import knn_oracle, synth
+    N, D, k, br = 1003, 64, 8, 4
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_worker_slots, args=(world, _free_port(), N, D, br, k, ret), nprocs=world, join=True)
+    P = synth.synth_unit_rows(N, D, 1)
+    Q = synth.synth_unit_rows(3 * world * br, D, 2)
+    oD, oI = knn_oracle.knn_l2_topk(P, Q, k)
+    for r in range(world):
+        outs, third, twice, reissued, gathers, allocs = ret[r]
+        for (d, i), b in zip(outs, (0, 1, 2, 0, 1, 2)):                         # every result is that of ITS OWN block
+            lo, m = (b * world + r) * br, br - (b == 2)
+            assert i.shape == (m, k), (b, i.shape)
+            assert np.array_equal(i, oI[lo:lo + m]) and np.array_equal(d, oD[lo:lo + m]), f"rank {r}: block {b + 1} got another block's neighbours"
+        assert third is not None and "prefetch_queries" in third
+        assert twice is not None and "already been searched" in twice
+        assert reissued is not None and "reissued" in reissued
+        assert gathers == 4                                                     # the handle-less search, h4, h5, h6; a refused prefetch gathers nothing
+        # buffers: two alternating pads + the handle-less call's own (+ the same three gathered blocks, send and receive at world 2)
+        assert allocs == (3 if world == 1 else 8)

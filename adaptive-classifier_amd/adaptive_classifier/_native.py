@@ -90,6 +90,10 @@ class ac_unigram_vocab(ctypes.Structure):
                 ("pad_id", c_int), ("lowercase", c_int), ("trailing_space_piece", c_int), ("ws_controls", c_int)]
 
 
+class ac_bpe_unicode(ctypes.Structure):
+    _fields_ = [("page_of", c_void_p), ("entries", c_void_p), ("n_pages", c_int)]
+
+
 class ac_unigram_unicode(ctypes.Structure):
     _fields_ = [("page_of", c_void_p), ("entries", c_void_p), ("images", c_void_p), ("n_pages", c_int), ("image_bytes", c_int)]
 
@@ -269,6 +273,10 @@ _SIGNATURES = {
     "ac_bpe_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
     "ac_bpe_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), c_int, c_void_p, c_void_p, c_void_p]),
+    "ac_bpe_utf8_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), ctypes.POINTER(ac_bpe_unicode), c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ac_bpe_utf8_encode_host": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_bpe_vocab), ctypes.POINTER(ac_bpe_unicode), c_int,
+                                        c_void_p, c_void_p, c_void_p]),
     "ac_unigram_hash": (c_uint64, [c_void_p, c_int]),
     "ac_unigram_encode": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(ac_unigram_vocab), c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),

@@ -118,7 +118,7 @@ class AdaptiveClassifier:
             # ModernBERT-style (ac_bpe_encode) -- and Metaspace + Unigram tokenizers -- DeBERTa-v2/v3, XLM-R style
             # (ac_unigram_encode) -- are tokenised on the device; anything else stays as given
             from .tokenizer import maybe_device_tokenizer
-            # config["device_tokenizer_unicode"]: WordPiece and Unigram tokenizers take non-ASCII texts on the device too (opt-in)
+            # config["device_tokenizer_unicode"]: WordPiece, byte-level BPE and Unigram tokenizers take non-ASCII texts on the device too (opt-in)
             tokenizer = maybe_device_tokenizer(tokenizer, self.device, unicode=bool((config or {}).get("device_tokenizer_unicode", False)))
         self.tokenizer = tokenizer
         self.embedding_dim = self.model.config.hidden_size

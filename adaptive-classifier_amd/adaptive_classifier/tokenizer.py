@@ -7,7 +7,8 @@ Replace `self.tokenizer(texts, max_length=..., truncation=True, padding=True, re
   tokenizers BertNormalizer + BertPreTokenizer + WordPiece), ids from `ac_wordpiece_encode` (ASCII texts) and, with
   `unicode=True`, from `ac_wordpiece_encode_utf8` (UTF-8 texts: below);
 * `HipByteBPETokenizer` -- GPT-2 byte-level BPE (RoBERTa-style and ModernBERT-style tokenizers: tokenizers
-  ByteLevel(use_regex=True) + BPE behind RobertaProcessing or a `<cls> $A <sep>` template), ids from `ac_bpe_encode`.
+  ByteLevel(use_regex=True) + BPE behind RobertaProcessing or a `<cls> $A <sep>` template), ids from `ac_bpe_encode` (ASCII
+  texts) and, with `unicode=True`, from `ac_bpe_utf8_encode` (UTF-8 texts: below).
   The vocabulary strings and merge sides are turned back into raw bytes (ByteLevel's byte <-> unicode map inverted), so the
   kernel works on the text's own bytes; `ac_bpe_encode_host` runs the same algorithm on the CPU;
 * `HipUnigramTokenizer` -- SentencePiece-style Unigram (DeBERTa-v2/v3 and XLM-R style tokenizers: tokenizers
@@ -37,7 +38,7 @@ wrapped tokenizer on it or the ASCII-only routing stays).  A pure-ASCII batch st
 wrapped tokenizer: texts with a host-only code point (a surviving combining mark that NFD may reorder; only with accent
 stripping), over 4096 bytes or with a literal special token -- decided per text by one compiled regular expression -- and what the
 kernel reports as not done (normalised text over 8192 bytes; malformed UTF-8 cannot come out of a str).  It is opt-in because the
-default routing of non-ASCII texts is pinned by existing tests; the BPE kernel is ASCII-only either way.
+default routing of non-ASCII texts is pinned by existing tests.
 
 Unigram on Unicode text (the same opt-in switch: `HipUnigramTokenizer(hf, unicode=True)`).  The whole normalizer chain (Precompiled /
 NFC / NFKC / Nmt / Lowercase / Replace / Strip) becomes a paged table by probing the wrapped pipeline (`build_unigram_unicode_tables`:
@@ -48,6 +49,17 @@ in blocks of 64 piece ends (csrc/unigram_core.h, csrc/unigram_utf8.hip; `ac_unig
 and a probe list must reproduce the wrapped tokenizer on it or the ASCII-only routing stays).  What still goes to the wrapped
 tokenizer: texts with a host-only code point, over 4096 bytes or with a literal special token, and what the kernel reports as
 not done (normalised text over 5120 bytes).
+
+Byte-level BPE on Unicode text (the same opt-in switch: `HipByteBPETokenizer(hf, unicode=True)`).  The merges already work on raw
+bytes; the only Unicode knowledge of the pipeline is the class of each code point in the pre-tokeniser pattern (whitespace, letter,
+number, other), which `build_bpe_unicode_tables` probes from the wrapped pre-tokenizer into a paged one-byte table.
+`ac_bpe_utf8_encode` decodes strictly, classifies every character and runs the pattern on characters, then the merge rounds of the
+ASCII kernel on the same bytes (csrc/bpe_core.h, csrc/bpe_utf8.hip; `ac_bpe_utf8_encode_host` is the same code on the CPU, and a
+probe list must reproduce the wrapped tokenizer on it or the ASCII-only routing stays).  The device does no normalisation: with an
+NFC normalizer (ModernBERT style) every code point NFC changes or may combine with a neighbour is host-only, so a device text is
+its own NFC.  What still goes to the wrapped tokenizer: texts with a host-only code point, over 4096 bytes or with a literal special
+token, and what the kernel reports as not done (a pre-token of more than 64 bytes: an unsegmented CJK or Thai run of more than
+about 21 characters).
 """
 import ctypes
 import json
@@ -457,6 +469,173 @@ def build_bpe_tables(spec):
 def bpe_vocab_struct(spec, pointers, slots):
     """ac_bpe_vocab over the four arrays' addresses (device or host), in build_bpe_tables order."""
     return nv.ac_bpe_vocab(*pointers, slots, spec["cls_id"], spec["sep_id"], spec["pad_id"], 1 if spec["add_prefix_space"] else 0)
+
+
+# ---- the classes of the GPT-2 pre-tokeniser pattern as a probed table (csrc/bpe_core.h) ---------------------------------------
+_BPE_WS, _BPE_LETTER, _BPE_DIGIT, _BPE_OTHER, _BPE_HOST_ONLY = 0, 1, 2, 3, 4      # bpe::kWs ... bpe::kHostOnly
+_BPE_UNICODE_CACHE = {}
+
+
+def _joins_carrier(pre, carrier, chars):
+    """For every character of `chars`: does the pre-tokenizer keep it in one piece with a `carrier` in front?  One call for the
+    whole list: the probes stand back to back (carrier, character, carrier, character ...) and the piece offsets (in characters
+    of the probe string) say where the pipeline cut.  Whether it cuts between a carrier and the character behind it depends on
+    those two alone; that this is so for the whole list is checked on each end of it by asking those probes alone again."""
+    cuts = {start for _, (start, _) in pre("".join(carrier + ch for ch in chars))}
+    got = [2 * i + 1 not in cuts for i in range(len(chars))]
+    for i in (0, len(chars) - 1):
+        if (len(pre(carrier + chars[i])) == 1) != got[i]:
+            return [len(pre(carrier + ch)) == 1 for ch in chars]
+    return got
+
+
+def build_bpe_unicode_tables(hf_tokenizer):
+    """The pre-tokeniser classes of a byte-level BPE tokenizer as the table behind ac_bpe_unicode, on the host (numpy); needs no
+    GPU.  A dict: page_of uint16 [0x1100], entries uint8 [n_pages, 256], n_pages, host_only (the flagged code points, sorted),
+    reasons (counts per probe), whitespace (the code points of class \\s, sorted), seconds (of the build).  An entry: bits 0-1
+    whitespace | letter | number | other, bit 2 host-only.
+
+    No Unicode data of our own: a Python `unicodedata` of another Unicode version would silently disagree with the library's
+    tables.  The only Unicode knowledge of the pipeline is the class of a code point d in the pattern, and the wrapped
+    pre-tokenizer itself shows it: d is a letter iff pre_tokenize_str("a" + d) stays one piece, a number iff "1" + d does, other
+    iff "!" + d does, and whitespace iff none does.  The probes of a page go in one call per carrier (`_joins_carrier`).
+    With an NFC normalizer the device does no normalisation: a text either is its own NFC or goes to the host.  Host-only are
+    * every code point whose normalize_str image differs from itself,
+    * every code point in a non-first position of the library's NFD of some code point (it may compose with what stands in
+      front), every non-starter (it changes places with U+0345 in front or U+0334 behind under the library's NFD) and every code
+      point whose decomposition opens with one of those,
+    * the surrogates (no UTF-8 text holds one: the decoder rejects them).
+    In a text without any of them every code point is NFC-stable and no neighbours interact, so the text is its own NFC.
+    The result is cached in-process by the serialised normalizer + pre-tokenizer (the sweep takes a few seconds)."""
+    import time
+    from tokenizers import normalizers
+    cfg = _backend_config(hf_tokenizer) or {}
+    key = json.dumps([cfg.get("normalizer"), cfg.get("pre_tokenizer")], sort_keys=True)
+    if key in _BPE_UNICODE_CACHE:
+        return _BPE_UNICODE_CACHE[key]
+    t0 = time.perf_counter()
+    be = hf_tokenizer.backend_tokenizer
+    pre = be.pre_tokenizer.pre_tokenize_str
+    kind = np.full(0x110000, _BPE_OTHER, np.uint8)
+    for page in range(0x1100):
+        cps = [cp for cp in range(page * 256, page * 256 + 256) if not 0xD800 <= cp < 0xE000]
+        if not cps:
+            continue
+        chars = list(map(chr, cps))
+        # most pages are of one class (CJK, Hangul: letters; unassigned, private use, symbols: other): the whole page behind one
+        # carrier stays one piece iff every code point of it joins that carrier
+        run = "".join(chars)
+        if len(pre("a" + run)) == 1:
+            kind[cps] = _BPE_LETTER
+            continue
+        if len(pre("!" + run)) == 1:
+            continue
+        letter, digit, other = (_joins_carrier(pre, carrier, chars) for carrier in "a1!")
+        for cp, l, d, o in zip(cps, letter, digit, other):
+            if l + d + o > 1:
+                raise nv.NativeError("build_bpe_unicode_tables: U+%04X joins more than one class of the pre-tokenizer" % cp)
+            kind[cp] = _BPE_LETTER if l else _BPE_DIGIT if d else _BPE_OTHER if o else _BPE_WS
+    host = np.zeros(0x110000, bool)
+    host[0xD800:0xE000] = True
+    reasons = {}
+
+    def flag(which, why):
+        which = [c for c in which if not host[c]]
+        host[which] = True
+        reasons[why] = reasons.get(why, 0) + len(which)
+
+    if be.normalizer is not None:
+        norm = be.normalizer.normalize_str
+        cps = list(range(0xD800)) + list(range(0xE000, 0x110000))
+        chars = list(map(chr, cps))
+        flag([cp for cp, ch in zip(cps, chars) if norm(ch) != ch], "image")
+        # composition seconds and non-starters, by the library's own NFD (as build_unigram_unicode_tables finds them)
+        nfd = normalizers.NFD().normalize_str
+        decs = list(map(nfd, chars))
+        seconds = {ord(d) for dec in decs if len(dec) > 1 for d in dec[1:]}
+        hi, lo = "\u0345", "\u0334"                              # combining classes 240 and 1
+        nonstart = set()
+        for page in range(0x1100):
+            ds = [ch for ch in map(chr, range(page * 256, page * 256 + 256)) if not 0xD800 <= ord(ch) < 0xE000]
+            ds = [d for d in ds if nfd(d) == d]
+            marked = "".join(hi + d + lo for d in ds)
+            if nfd(marked) != marked:
+                nonstart |= {ord(d) for d in ds if nfd(hi + d) != hi + d or nfd(d + lo) != d + lo}
+        flag(sorted(seconds), "composes")
+        flag(sorted(nonstart), "non-starter")
+        flag([cp for cp, dec in zip(cps, decs) if dec and (ord(dec[0]) in nonstart or ord(dec[0]) in seconds)], "decomposes to one")
+    whitespace = [int(c) for c in np.flatnonzero(kind == _BPE_WS) if not 0xD800 <= c < 0xE000]
+    kind[host] |= _BPE_HOST_ONLY
+    pages, page_of = np.unique(kind.reshape(0x1100, 256), axis=0, return_inverse=True)
+    host_only = [int(c) for c in np.flatnonzero(host) if not 0xD800 <= c < 0xE000]
+    tables = {"page_of": page_of.reshape(-1).astype(np.uint16), "entries": np.ascontiguousarray(pages, np.uint8),
+              "n_pages": int(len(pages)), "host_only": host_only, "reasons": reasons, "whitespace": whitespace,
+              "seconds": time.perf_counter() - t0}
+    _BPE_UNICODE_CACHE[key] = tables
+    return tables
+
+
+def bpe_unicode_struct(tables, pointers=None):
+    """ac_bpe_unicode over the two arrays' addresses (device), or over the host arrays themselves."""
+    if pointers is None:
+        pointers = [tables[k].ctypes.data for k in ("page_of", "entries")]
+    return nv.ac_bpe_unicode(*pointers, tables["n_pages"])
+
+
+def _bpe_unicode_probes():
+    """The fixed probe list of the guard: typographic punctuation, accents, Cyrillic, Greek, CJK, kana, Hangul, emoji, Unicode
+    whitespace of each kind (leading, trailing, doubled, next to 0x20), numbers of several scripts, contractions next to
+    non-ASCII letters -- and strings that must defer where the table flags them (combining sequences, jamo)."""
+    base = ["", "a", "Hello, World!", "it\u2019s \u201cquoted\u201d \u2014 dash\u2026 en\u2013dash", "caf\u00e9 na\u00efve r\u00e9sum\u00e9",
+            "CAF\u00c9 NA\u00cfVE", "\u00e9's 's\u00e9 \u4e2d's x\u2019s x'r\u00e9 x're\u00e9 we\u2019ll we'll\u00e9",
+            "\u00c5ngstr\u00f6m \u0152uvre Stra\u00dfe \u0130stanbul", "\u041f\u0440\u0438\u0432\u0435\u0442, \u041c\u0418\u0420! \u0401\u043b\u043a\u0430",
+            "\u03a3\u038a\u03a3\u03a5\u03a6\u039f\u03a3 \u03c3\u03af\u03c3\u03c5\u03c6\u03bf\u03c2", "\u4e2d\u6587 mixed \u6587\u672c with \u65e5\u672c\u8a9e",
+            "\u3072\u3089\u304c\u306a \u30ab\u30bf\u30ab\u30ca", "\ud55c\uad6d\uc5b4 \ud14d\uc2a4\ud2b8",
+            "emoji \U0001f600 \U0001f1e9\U0001f1ea here \U0001f44d\U0001f3fd",
+            "a\u3000b\u00a0c\u2003d\u2028e\u0085f\u1680g\u202fh\u205fi", "\u00a0lead", "trail\u3000", "a\u00a0\u00a0b", "a \u2003 b", "\u3000\u3000",
+            "a\u00a0 b", "a \u00a0b", "\u2028", "a \u2029", "\u00a0's \u00a0\u00a0 's", "zero\u200bwidth soft\u00adhyphen \ufeffbom",
+            "12\u00b2 \u0661\u0662\u06634 \u2167 \u2460 \u00bd x\u00b2y 3\u00e9", "\u20ac100 \u00a35 \u00a57 \u2122 \u2103 \u00a9 \u00ab x \u00bb \u00bfQu\u00e9?",
+            "\U00020000\U0002a6d6 x\U00020000y", "\u0e20\u0e32\u0e29\u0e32 \u0939\u093f\u0928\u094d\u0926\u0940", "full \uff57\uff49\uff44\uff54\uff48 \uff11\uff12\uff13",
+            "e\u0301 combining", "A\u0301\u0323", "\u212b \u2126", "\u1100\u1161 jamo", "\uac00\u11a8"]
+    return base + [" ".join(base[i:i + 3]) for i in range(3, 30, 3)]
+
+
+def _bpe_unicode_matches(hf, spec, vocab_struct, tables, probes):
+    """Does ac_bpe_utf8_encode_host (host tables) give the wrapped tokenizer's ids, mask and lengths on these probes, and report
+    as not done exactly those that hold a host-only code point?  A probe that fills max_length counts as a mismatch."""
+    M = _PROBE_MAX_LENGTH
+    probes = [t for t in probes if not any(sp in t for sp in spec["specials"])]
+    flagged = _host_only_regex(tables)
+    raws = [t.encode("utf-8") for t in probes]
+    offs = np.zeros(len(raws) + 1, np.int32)
+    offs[1:] = np.cumsum([len(r) for r in raws])
+    blob = np.frombuffer(b"".join(raws) + b"\0" * 64, np.uint8).copy()
+    ids = np.zeros((len(raws), M), np.int64)
+    mask = np.zeros((len(raws), M), np.int64)
+    lens = np.zeros(len(raws), np.int32)
+    uni = bpe_unicode_struct(tables)
+    nv.check(nv.lib().ac_bpe_utf8_encode_host(blob.ctypes.data, offs.ctypes.data, len(raws), ctypes.byref(vocab_struct), ctypes.byref(uni),
+                                              M, ids.ctypes.data, mask.ctypes.data, lens.ctypes.data), "ac_bpe_utf8_encode_host")
+    want = hf(probes, max_length=M, truncation=True, padding="max_length", return_tensors="np")
+    for i, t in enumerate(probes):
+        if flagged is not None and flagged.search(t):
+            if lens[i] != -1:
+                return False
+        elif lens[i] < 0 or lens[i] >= M or not np.array_equal(want["input_ids"][i], ids[i]) \
+                or not np.array_equal(want["attention_mask"][i], mask[i]):
+            return False
+    return True
+
+
+def bpe_unicode_tables(hf, spec, vocab_struct):
+    """build_bpe_unicode_tables(hf) behind its probe guard: the tables if the host entry over them (and the host merge table
+    behind `vocab_struct`) reproduces the wrapped tokenizer on the probe list, else None -- the tokenizer then keeps its
+    ASCII-only routing."""
+    try:
+        tables = build_bpe_unicode_tables(hf)
+        return tables if _bpe_unicode_matches(hf, spec, vocab_struct, tables, _bpe_unicode_probes()) else None
+    except Exception:
+        return None
 
 
 # ---- SentencePiece-style Unigram (DeBERTa-v2/v3, XLM-R) ---------------------------------------------------------------------
@@ -1069,10 +1248,17 @@ class HipWordPieceTokenizer(_DeviceTokenizer):
 
 class HipByteBPETokenizer(_DeviceTokenizer):
     """GPT-2 byte-level BPE on the device (ac_bpe_encode): RoBERTa-style and ModernBERT-style tokenizers.  Returns the keys
-    the wrapped tokenizer returns (no token_type_ids where its model_input_names has none)."""
+    the wrapped tokenizer returns (no token_type_ids where its model_input_names has none).
+
+    With `unicode=True` a batch that holds non-ASCII text goes through ac_bpe_utf8_encode: the classes of the pre-tokeniser
+    pattern as the probed table of build_bpe_unicode_tables, the merges on the text's own bytes as before.  A non-ASCII text is a
+    device text if it has at most 4096 bytes, no literal special / added-token string and no host-only code point (one compiled
+    character class; with an NFC normalizer: what NFC changes or may combine); a pre-token of more than 64 bytes comes back
+    from the kernel as not done.  Opt-in: without it every non-ASCII text takes the host route, as before.  `unicode` reads False
+    afterwards if the probe guard rejected the tables."""
     _defers = True
 
-    def __init__(self, hf_tokenizer, device=None):
+    def __init__(self, hf_tokenizer, device=None, unicode=False):
         nv.require_gpu()
         spec = _bpe_spec(hf_tokenizer)
         if spec is None:
@@ -1083,10 +1269,35 @@ class HipByteBPETokenizer(_DeviceTokenizer):
         keys, entries, blob, byte_id, slots = build_bpe_tables(spec)
         self._t = [torch.from_numpy(a).to(self.device) for a in (keys.view(np.int64), entries, blob, byte_id)]
         self.vocab = bpe_vocab_struct(spec, [t.data_ptr() for t in self._t], slots)
+        self.unicode = False
+        if unicode:
+            self._enable_unicode(spec, (keys, entries, blob, byte_id), slots)
+
+    # ---- class table -> device (behind the probe guard, which runs on the host arrays) ----
+    def _enable_unicode(self, spec, arrays, slots):
+        host_vocab = bpe_vocab_struct(spec, [a.ctypes.data for a in arrays], slots)
+        tables = bpe_unicode_tables(self.hf, spec, host_vocab)
+        if tables is None:
+            return
+        self._ut = [torch.from_numpy(a).to(self.device) for a in (tables["page_of"].view(np.int16), tables["entries"])]
+        self.unicode_tables = bpe_unicode_struct(tables, [t.data_ptr() for t in self._ut])
+        self._host_only = _host_only_regex(tables)
+        self.unicode = self._utf8 = True
+
+    def _device_ok(self, text, raw):
+        if not self._utf8 or raw.isascii():
+            return super()._device_ok(text, raw)
+        return len(raw) <= MAX_DEVICE_BYTES and not (self._host_only is not None and self._host_only.search(text)) \
+            and not any(sp in text for sp in self.specials)
 
     def _encode(self, d_text, d_offs, b, M, ids, mask, lens, ascii_only=True):
-        nv.check(nv.lib().ac_bpe_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
-                                        nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_bpe_encode")
+        if ascii_only:
+            nv.check(nv.lib().ac_bpe_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab), M, nv.ptr(ids),
+                                            nv.ptr(mask), nv.ptr(lens), nv.stream_ptr(self.device)), "ac_bpe_encode")
+        else:
+            nv.check(nv.lib().ac_bpe_utf8_encode(nv.ptr(d_text), nv.ptr(d_offs), b, ctypes.byref(self.vocab),
+                                                 ctypes.byref(self.unicode_tables), M, nv.ptr(ids), nv.ptr(mask), nv.ptr(lens),
+                                                 nv.stream_ptr(self.device)), "ac_bpe_utf8_encode")
 
 
 class HipUnigramTokenizer(_DeviceTokenizer):
@@ -1151,14 +1362,14 @@ class HipUnigramTokenizer(_DeviceTokenizer):
 def maybe_device_tokenizer(hf_tokenizer, device, unicode=False):
     """HipWordPieceTokenizer around a BERT WordPiece tokenizer, HipByteBPETokenizer around a GPT-2 byte-level BPE tokenizer,
     HipUnigramTokenizer around a Metaspace + Unigram tokenizer, anything else unchanged.  unicode: non-ASCII texts on the device
-    too where the family has a kernel for them (WordPiece and Unigram; the BPE kernel is ASCII-only)."""
+    too (all three families have a kernel for them; each keeps its ASCII-only routing if its probe guard rejects the tables)."""
     if hf_tokenizer is None or isinstance(hf_tokenizer, _DeviceTokenizer):
         return hf_tokenizer
     try:
         if _wordpiece_spec(hf_tokenizer) is not None:
             return HipWordPieceTokenizer(hf_tokenizer, device, unicode=unicode)
         if _bpe_spec(hf_tokenizer) is not None:
-            return HipByteBPETokenizer(hf_tokenizer, device)
+            return HipByteBPETokenizer(hf_tokenizer, device, unicode=unicode)
         structure = _unigram_structure(hf_tokenizer)
         if structure is not None:                             # (the probe guard runs inside the constructor)
             return HipUnigramTokenizer(hf_tokenizer, device, structure, unicode=unicode)

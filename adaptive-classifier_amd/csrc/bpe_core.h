@@ -1,5 +1,6 @@
 // GPT-2 byte-level BPE on ASCII text, written once for the kernel (bpe.hip), the host entry point (ac_bpe_encode_host) and any
-// plain C++ program: no HIP runtime header is needed, BPE_HD is empty without hipcc.
+// plain C++ program: no HIP runtime header is needed, BPE_HD is empty without hipcc.  The second half of the file is the same for
+// UTF-8 text (bpe_utf8.hip).
 //
 //   pre-tokeniser   's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+   restricted to bytes < 128:
 //                   whether a token starts at byte p is a function of t[p-4 .. p+2] alone (is_start), so every boundary of a
@@ -123,6 +124,146 @@ inline int encode_text(const Table& t, const uint8_t* c, int n, int room, int64_
         while (p1 < n && !is_start(c, n, p1)) ++p1;
         for (int i = p0; i < p1; ++i) { id_at[i] = t.byte_id[c[i]]; next_at[i] = i + 1; }
         auto pair_of = [&](int i) {                             // rank of (symbol at i, symbol after it), kNoRank if none
+            rank_at[i] = kNoRank;
+            const int j = next_at[i];
+            if (j < p1) {
+                int r, m;
+                if (lookup(t, c + i, j - i, next_at[j] - i, r, m)) { rank_at[i] = r; mid_at[i] = m; }
+            }
+        };
+        for (int i = p0; i < p1; ++i) pair_of(i);
+        for (;;) {
+            int best = -1, before_best = -1;
+            for (int i = p0, prev = -1; i < p1; prev = i, i = next_at[i])
+                if (rank_at[i] != kNoRank && (best < 0 || rank_at[i] < rank_at[best])) { best = i; before_best = prev; }
+            if (best < 0) break;
+            id_at[best] = mid_at[best];
+            next_at[best] = next_at[next_at[best]];
+            pair_of(best);
+            if (before_best >= 0) pair_of(before_best);
+        }
+        for (int i = p0; i < p1 && total < room; i = next_at[i]) out[total++] = id_at[i];
+        p0 = p1;
+    }
+    return total;
+}
+
+// ---- UTF-8 texts (ac_bpe_utf8_encode[_host], ac_version() >= 17) ---------------------------------------------------------------
+// The same pipeline over Unicode text, written once for bpe_utf8_kernel (bpe_utf8.hip), ac_bpe_utf8_encode_host and any plain C++
+// program.  The merges work on raw bytes and need no change; the only Unicode knowledge of the pipeline is the class of each code
+// point in the pre-tokeniser pattern (\s, \p{L}, \p{N}, other), and that comes from a table the host wrapper probes from the
+// wrapped pipeline (tokenizer.py, build_bpe_unicode_tables): nothing here knows a Unicode property.
+//
+//   decoding        strict UTF-8 (decode_utf8): an overlong form, an encoded surrogate, a value above U+10FFFF, a stray
+//                   continuation byte or a truncated tail makes the text NOT DONE -- never a guess
+//   classes         one byte per text byte (classify_text / the kernel's class pass): bits 0-1 the class of the CHARACTER the byte
+//                   belongs to, kContByte on every byte but the character's first.  class_at[p - 1] is thus the class of the
+//                   character that ends at p - 1, and every later question is a read of the two arrays
+//   host-only       a code point the device does not reproduce (the normalizer changes it or may combine it with its neighbour):
+//                   the text is NOT DONE
+//   boundaries      is_start_utf8 = is_start stated on characters; pre-token boundaries are character boundaries, so the merge
+//                   loop is encode_text's on the same bytes
+
+// ac_bpe_unicode: page_of[cp >> 8] names one of n_pages pages of 256 one-byte entries (identical pages are stored once).
+// An entry: bits 0-1 kWs / kLetter / kDigit / kOther, kHostOnly on top.
+struct Unicode {
+    const uint16_t* page_of;    // [0x1100]
+    const uint8_t* entries;     // [n_pages][256]
+    int n_pages;
+};
+
+constexpr int kClassMask = 3;
+constexpr int kHostOnly = 4;    // in a table entry
+constexpr int kContByte = 4;    // in a text's class array: not the first byte of its character
+
+BPE_HD bool is_cont(uint8_t c) { return (c & 0xC0) == 0x80; }
+// bytes of the character whose lead byte is c (only asked of validated text)
+BPE_HD int char_len(uint8_t c) { return c < 0xC0 ? 1 : c < 0xE0 ? 2 : c < 0xF0 ? 3 : 4; }
+
+// Strict UTF-8: the length of the sequence that starts at p (`avail` bytes are left of the text) and its code point; 0 for a
+// continuation byte, a truncated sequence, an overlong form, an encoded surrogate or a value above U+10FFFF.  Reads p[0, min(len, avail)).
+BPE_HD int decode_utf8(const uint8_t* p, int avail, uint32_t& cp) {
+    const uint32_t b0 = p[0];
+    if (b0 < 0x80) { cp = b0; return 1; }
+    int len;
+    uint32_t lo;
+    if (b0 >= 0xC2 && b0 <= 0xDF) { len = 2; cp = b0 & 0x1f; lo = 0x80; }
+    else if ((b0 & 0xF0) == 0xE0) { len = 3; cp = b0 & 0x0f; lo = 0x800; }
+    else if (b0 >= 0xF0 && b0 <= 0xF4) { len = 4; cp = b0 & 0x07; lo = 0x10000; }
+    else return 0;
+    if (len > avail) return 0;
+    for (int i = 1; i < len; ++i) {
+        const uint32_t b = p[i];
+        if ((b & 0xC0) != 0x80) return 0;
+        cp = (cp << 6) | (b & 0x3f);
+    }
+    if (cp < lo || cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) return 0;
+    return len;
+}
+
+// the table entry of a code point <= U+10FFFF; a page number outside the table reads as host-only
+BPE_HD int entry_of(const Unicode& u, uint32_t cp) {
+    const int page = u.page_of[cp >> 8];
+    return page < u.n_pages ? u.entries[(size_t)page * 256 + (cp & 0xff)] : kHostOnly;
+}
+
+// t[p] == '\'': does a token start at this apostrophe?  apos_start with the class of the CHARACTER in front.
+BPE_HD bool apos_start_utf8(const uint8_t* t, const uint8_t* class_at, int p) {
+    if (p == 0) return true;
+    const int kd = class_at[p - 1] & kClassMask;
+    return kd == kLetter || kd == kDigit || (kd == kWs && t[p - 1] != 0x20);
+}
+
+// Does a pre-token start at byte p of t[0, n)?  0 <= p < n; class_at[0, n) as classify_text leaves it.  A continuation byte is
+// never a start.  The contraction rules stay on ASCII bytes ('s 't 're ... are ASCII, and 0x27 is no part of a longer
+// sequence), with kLetter / kDigit of the neighbours from the table: "é's" cuts like "e's", U+2019 + s is no contraction.
+BPE_HD bool is_start_utf8(const uint8_t* t, const uint8_t* class_at, int n, int p) {
+    const int kc = class_at[p];
+    if (kc & kContByte) return false;
+    if (p == 0) return true;
+    const uint8_t d = t[p - 1];
+    const int k = kc & kClassMask, kd = class_at[p - 1] & kClassMask;
+    if (k == kWs) {
+        if (kd != kWs) return true;                             // a whitespace run begins
+        const int q = p + char_len(t[p]);                       // "\s+(?!\S)" gives the run's last CHARACTER back to what follows
+        return q < n && (class_at[q] & kClassMask) != kWs;
+    }
+    if (kd == kWs) return d != 0x20;                            // " ?X+" takes one 0x20 in front: the byte, no other whitespace
+    if (k != kd)
+        return !(d == '\'' && k == kLetter && apos_start_utf8(t, class_at, p - 1) && contraction_len(t, n, p - 1) != 0);
+    if (k == kLetter) {                                         // a contraction's letters are ASCII: p - 2 / p - 3 are byte offsets
+        if (p >= 2 && t[p - 2] == '\'' && apos_start_utf8(t, class_at, p - 2) && contraction_len(t, n, p - 2) == 2) return true;
+        if (p >= 3 && t[p - 3] == '\'' && apos_start_utf8(t, class_at, p - 3) && contraction_len(t, n, p - 3) == 3) return true;
+    }
+    return false;
+}
+
+// class_at[0, n) of the text c[0, n); false = NOT DONE (malformed UTF-8 or a host-only code point; class_at is then undefined)
+inline bool classify_text(const Unicode& u, const uint8_t* c, int n, uint8_t* class_at) {
+    for (int p = 0; p < n;) {
+        uint32_t cp;
+        const int len = decode_utf8(c + p, n - p, cp);
+        if (len == 0) return false;
+        const int e = entry_of(u, cp);
+        if (e & kHostOnly) return false;
+        class_at[p] = (uint8_t)(e & kClassMask);
+        for (int i = 1; i < len; ++i) class_at[p + i] = (uint8_t)((e & kClassMask) | kContByte);
+        p += len;
+    }
+    return true;
+}
+
+// encode_text over is_start_utf8: one text on one thread, any pre-token length.  c[0, n) with the prefix space in place;
+// class_at: n bytes of work space.  Returns the number of ids written, or -1: NOT DONE (nothing of `out` is then meaningful).
+inline int encode_text_utf8(const Table& t, const Unicode& u, const uint8_t* c, int n, int room, int64_t* out, uint8_t* class_at,
+                            int32_t* id_at, int32_t* next_at, int32_t* rank_at, int32_t* mid_at) {
+    if (!classify_text(u, c, n, class_at)) return -1;
+    int total = 0;
+    for (int p0 = 0; p0 < n && total < room;) {
+        int p1 = p0 + 1;
+        while (p1 < n && !is_start_utf8(c, class_at, n, p1)) ++p1;
+        for (int i = p0; i < p1; ++i) { id_at[i] = t.byte_id[c[i]]; next_at[i] = i + 1; }
+        auto pair_of = [&](int i) {                             // as in encode_text
             rank_at[i] = kNoRank;
             const int j = next_at[i];
             if (j < p1) {

@@ -142,7 +142,7 @@ bool first_call_on_device(std::atomic<unsigned long long>& done) {
 
 extern "C" const char* ac_last_error(void) { return ac::g_err; }
 
-extern "C" int ac_version(void) { return 16; }    // 16: ac_gemm_f16x2_launches (diagnostic counter of the GEMM launches on fp16x2 operand planes); 15: ac_unigram_unicode, ac_unigram_encode_utf8[_host] (Unigram on UTF-8 text, words of any length); 14: ac_wordpiece_unicode, ac_wordpiece_encode_utf8[_host] (WordPiece on UTF-8 text); 13: ac_unigram_vocab, ac_unigram_hash, ac_unigram_encode[_host] (Unigram tokenizers on the device); 12: ac_bert_weights grew attn_disentangled in front of attn_rel_bias (ac_bert_disentangled, ac_bert_disentangled_scratch: DeBERTa-v2/v3); 11: ac_bert_weights grew a trailing attn_rel_bias / rel_span (relative position bias of the self-attention: MPNet); 10: byte-level BPE tokenisation (ac_bpe_vocab, ac_bpe_encode, ac_bpe_encode_host, ac_bpe_pair_hash); 9: ac_bert_config / ac_modernbert_config grew a trailing pool_opt (AC_POOL_*: masked mean pooling); 8: range search over the prepared store (ac_knn_*_range_count_batch[_sel], ac_knn_range_batch_workspace); 2: the inner-product search (ac_knn_ip_topk*, ac_topk_merge_ip_f64); 3: its prepared-store form (ac_knn_ip_topk_batch*); 4: range search (ac_knn_*_range_*); 5: filtered search (ac_knn_*_topk_sel / _ids, ac_knn_sel_*); 6: its prepared-store form (ac_knn_*_topk_batch_sel); 7: filtered range search (ac_knn_*_range_count_sel, ac_knn_*_range_*_ids)
+extern "C" int ac_version(void) { return 17; }    // 17: ac_bpe_unicode, ac_bpe_utf8_encode[_host] (byte-level BPE on UTF-8 text); 16: ac_gemm_f16x2_launches (diagnostic counter of the GEMM launches on fp16x2 operand planes); 15: ac_unigram_unicode, ac_unigram_encode_utf8[_host] (Unigram on UTF-8 text, words of any length); 14: ac_wordpiece_unicode, ac_wordpiece_encode_utf8[_host] (WordPiece on UTF-8 text); 13: ac_unigram_vocab, ac_unigram_hash, ac_unigram_encode[_host] (Unigram tokenizers on the device); 12: ac_bert_weights grew attn_disentangled in front of attn_rel_bias (ac_bert_disentangled, ac_bert_disentangled_scratch: DeBERTa-v2/v3); 11: ac_bert_weights grew a trailing attn_rel_bias / rel_span (relative position bias of the self-attention: MPNet); 10: byte-level BPE tokenisation (ac_bpe_vocab, ac_bpe_encode, ac_bpe_encode_host, ac_bpe_pair_hash); 9: ac_bert_config / ac_modernbert_config grew a trailing pool_opt (AC_POOL_*: masked mean pooling); 8: range search over the prepared store (ac_knn_*_range_count_batch[_sel], ac_knn_range_batch_workspace); 2: the inner-product search (ac_knn_ip_topk*, ac_topk_merge_ip_f64); 3: its prepared-store form (ac_knn_ip_topk_batch*); 4: range search (ac_knn_*_range_*); 5: filtered search (ac_knn_*_topk_sel / _ids, ac_knn_sel_*); 6: its prepared-store form (ac_knn_*_topk_batch_sel); 7: filtered range search (ac_knn_*_range_count_sel, ac_knn_*_range_*_ids)
 
 extern "C" int ac_device_info(int* cu_count, int* lds_bytes_per_block, size_t* hbm_bytes) {
     const ac::DevInfo& d = ac::dev_info();

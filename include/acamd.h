@@ -1321,6 +1321,42 @@ int ac_bpe_encode_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
                        const ac_bpe_vocab* vocab, int max_length,
                        int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
 
+/* The classes of the GPT-2 pre-tokeniser pattern as a table over the code points U+0000 .. U+10FFFF, built by the host wrapper by
+ * probing the wrapped tokenizers pipeline (tokenizer.py build_bpe_unicode_tables; no Unicode data lives in this library).
+ * page_of[cp >> 8] names a page of 256 one-byte entries, identical pages stored once.  An entry:
+ *   bits 0-1   the class of the code point in the pattern: 0 whitespace (\s), 1 letter (\p{L}), 2 number (\p{N}), 3 other
+ *   bit 2      host-only: the pipeline's normalizer (NFC) changes the code point or may combine it with a neighbour -- the
+ *              device does no normalisation, so a text that holds one comes back NOT DONE
+ * A page number outside the table reads as host-only.
+ * Device pointers for ac_bpe_utf8_encode, host pointers for ac_bpe_utf8_encode_host.  (ac_version() >= 17) */
+typedef struct ac_bpe_unicode {
+    const uint16_t* page_of;    /* [0x1100] page of the code points cp with cp >> 8 == index */
+    const uint8_t* entries;     /* [n_pages][256] */
+    int n_pages;                /* 1 .. 65535 */
+} ac_bpe_unicode;
+
+/*
+ * ac_bpe_encode for UTF-8 texts.  `vocab` is the ac_bpe_vocab of ac_bpe_encode (the merges work on raw bytes).  The text is
+ * decoded strictly, every character gets its class from `unicode`, the pre-tokeniser pattern is applied on characters (the seven
+ * contractions stay ASCII; "one space in front" stays the byte 0x20) and every pre-token goes through the merges byte by byte.
+ * (The names do not start with ac_bpe_encode on purpose: the ASCII entries keep that prefix to themselves.)
+ *   d_lens   int32 [b] as for ac_bpe_encode, or -1: NOT DONE -- the text is not well-formed UTF-8 (an overlong form, an encoded
+ *            surrogate, a value above U+10FFFF, a stray continuation byte, a truncated tail), holds a host-only code point, has
+ *            more than 4096 bytes or holds a pre-token of more than 64 bytes.  Its rows of d_ids / d_mask are not written; nothing
+ *            is read past a text's own end and the other rows are unaffected.
+ * Literal special / added-token strings are the caller's to route, as for ac_bpe_encode.
+ */
+int ac_bpe_utf8_encode(const uint8_t* d_text, const int32_t* d_offsets, int b,
+                       const ac_bpe_vocab* vocab, const ac_bpe_unicode* unicode, int max_length,
+                       int64_t* d_ids, int64_t* d_mask, int32_t* d_lens, ac_stream_t stream);
+
+/* The same routines (csrc/bpe_core.h) text by text on the CPU: host pointers everywhere, no GPU call, exact for every pre-token
+ * length (a long pre-token is NOT a reason for -1 here; the other three are).  The wrapper's probe guard and the CPU tests run
+ * on it. */
+int ac_bpe_utf8_encode_host(const uint8_t* h_text, const int32_t* h_offsets, int b,
+                            const ac_bpe_vocab* vocab, const ac_bpe_unicode* unicode, int max_length,
+                            int64_t* h_ids, int64_t* h_mask, int32_t* h_lens);
+
 /* A SentencePiece-style Unigram vocabulary (DeBERTa-v2/v3 and XLM-R style tokenizers: tokenizers Metaspace(always) + Unigram)
  * as an open-addressing hash table over its PURE-ASCII pieces, built by the host wrapper and filled to at most half: slot of a
  * piece = (h ^ (h >> 32)) & (slots - 1), linear probing, h = ac_unigram_hash(piece bytes).  The metaspace is stored as the byte
